@@ -7,13 +7,18 @@ limb-transforms, 360 MiB, i.e. larger than the 256 MiB MALL, so every step strea
 reference call nwt_2d_radix8_forward_inplace(data, tables, 45, 0) (src/ntt/fntt_2d.cu:620-653) applied to every
 polynomial of the batch in one launch pair (pha_nwt_2d_radix8_forward_inplace_batched; the reference's own
 ntt_bench sweeps the limbs per launch the same way, benchmark/ntt_bench.cu:104-117).  `value` is
-limb-transforms per second over all ranks.  The same line also carries
+limb-transforms per second over all ranks, `ms_per_step` the wall time of one of the --steps timed steps.
+
+A plain run does only that: set up, warm up, time the steps, write the outputs (--dump-outputs DIR) and print the line.
+With --full the run first times the CPU baseline and then measures, after the headline, what the line also carries:
   * single_polynomial: the r01 protocol (one 45-limb polynomial per launch pair), in place (MALL-resident) and
     rotating over the 16 buffers (HBM-resident),
   * HomMul + relinearize + rescale per second for the same parameter set, alone and batched,
   * keyswitch_c4: BASELINE config 4 -- BFV relinearize + Galois rotate at N = 2^15, 30 + 15 limbs, a batch of 64
     ciphertexts split over the ranks (strong scaling), with a checksum that is the same for every world size,
-  * the roofline object of the forward NTT and the CPU baseline (the oracle, timed on host cores).
+  * the roofline object of the forward NTT (calibration streams, per-step events, sustained leg, offline traffic) and the
+    CPU baseline (the oracle, timed on host cores),
+and writes the full record to --full-out.
 
 Multi-GPU: independent ciphertexts shard across ranks (no data-path collective); evaluation / Galois keys are
 generated on rank 0 and broadcast once over RCCL (setup, not timed).  `python bench.py --gpus N` without a
@@ -105,6 +110,27 @@ def uniform_residues(primes, n, device, gen):
     for i, q in enumerate(primes):
         out[i] = torch.randint(0, int(q), (n,), dtype=torch.int64, device=device, generator=gen)
     return out
+
+
+DUMP_COLUMNS = 1024      # coefficient positions per limb that --dump-outputs writes (16 x 45 x 1024 words: 5.9 MB per file)
+DUMP_SEED = 0xD0        # seed of that sample of positions
+
+
+def write_outputs(out_dir, polys):
+    """--dump-outputs: the batch the timed path left in place ([polynomials][limbs][N] residues, what a caller of
+    pha_nwt_2d_radix8_forward_inplace_batched receives), at DUMP_COLUMNS positions drawn once from DUMP_SEED and shared by every
+    limb, as [polynomials][limbs][DUMP_COLUMNS] float64 arrays.  A residue has up to 60 bits and float64 keeps 53, so beside the
+    rounded value (ntt_output.npy) every word is also written exactly, as its two 32-bit halves (ntt_output_hi32 / _lo32.npy)."""
+    import numpy as np
+    import torch
+    n = polys.shape[-1]
+    cols = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=min(DUMP_COLUMNS, n), replace=False))
+    x = polys.index_select(polys.dim() - 1, torch.as_tensor(cols, device=polys.device)).cpu()
+    arrays = {"ntt_output": x, "ntt_output_hi32": x >> 32, "ntt_output_lo32": x & 0xFFFFFFFF}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.to(torch.float64).numpy())
+    return sorted(arrays)
 
 
 def cpu_baseline(primes, n, seconds=12.0, gpu_forward=None):
@@ -346,22 +372,30 @@ def preflight(args, P, pdist, torch, dist, dev, world, rank, share, force_dist, 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=int, default=100, help="timed steps (K)")
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: CPU baseline, calibration, per-step events, sustained, single-"
+                         "polynomial, HomMul, config-4 / config-5 and BFV / GEMM legs, and write the full record to --full-out")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's batch, a fixed sample of positions) "
+                         "as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline and the config-4 oracle check")
     ap.add_argument("--graph", action="store_true", help="replay the K steps from one hipGraph")
     ap.add_argument("--no-graph", action="store_true", help="enqueue the K steps one by one from Python")
-    ap.add_argument("--only-ntt", action="store_true", help="skip the HomMul and config-4 / config-5 legs (profiling runs)")
-    ap.add_argument("--no-c5", action="store_true", help="skip the config-5 leg (23 GB of Galois keys)")
+    ap.add_argument("--only-ntt", action="store_true", help="--full without the HomMul and config-4 / config-5 legs (profiling runs)")
+    ap.add_argument("--no-c5", action="store_true", help="--full without the config-5 leg (23 GB of Galois keys)")
     ap.add_argument("--sustain", type=float, default=6.0,
-                    help="seconds of back-to-back headline steps AFTER the K timed ones (a sustained figure, and a GPU that the "
-                         "driver's utilisation sampler can see); 0 = off")
+                    help="--full: seconds of back-to-back headline steps AFTER the K timed ones (a sustained figure, and a GPU "
+                         "that a utilisation sampler can see); 0 = off")
     ap.add_argument("--full-out", default=os.path.join("gpurun_out", "bench_full.json"),
                     help="where the FULL record goes (sweeps, notes, calibration streams); stdout carries one compact line")
     ap.add_argument("--preflight", action="store_true",
                     help="first-contact check of an N-GPU run (devices, memory budget, RCCL init, a 64 MiB trial broadcast through "
                          "both key-broadcast paths); prints one JSON line and exits")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))
@@ -425,6 +459,13 @@ def main():
         if world > 1 or force_dist:
             dist.barrier()
 
+    def close_group():
+        if world > 1 or force_dist:
+            if not share:
+                torch.cuda.synchronize()
+            dist.barrier()                  # the other ranks leave only after rank 0 has printed the line
+            dist.destroy_process_group()
+
     # r06: every multi-rank run starts with the first-contact checks (devices, memory, the communicator's own rank count, a trial
     # broadcast through both key paths) and REFUSES, with one JSON line and exit code 1, instead of timing a broken group
     preflight_rec = None
@@ -447,7 +488,7 @@ def main():
     #      times it (reported at N = 1 by contract; for N > 1 the other ranks wait at the barrier below, so that every rank ramps
     #      its clocks at the same moment afterwards).
     cpu_line = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if rank == 0 and args.full and not args.no_cpu_baseline:
         def gpu_forward(host_poly):   # the product path on the baseline's own input
             d = P.to_device(host_poly, dev)
             ctx.nwt_2d_radix8_forward_inplace(d, 45, 0)
@@ -503,6 +544,9 @@ def main():
     def ntt_step():
         ctx.nwt_2d_radix8_forward_inplace_batched(polys, size_q, 0, nb, poly_stride)
 
+    # the steps transform in place, and the clock ramp below runs for a time, not a count: the timed steps start again from the
+    # seeded batch, so that what they compute depends only on the arguments
+    seeded = polys.clone()
     for _ in range(args.warmup):
         ntt_step()
     torch.cuda.synchronize()
@@ -530,6 +574,8 @@ def main():
         g.replay()                   # one untimed replay (warm instantiation)
         torch.cuda.synchronize()
         graph = g
+    polys.copy_(seeded)
+    del seeded
     barrier()
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     t0 = time.perf_counter()
@@ -546,6 +592,30 @@ def main():
     elapsed = pdist.max_over_ranks(time.perf_counter() - t0, device=red_dev)
     kernel_ms = e0.elapsed_time(e1) / args.steps      # average duration of one launch pair inside the timed region
     ntt_per_s = world * args.steps * nb * size_q / elapsed
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, polys)
+    alg_bytes = 16.0 * n * size_q * nb             # 8 B read + 8 B write per coefficient
+    achieved = alg_bytes / (kernel_ms * 1e-3)
+    head = {
+        "metric": "forward NTT limb-transforms/s at N=2^16, 45 RNS moduli",
+        "value": ntt_per_s, "unit": "NTT/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "u64", "data": "synthetic",
+        "config": {"workload": f"CKKS N=2^16, 45 data limbs (+15 special), forward NTT of a batch of {nb} ciphertext "
+                               f"polynomials per step ({nb * size_q} limb-transforms, {nb * size_q * n * 8 >> 20} MiB, "
+                               "HBM-resident; configs[2] parameter set)",
+                   "N": n, "limbs": size_q, "special_limbs": SIZE_P, "polynomials_per_step": nb,
+                   "parallelism": f"ciphertext-batch x{world}",
+                   "launch": ("hipGraph replay of the K steps" if graph is not None else "K steps enqueued one by one from Python"
+                              if args.no_graph else "K steps enqueued by one library call (2 K eager kernel launches)"),
+                   "untimed_clock_ramp_steps": ramp_steps}}
+    if not args.full:
+        if rank == 0:
+            head["roofline"] = {"bound": "hbm", "achieved": achieved / 1e9, "peak": PEAK_HBM / 1e9, "unit": "GB/s",
+                                "frac": achieved / PEAK_HBM, "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": kernel_ms}
+            print(json.dumps(head, separators=(",", ":")), flush=True)
+        close_group()
+        return
     step_stats = per_step_events(ntt_step, max(100, args.steps) if not small else 10)
 
     # ---- sustained (r05): the same step back to back for --sustain seconds, in chunks of 100 steps enqueued by one library call
@@ -934,27 +1004,13 @@ def main():
         del gkeys, glks, blocks5, res5, pool5, flat5
 
     if rank == 0:
-        alg_bytes = 16.0 * n * size_q * nb             # 8 B read + 8 B write per coefficient
-        achieved = alg_bytes / (kernel_ms * 1e-3)
         one = 16.0 * n * size_q
         traffic, traffic_ref = load_record(TRAFFIC_FILE)
         traffic = traffic or {}
         # two in-place passes: every coefficient is read and written twice, so the algorithmic rate cannot exceed half the rate of an
         # in-place read-modify-write stream (r04: measured with the calibration kernels, not with the r01-r03 grid-stride copy)
         ceiling = cal["rmw_GBps"] * 1e9 / 2.0 / PEAK_HBM
-        full = {
-            "metric": "forward NTT limb-transforms/s at N=2^16, 45 RNS moduli",
-            "value": ntt_per_s, "unit": "NTT/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None, "dtype": "u64", "data": "synthetic",
-            "config": {"workload": f"CKKS N=2^16, 45 data limbs (+15 special), forward NTT of a batch of {nb} ciphertext "
-                                   f"polynomials per step ({nb * size_q} limb-transforms, {nb * size_q * n * 8 >> 20} MiB, "
-                                   "HBM-resident; configs[2] parameter set)",
-                       "N": n, "limbs": size_q, "special_limbs": SIZE_P, "polynomials_per_step": nb,
-                       "parallelism": f"ciphertext-batch x{world}",
-                       "launch": ("hipGraph replay of the K steps" if graph is not None else "K steps enqueued one by one from Python"
-                                  if args.no_graph else "K steps enqueued by one library call (2 K eager kernel launches)"),
-                       "untimed_clock_ramp_steps": ramp_steps},
+        full = dict(head, **{
             "roofline": {"bound": "hbm", "achieved": achieved / 1e9, "peak": PEAK_HBM / 1e9, "unit": "GB/s",
                          "frac": achieved / PEAK_HBM,
                          "traffic": traffic.get("ntt_batched_bytes_per_launch"),
@@ -1005,7 +1061,7 @@ def main():
             "key_broadcast_path": pdist.LAST_BROADCAST_PATH,
             "collectives": ("RCCL (torch.distributed backend nccl)" if (world > 1 or force_dist) and not share else
                             "gloo (PHA_BENCH_SHARE_GPU)" if share and world > 1 else "none (one rank, no process group)"),
-        }
+        })
         if hm is not None:
             if traffic.get("hommul_bytes_per_op"):
                 hm["traffic"] = traffic["hommul_bytes_per_op"]
@@ -1028,11 +1084,7 @@ def main():
         except OSError as e:               # a read-only tree must not cost the line
             full_path = f"not written: {e}"
         print(compact_line(full, full_path), flush=True)
-    if world > 1 or force_dist:
-        if not share:
-            torch.cuda.synchronize()
-        dist.barrier()                  # the other ranks leave only after rank 0 has printed the line
-        dist.destroy_process_group()
+    close_group()
 
 
 if __name__ == "__main__":

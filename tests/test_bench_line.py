@@ -57,3 +57,26 @@ def test_an_oversized_record_sheds_optional_legs_instead_of_breaking_the_line():
     full["keyswitch_c4"] = dict(full["keyswitch_c4"] or {}, checked="x" * 9000)
     d = json.loads(bench.compact_line(full, "f.json"))
     assert isinstance(d["keyswitch_c4"], str) and d["keyswitch_c4"].startswith("dropped") and "roofline" in d and "cpu_baseline" in d
+
+
+def test_dump_outputs_writes_an_exact_fixed_sample_in_float64(tmp_path):
+    """--dump-outputs (bench.write_outputs, checked here on a host tensor): float64 files within 64 MB, the same positions in every
+    run, and the 64-bit words recoverable exactly from their two 32-bit halves even where float64 rounds the value itself."""
+    import numpy as np
+    import torch
+    n = 1 << 13
+    g = torch.Generator().manual_seed(7)
+    polys = torch.randint(0, (1 << 60) - 93, (2, 3, n), generator=g, dtype=torch.int64)
+    names = bench.write_outputs(str(tmp_path / "a"), polys)
+    assert names == ["ntt_output", "ntt_output_hi32", "ntt_output_lo32"]
+    bench.write_outputs(str(tmp_path / "b"), polys)
+    got = {k: np.load(tmp_path / "a" / (k + ".npy")) for k in names}
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    for k in names:
+        assert got[k].dtype == np.float64 and got[k].shape == (2, 3, bench.DUMP_COLUMNS)
+        assert np.array_equal(got[k], np.load(tmp_path / "b" / (k + ".npy")))
+    cols = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n, size=bench.DUMP_COLUMNS, replace=False))
+    want = polys.numpy().astype(np.uint64)[:, :, cols]
+    words = (got["ntt_output_hi32"].astype(np.uint64) << np.uint64(32)) | got["ntt_output_lo32"].astype(np.uint64)
+    assert np.array_equal(words, want)
+    assert np.allclose(got["ntt_output"], want.astype(np.float64), rtol=0, atol=0)

@@ -24,7 +24,7 @@ def _run(extra_args, full=True, **extra_env):
     with tempfile.TemporaryDirectory() as tmp:
         path = os.path.join(tmp, "full.json")
         pre = "--preflight" in extra_args
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra_args + ([] if pre else ["--full-out", path]),
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + extra_args + ([] if pre else ["--full", "--full-out", path]),
                              capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
         assert out.returncode == 0, out.stdout + out.stderr
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -38,6 +38,58 @@ def _run(extra_args, full=True, **extra_env):
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "scaling", "dtype"):   # same run, same numbers
         assert line[k] == record[k] or abs(line[k] - record[k]) <= 1e-5 * abs(record[k]), k
     return record if full else line
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_what_it_computed(gpu, tmp_path):
+    """A plain run (no --full): one line with the headline keys and none of the --full legs, --steps timed steps, and with
+    --dump-outputs the batch the last timed step left: the same in two runs, and equal to the oracle's forward NTT applied
+    --steps times to the seeded input (so the warm-up and clock-ramp steps do not leak into it)."""
+    import numpy as np
+    import torch
+
+    import bench
+    import phantom_fhe_amd as P
+    from oracle import oracle as O
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    names = ("ntt_output", "ntt_output_hi32", "ntt_output_lo32")
+    lines, dumps = [], []
+    for i in range(2):
+        out_dir = tmp_path / f"out{i}"
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2",
+                              "--dump-outputs", str(out_dir)], capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+        assert out.returncode == 0, out.stdout + out.stderr
+        js = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert len(js) == 1, out.stdout + out.stderr
+        lines.append(json.loads(js[0]))
+        dumps.append({k: np.load(out_dir / (k + ".npy")) for k in names})
+    d = lines[0]
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
+                "vs_baseline", "dtype", "data", "config", "roofline"):
+        assert key in d, key
+    assert d["n_gpus"] == 1 and d["steps"] == 3 and d["warmup"] == 2 and d["higher_is_better"] is True and d["dtype"] == "u64"
+    for key in ("cpu_baseline", "single_polynomial_us", "hommul_relin_rescale", "keyswitch_c4", "matvec_c5", "full_record"):
+        assert key not in d, key
+    per_step = d["config"]["polynomials_per_step"] * 45
+    assert abs(d["value"] - per_step / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    nb, n = d["config"]["polynomials_per_step"], 1 << bench.LOG_N
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+    for k in names:
+        assert dumps[0][k].dtype == np.float64 and dumps[0][k].shape == (nb, 45, bench.DUMP_COLUMNS)
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+    words = (dumps[0]["ntt_output_hi32"].astype(np.uint64) << np.uint64(32)) | dumps[0]["ntt_output_lo32"].astype(np.uint64)
+    assert np.array_equal(words.astype(np.float64), dumps[0]["ntt_output"])
+    # the seeded input of polynomial 0, drawn as bench.py draws it, through the oracle three times
+    primes = [int(p) for p in P.coeff_modulus_create(n, bench.BITS)][:45]
+    gen = torch.Generator(device=gpu)
+    gen.manual_seed(0x5EED0000 + 3)
+    x = bench.uniform_residues(primes, n, gpu, gen).cpu().numpy().astype(np.uint64)
+    oc = O.Ctx(bench.LOG_N, primes, 0)
+    for _ in range(3):
+        x = oc.nwt_forward(x, 45, 0)
+    cols = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(n, size=bench.DUMP_COLUMNS, replace=False))
+    assert np.array_equal(words[0], x[:, cols])
 
 
 def test_bench_compact_line(gpu):

@@ -10,7 +10,7 @@ OUT=$R/gpurun_out
 TAG=${TAG:-r06}
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_trace -o trace -- python $R/bench.py --steps 50 --warmup 5 --no-cpu-baseline --no-c5 > $OUT/prof_trace.log 2>&1
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_trace -o trace -- python $R/bench.py --full --steps 50 --warmup 5 --no-cpu-baseline --no-c5 > $OUT/prof_trace.log 2>&1
 timeout 200 rocprofv3 --kernel-trace --output-format csv -d $OUT/prof_stage -o trace -- python $R/tools/traffic_probe.py hommul > $OUT/prof_stage.log 2>&1
 python $R/tools/stage_table.py $OUT/prof_stage $OUT/stages.json > $OUT/${TAG}_stages.txt 2>&1
 for B in 8 32; do
@@ -19,7 +19,7 @@ done
 python $R/tools/stage_table_batched.py $OUT/stages_batched.json 8=$OUT/prof_hb8 32=$OUT/prof_hb32 > $OUT/${TAG}_stages_batched.txt 2>&1
 pmc() {   # name, counters...
   local name=$1; shift
-  timeout 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/prof_pmc_$name/ntt -o pmc -- python $R/bench.py --only-ntt --steps 4 --warmup 1 --no-cpu-baseline --no-graph > $OUT/prof_pmc_$name.log 2>&1
+  timeout 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/prof_pmc_$name/ntt -o pmc -- python $R/bench.py --full --only-ntt --steps 4 --warmup 1 --no-cpu-baseline --no-graph > $OUT/prof_pmc_$name.log 2>&1
   timeout 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/prof_pmc_$name/ops -o pmc -- python $R/tools/traffic_probe.py hommul >> $OUT/prof_pmc_$name.log 2>&1
   timeout 300 rocprofv3 --pmc "$@" --output-format csv -d $OUT/prof_pmc_$name/hb -o pmc -- python $R/tools/traffic_probe.py hommul_batched:8 >> $OUT/prof_pmc_$name.log 2>&1
 }
@@ -33,10 +33,10 @@ bash $R/tools/traffic.sh > $OUT/${TAG}_traffic.txt 2>&1
 # the bench line LAST, with the records of THIS run in place: bench.py attaches profiles/{traffic,stages,stages_batched}.json with their sha, and
 # tools/collect_profiles.sh copies the same three files from gpurun_out/ into profiles/ of the build container afterwards
 cp $OUT/traffic.json $OUT/stages.json $OUT/stages_batched.json $R/profiles/ 2>/dev/null
-# r06: the DRIVER'S OWN COMMAND; stdout must be ONE JSON line of at most 8000 bytes that json.loads; the full record
+# r06: the bench command with every leg (--full); stdout must be ONE JSON line of at most 8000 bytes that json.loads; the full record
 # (what r01-r05 printed) goes to the file named in the line
 cd $R
-timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full-out $OUT/${TAG}_bench_full.json > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
+timeout 900 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full --full-out $OUT/${TAG}_bench_full.json > $OUT/${TAG}_bench_line.json 2> $OUT/${TAG}_bench.err
 python3 - <<PY
 import json
 raw = open("$OUT/${TAG}_bench_line.json").read()
