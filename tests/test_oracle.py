@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from util import C1_PRIMES, brev, crt_compose, oracle_ctx, primes_of, rng_for, uniform_poly
+from util import BETA_GT4_LEVELS, C1_PRIMES, brev, crt_compose, oracle_ctx, primes_of, rng_for, uniform_poly
 
 
 def test_reference_kats_from_survey():
@@ -667,3 +667,18 @@ def test_every_literal_default_prime_of_the_reference_is_an_ntt_prime_for_the_or
         assert np.array_equal(c.nwt_backward(c.nwt_forward(x, len(ps), 0), len(ps), 0), x)
         for i, q in enumerate(ps):
             assert pow(O.minimal_primitive_root(2 * n, q), n, q) == q - 1
+
+
+@pytest.mark.parametrize("name", sorted(BETA_GT4_LEVELS))
+def test_parameter_sets_with_more_than_four_digits_construct(name):
+    """The beta > 4 sets of tests/test_gpu_batched_dispatch.py: the chain builds, every listed level has a tool, and the tool
+    reports the digit count the GPU cases rely on (beta = ceil(size_Ql / alpha)) -- on both sides of the beta <= 4 dispatch."""
+    log_n, primes, size_p = primes_of(name)
+    assert len(set(primes)) == len(primes) and all((int(p) - 1) % (2 << log_n) == 0 for p in primes)
+    oc = oracle_ctx(name)
+    for ql, beta in BETA_GT4_LEVELS[name].items():
+        assert 1 <= ql <= len(primes) - size_p
+        tool = O.Tool(oc, ql)
+        assert tool.beta == beta == -(-ql // size_p), (name, ql)
+        assert tool.size_qlp == ql + size_p
+    assert max(BETA_GT4_LEVELS[name].values()) > 4 and size_p > 1

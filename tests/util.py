@@ -25,6 +25,18 @@ CONFIGS = {
     "wide_p20": (12, [45] * 24 + [46] * 20, 20),           # 17..32 special primes: the 30 / 31-bit split converter (two digits: 20 + 4 limbs)
     "p61_a2": (12, [50] * 6 + [61, 61], 2),               # 61-bit special primes: 30 / 31 cuts in mod-up, 31 / 30 in mod-down
     "bfv13_50": (13, [50] * 4 + [60, 60], 2),             # uniform data primes: what the HPS variant of BFV multiply needs
+    # more than four key-switch digits with alpha > 1 (tests/test_gpu_batched_dispatch.py): the unfused mod-up + inner product of one
+    # ciphertext, the per-ciphertext inner product loop of a batch, the mod-up that copies the digits' own limbs
+    "hyb13_b5": (13, [60] + [50] * 9 + [60] * 2, 2),      # 10 data limbs: beta 5 at levels 10 and 9 (short last digit), 4 at level 8
+    "hyb14_b6": (14, [60] + [50] * 11 + [60] * 2, 2),     # beta 6 at N = 2^14, a size whose fused mod-up + inner product stops at beta 4
+    "hyb16_b5": (16, [60] + [50] * 44 + [60] * 9, 9),     # 45 data limbs in 5 digits of 9 at N = 2^16: the 16-input fused mod-up conversion with 9 live inputs; beta 5 at levels 45 and 37 (one-limb last digit), 4 at level 36
+}
+
+# (config, live data limbs) -> number of key-switch digits, for the sets above
+BETA_GT4_LEVELS = {
+    "hyb13_b5": {10: 5, 9: 5, 8: 4, 1: 1},
+    "hyb14_b6": {12: 6, 8: 4},
+    "hyb16_b5": {45: 5, 37: 5, 36: 4},
 }
 
 
