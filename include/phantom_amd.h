@@ -397,6 +397,24 @@ int pha_bfv_multiply_hps_overq_leveled(pha_context_t ctx, size_t size_Ql, const 
  * never leaves level l, so the result differs (in its noise) from multiply followed by the leveled key switch. dst [2][Q][N] */
 int pha_bfv_mul_relin_hps_overq_leveled(pha_context_t ctx, size_t size_Ql, const uint64_t *ct1, const uint64_t *ct2,
                                         const uint64_t *const *rlk, uint64_t *dst, void *stream);
+/* Extension (the reference loops over ciphertexts): the BFV multiplies over a batch of independent ciphertext pairs.
+ * ct1, ct2 [batch][2][Q][N] -> dst [batch][3][Q][N] (the ct3 layout of pha_relinearize_rotate_batched), coefficient form over
+ * the full base Q, canonical.  Ciphertext b of dst is bit-identical to what the matching single-pair entry returns for pair b.
+ * `chunk` pairs (0 = the library's default, 8) go through one set of launches whose count does not depend on chunk, with no
+ * device-to-device copies; the scratch is sized by chunk, not by batch, and every chunk gives the same bits.  ct1 == ct2 (the
+ * same pointer) takes the squaring path for the whole batch (for hps_overq: the reference's squaring shortcut, as the single
+ * entry keeps it).  The inputs are only read; dst overlapping an input is refused (status -1), as are null pointers, a missing
+ * plain modulus and size_Ql outside [1, |Q|]; batch == 0 does nothing.  Unlike the single entries these check both operands in
+ * strict mode ("<entry> ct1" / "<entry> ct2").  More than 32 limbs in a conversion's input base: those conversions run per
+ * polynomial (bConv_HPS's second branch), everything else stays batched.
+ *   pha_bfv_multiply_hps_overq_batched: size_Ql == |Q| is hps_overq, size_Ql < |Q| is hps_overq_leveled with |Q| - size_Ql
+ *   levels dropped (pha_bfv_multiply_hps_overq_leveled). */
+int pha_bfv_multiply_behz_batched(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst, size_t batch,
+                                  size_t chunk, void *stream);
+int pha_bfv_multiply_hps_batched(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst, size_t batch,
+                                 size_t chunk, void *stream);
+int pha_bfv_multiply_hps_overq_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct1, const uint64_t *ct2,
+                                       uint64_t *dst, size_t batch, size_t chunk, void *stream);
 int pha_scaleAndRound_HPS_Q_Ql(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream);
 int pha_ExpandCRTBasis_Ql_Q(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream);
 int pha_keyswitch_inplace_bfv_leveled(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const uint64_t *c2,

@@ -20,6 +20,7 @@ struct MrqArgs {
     const u64x2 *inv_mt_mod_bsk;
     u64x2 neg_inv_prod_q_mod_mt;
     uint32_t aux0, size_bsk, n;
+    size_t dst_stride = 0;   // words between the polynomials of dst (0 = packed, size_bsk * n)
 };
 __global__ __launch_bounds__(256) void sm_mrq_kernel(const MrqArgs k) {
     const uint32_t j = blockIdx.y, coeff = blockIdx.x * 256 + threadIdx.x;
@@ -33,7 +34,8 @@ __global__ __launch_bounds__(256) void sm_mrq_kernel(const MrqArgs k) {
     const u64 x = in[(size_t)j * k.n + coeff];
     lo += x;
     hi += lo < x;
-    k.dst[((size_t)blockIdx.z * k.size_bsk + j) * k.n + coeff] = shoup(barrett128(lo, hi, m), k.inv_mt_mod_bsk[j], m.value);
+    const size_t dz = k.dst_stride ? k.dst_stride : (size_t)k.size_bsk * k.n;
+    k.dst[(size_t)blockIdx.z * dz + (size_t)j * k.n + coeff] = shoup(barrett128(lo, hi, m), k.inv_mt_mod_bsk[j], m.value);
 }
 
 // second half of bconv_fuse_sub_mul_unroll2_kernel rns.cu:1343-1386: (x_Bsk + (p - conv)) * prod(q)^-1 mod p
@@ -421,10 +423,11 @@ struct ExpandArgs {
     const u64 *c, *c_shoup;
     const DModulus *mod;
     uint32_t size_ql, n;
+    size_t poly_stride = 0;   // polynomial blockIdx.z of dst and src
 };
 __global__ __launch_bounds__(256) void hps_expand_kernel(const ExpandArgs k) {
     const uint32_t i = blockIdx.y, coeff = blockIdx.x * 256 + threadIdx.x;
-    const size_t id = (size_t)i * k.n + coeff;
+    const size_t id = blockIdx.z * k.poly_stride + (size_t)i * k.n + coeff;
     k.dst[id] = i < k.size_ql ? shoup(k.src[id], u64x2{k.c[i], k.c_shoup[i]}, k.mod[i].value) : 0;
 }
 static void launch_scale_round_q(Context &c, u64 *dst, const u64 *src, const double *frac, const u64 *tab, uint32_t size_ql,
@@ -448,9 +451,9 @@ static void launch_scale_round_q(Context &c, u64 *dst, const u64 *src, const dou
 #undef PHA_SRQ
     check_launch();
 }
-static void launch_expand(Context &c, HpsQ &h, u64 *dst, const u64 *src, hipStream_t s) {
-    ExpandArgs ka{dst, src, h.drop_mod_q.p, h.drop_mod_q_shoup.p, c.d_mod.p, h.size_q, (uint32_t)c.n};
-    hipLaunchKernelGGL(hps_expand_kernel, dim3((unsigned)(c.n / 256), h.size_q_full), dim3(256), 0, s, ka);
+static void launch_expand(Context &c, HpsQ &h, u64 *dst, const u64 *src, hipStream_t s, uint32_t batch = 1, size_t poly_stride = 0) {
+    ExpandArgs ka{dst, src, h.drop_mod_q.p, h.drop_mod_q_shoup.p, c.d_mod.p, h.size_q, (uint32_t)c.n, poly_stride};
+    hipLaunchKernelGGL(hps_expand_kernel, dim3((unsigned)(c.n / 256), h.size_q_full, batch), dim3(256), 0, s, ka);
     check_launch();
 }
 
@@ -632,6 +635,208 @@ extern "C" int pha_bfv_multiply_behz(pha_context_t ctx, const uint64_t *ct1, con
     SkArgs ka{dst, msk, fl + (size_t)sb * n, c.d_mod.p, b.prod_b_mod_q.p, b.inv_prod_b_mod_msk, b.m_sk, n, qn, n, bn};
     hipLaunchKernelGGL(sk_fix_kernel, dim3(n / 256, sq, 3), dim3(256), 0, s, ka);
     check_launch();
+    PHA_API_END
+}
+
+// ---- batched BFV multiplies (extension: the reference loops over ciphertexts) -------------------------------------------------
+// ct1, ct2 [batch][2][Q][N] -> dst [batch][3][Q][N], the ct3 layout of pha_relinearize_rotate_batched.  A chunk of C pairs goes
+// through ONE set of launches: every stage covers its 2C or 3C polynomials (blockIdx.z, or y for the scale-and-round kernels), so the
+// launch count does not depend on C, and there are no device-to-device copies.  Working buffers per chunk, L = |Q| + |aux| limbs:
+//   xa [C][2][L][N] | xb [C][2][L][N] | xp [C][3][L][N] | stage scratch
+// The operands' Q limbs are produced by the forward transform reading the caller's ciphertext out of place, the auxiliary limbs by
+// the conversion straight into place; the tensor product writes xp (its [3]-polynomial pitch is what every later stage and dst
+// share), in one launch over the Q rows and the auxiliary rows (launch_tensor_batched).  Every stage computes per coefficient
+// exactly what the single-pair entries compute, so ciphertext b of the result has the single entry's bits for pair b.
+//
+// Default pairs per chunk.  Measured at config 4 (N = 2^15, 30 data limbs, t = 1032193; B = 64, profiles/bfv_multiply_batched.md): per-op
+// time falls steeply from chunk 1 to 4 (HPS 0.376 -> 0.264 ms) and stays within 3 % from 4 to 64; 8 is the fastest for BEHZ (0.3005 ms)
+// and over-Q (0.2382) and 1.3 % behind 16 for HPS (0.2627 against 0.2592), with a working set of about 1 GB instead of 2.
+constexpr size_t kBfvBatchChunk = 8;
+constexpr size_t kBfvMaxChunk = 1024;   // 3 * chunk polynomials ride in grid z / y (limit 65535)
+
+static bool bfv_overlaps(const u64 *a, size_t na, const u64 *b, size_t nb) { return a < b + nb && b < a + na; }
+
+// refusals and strict checks shared by the three entries; returns the pairs per chunk
+static size_t bfv_batched_begin(Context &c, const char *name, const u64 *ct1, const u64 *ct2, const u64 *dst, size_t batch,
+                                size_t chunk, hipStream_t s) {
+    const size_t qn = (size_t)c.size_q * c.n;
+    if (bfv_overlaps(dst, batch * 3 * qn, ct1, batch * 2 * qn) || bfv_overlaps(dst, batch * 3 * qn, ct2, batch * 2 * qn))
+        throw std::invalid_argument("dst must not overlap ct1 or ct2");
+    if (strict_mode()) {   // large batches in pieces of at most 65534 polynomials (grid z); never skipped
+        const std::string n1 = std::string(name) + " ct1", n2 = std::string(name) + " ct2";
+        for (size_t b0 = 0; b0 < batch; b0 += 32767) {
+            const uint32_t polys = (uint32_t)(2 * std::min<size_t>(32767, batch - b0));
+            strict_operand(c, n1.c_str(), ct1 + b0 * 2 * qn, rows_plain(0, c.size_q), polys, qn, s);
+            if (ct2 != ct1) strict_operand(c, n2.c_str(), ct2 + b0 * 2 * qn, rows_plain(0, c.size_q), polys, qn, s);
+        }
+    }
+    if (chunk == 0) chunk = kBfvBatchChunk;
+    return std::min(std::min(chunk, batch), kBfvMaxChunk);
+}
+
+static LimbSel qr_tail_sel(uint32_t size_q, uint32_t size_r, uint32_t aux0) {  // the auxiliary limbs of a [Q || aux] buffer
+    LimbSel s = qr_sel(size_q, size_r, aux0);
+    s.start = size_q;
+    s.count = size_r;
+    return s;
+}
+
+// forward transform of the Q limbs of `polys` polynomials, ct [.][Q_in][N] -> x [.][L][N], out of place
+static void lift_q_ntt(Context &c, const u64 *ct, size_t ct_stride, u64 *x, size_t x_stride, uint32_t sq, uint32_t polys, hipStream_t s) {
+    NttExtra xq;
+    xq.batch = polys;
+    xq.poly_stride = x_stride;
+    xq.in_stride = ct_stride;
+    ntt_forward(c, ct, x, x, plain_sel(0, sq), EPI_FWD_CANON, xq, s);
+}
+
+extern "C" int pha_bfv_multiply_hps_batched(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst,
+                                            size_t batch, size_t chunk, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
+    if (batch == 0) return 0;
+    Context &c = ctx->c;
+    Hps &h = c.hps();
+    hipStream_t s = as_stream(stream);
+    const size_t C = bfv_batched_begin(c, "bfv_multiply_hps_batched", ct1, ct2, dst, batch, chunk, s);
+    const uint32_t n = (uint32_t)c.n, sq = h.size_q, sr = h.size_r, sqr = sq + sr;
+    const size_t qn = (size_t)sq * n, rn = (size_t)sr * n, qrn = (size_t)sqr * n;
+    const bool square = ct1 == ct2;
+    // scratch: xa [C][2][Q+R] | xb [C][2][Q+R] | xp [C][3][Q+R] | tmp [C][3][R] | y [max(Q, R)] (wide bases only)
+    u64 *xa = c.scratch(stream, C * (7 * qrn + 3 * rn) + std::max(qn, rn));
+    u64 *xb = xa + C * 2 * qrn, *xp = xb + C * 2 * qrn, *tmp = xp + C * 3 * qrn, *y = tmp + C * 3 * rn;
+    for (size_t b0 = 0; b0 < batch; b0 += C) {
+        const uint32_t B = (uint32_t)std::min(C, batch - b0);
+        // lift every input polynomial from base Q to Q || R (evaluate.cu:702-716, :733-748)
+        for (int w = 0; w < (square ? 1 : 2); w++) {
+            const u64 *ct = (w ? ct2 : ct1) + b0 * 2 * qn;
+            u64 *x = w ? xb : xa;
+            lift_q_ntt(c, ct, qn, x, qrn, sq, 2 * B, s);
+            bconv_hps(c, h.q_to_r, h.d_q_to_r.p, h.q_inv.p, h.alpha_q_mod_r.p, x + qn, ct, y, s, 2 * B, qrn, qn);
+            NttExtra xr;
+            xr.batch = 2 * B;
+            xr.poly_stride = qrn;
+            ntt_forward(c, x, x, x, qr_tail_sel(sq, sr, h.aux0), EPI_FWD_CANON, xr, s);
+        }
+        launch_tensor_batched(c, xa, square ? xa : xb, xp, sqr, sq, h.aux0 - sq, square, B, s);
+        NttExtra xi;
+        xi.batch = 3 * B;
+        xi.poly_stride = qrn;
+        ntt_inverse(c, xp, xp, xp, qr_sel(sq, sr, h.aux0), EPI_INV_CANON, xi, s);
+        // scale by t/Q and round into base R, then R -> Q (evaluate.cu:800-808)
+        ScaleRoundArgs ka{tmp, xp, h.frac.p, h.div_mod_r.p, c.d_mod.p, sq, sr, h.aux0, n, rn, qrn};
+        launch_scale_round(c, ka, s, 3 * B);
+        bconv_hps(c, h.r_to_q, h.d_r_to_q.p, h.r_inv.p, h.alpha_r_mod_q.p, dst + b0 * 3 * qn, tmp, y, s, 3 * B, qn, rn);
+    }
+    PHA_API_END
+}
+
+extern "C" int pha_bfv_multiply_hps_overq_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct1, const uint64_t *ct2,
+                                                  uint64_t *dst, size_t batch, size_t chunk, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
+    Context &c = ctx->c;
+    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("RNSBase is invalid");
+    if (batch == 0) return 0;
+    HpsQ &h = c.hps_overq((uint32_t)size_Ql);
+    hipStream_t s = as_stream(stream);
+    const size_t C = bfv_batched_begin(c, "bfv_multiply_hps_overq_batched", ct1, ct2, dst, batch, chunk, s);
+    const uint32_t n = (uint32_t)c.n, sq = h.size_q, sr = h.size_r, sqr = sq + sr, sqf = h.size_q_full;
+    const size_t qn = (size_t)sq * n, rn = (size_t)sr * n, qrn = (size_t)sqr * n, qfn = (size_t)sqf * n;
+    const bool square = ct1 == ct2;
+    // scratch: xa [C][2][Ql+Rl] | xb [C][2][Ql+Rl] | xp [C][3][Ql+Rl] | y [max(Q, Rl)] (wide bases only)
+    u64 *xa = c.scratch(stream, C * 7 * qrn + std::max(qfn, rn));
+    u64 *xb = xa + C * 2 * qrn, *xp = xb + C * 2 * qrn, *y = xp + C * 3 * qrn;
+    NttExtra xf;
+    xf.poly_stride = qrn;
+    for (size_t b0 = 0; b0 < batch; b0 += C) {
+        const uint32_t B = (uint32_t)std::min(C, batch - b0);
+        const u64 *in1 = ct1 + b0 * 2 * qfn, *in2 = ct2 + b0 * 2 * qfn;
+        xf.batch = 2 * B;
+        // first operand: (scaled down to Ql when levels are dropped, :709-710) exact lift to Ql || Rl
+        if (h.drop) {
+            launch_scale_round_q(c, xa, in1, h.frac_drop.p, h.div_mod_q_drop.p, sq, h.drop, s, 2 * B, qrn, qfn);
+            bconv_hps(c, h.q_to_r, h.d_q_to_r.p, h.q_inv.p, h.alpha_q_mod_r.p, xa + qn, xa, y, s, 2 * B, qrn, qrn);
+            ntt_forward(c, xa, xa, xa, qr_sel(sq, sr, h.aux0), EPI_FWD_CANON, xf, s);
+        } else {
+            lift_q_ntt(c, in1, qfn, xa, qrn, sq, 2 * B, s);
+            bconv_hps(c, h.q_to_r, h.d_q_to_r.p, h.q_inv.p, h.alpha_q_mod_r.p, xa + qn, in1, y, s, 2 * B, qrn, qfn);
+            ntt_forward(c, xa, xa, xa, qr_tail_sel(sq, sr, h.aux0), EPI_FWD_CANON, xf, s);
+        }
+        if (!square) {   // second operand: Q -> Rl by bConv_BEHZ_var1, then Rl -> Ql exactly (:745-751)
+            launch_bconv(c, h.d_q_to_r_var1.p, 0, 2 * B, h.q_to_r_var1.isz, sr, h.q_to_r_var1.split_kind, xb + qn, qrn, in2, qfn, nullptr,
+                         true, s);
+            bconv_hps(c, h.r_to_q, h.d_r_to_q.p, h.r_inv.p, h.alpha_r_mod_q.p, xb, xb + qn, y, s, 2 * B, qrn, qrn);
+            ntt_forward(c, xb, xb, xb, qr_sel(sq, sr, h.aux0), EPI_FWD_CANON, xf, s);
+        }
+        launch_tensor_batched(c, xa, square ? xa : xb, xp, sqr, sq, h.aux0 - sq, square, B, s);
+        NttExtra xi;
+        xi.batch = 3 * B;
+        xi.poly_stride = qrn;
+        ntt_inverse(c, xp, xp, xp, qr_sel(sq, sr, h.aux0), EPI_INV_CANON, xi, s);
+        // scale by t / Rl and round straight into base Ql (:790-792), expand to Q (:794-795)
+        u64 *out = dst + b0 * 3 * qfn;
+        launch_scale_round_q(c, out, xp, h.frac.p, h.div_mod_q.p, sq, sr, s, 3 * B, qfn, qrn);
+        if (h.drop) launch_expand(c, h, out, out, s, 3 * B, qfn);
+    }
+    PHA_API_END
+}
+
+extern "C" int pha_bfv_multiply_behz_batched(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst,
+                                             size_t batch, size_t chunk, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
+    if (batch == 0) return 0;
+    Context &c = ctx->c;
+    Behz &b = c.behz();
+    hipStream_t s = as_stream(stream);
+    const size_t C = bfv_batched_begin(c, "bfv_multiply_behz_batched", ct1, ct2, dst, batch, chunk, s);
+    const uint32_t n = (uint32_t)c.n, sq = b.size_q, sk = b.size_bsk, sb = b.size_b, sqk = sq + sk;
+    const size_t qn = (size_t)sq * n, bn = (size_t)sk * n, qbn = (size_t)sqk * n;
+    const bool square = ct1 == ct2;
+    // scratch: xa [C][2][Q+Bsk] | xb [C][2][Q+Bsk] | xp [C][3][Q+Bsk] | tmp (lift [C][2][Bsk+1], later conv / floor / m_sk)
+    const size_t tmp_words = std::max(2 * (bn + n), 6 * bn + 3 * (size_t)n);
+    u64 *xa = c.scratch(stream, C * (7 * qbn + tmp_words));
+    u64 *xb = xa + C * 2 * qbn, *xp = xb + C * 2 * qbn, *tmp = xp + C * 3 * qbn;
+    for (size_t b0 = 0; b0 < batch; b0 += C) {
+        const uint32_t B = (uint32_t)std::min(C, batch - b0);
+        // BEHZ_mul_1 (evaluate.cu:404-441) for the 2 B polynomials of each operand, as behz_lift
+        for (int w = 0; w < (square ? 1 : 2); w++) {
+            const u64 *ct = (w ? ct2 : ct1) + b0 * 2 * qn;
+            u64 *x = w ? xb : xa;
+            lift_q_ntt(c, ct, qn, x, qbn, sq, 2 * B, s);
+            launch_bconv(c, b.d_q_to_bskmt.p, 0, 2 * B, sq, sk + 1, b.q_to_bskmt.split_kind, tmp, (size_t)(sk + 1) * n, ct, qn, nullptr,
+                         true, s);
+            MrqArgs ma{x + qn, tmp, c.d_mod.p, b.prod_q_mod_bsk.p, b.inv_mt_mod_bsk.p, b.neg_inv_prod_q_mod_mt, b.aux0, sk, n, qbn};
+            hipLaunchKernelGGL(sm_mrq_kernel, dim3(n / 256, sk, 2 * B), dim3(256), 0, s, ma);
+            check_launch();
+            NttExtra xk;
+            xk.batch = 2 * B;
+            xk.poly_stride = qbn;
+            ntt_forward(c, x, x, x, qr_tail_sel(sq, sk, b.aux0), EPI_FWD_CANON, xk, s);
+        }
+        // step 4: tensor product in both bases (evaluate.cu:479-498), steps 5-6: inverse transforms fused with the multiplication by t
+        launch_tensor_batched(c, xa, square ? xa : xb, xp, sqk, sq, b.aux0 - sq, square, B, s);
+        NttExtra xi;
+        xi.batch = 3 * B;
+        xi.poly_stride = qbn;
+        xi.scale = b.t_qb.p;
+        xi.scale_shoup = b.t_qb_shoup.p;
+        ntt_inverse(c, xp, xp, xp, qr_sel(sq, sk, b.aux0), EPI_INV_SCALE, xi, s);
+        u64 *conv = tmp, *fl = tmp + (size_t)B * 3 * bn, *msk = fl + (size_t)B * 3 * bn;  // conv, fl [3B][Bsk][N], msk [3B][N]
+        u64 *out = dst + b0 * 3 * qn;
+        // step 7 fast_floor (rns.cu:1394-1419)
+        launch_bconv(c, b.d_q_to_bsk.p, 0, 3 * B, sq, sk, b.q_to_bsk.split_kind, conv, bn, xp, qbn, nullptr, true, s);
+        FloorArgs fa{fl, xp + qn, conv, c.d_mod.p, b.inv_prod_q_mod_bsk.p, b.aux0, n, bn, qbn, bn};
+        hipLaunchKernelGGL(fast_floor_kernel, dim3(n / 256, sk, 3 * B), dim3(256), 0, s, fa);
+        check_launch();
+        // step 8 fastbconv_sk (rns.cu:1470-1510)
+        launch_bconv(c, b.d_b_to_msk.p, 0, 3 * B, sb, 1, b.b_to_msk.split_kind, msk, n, fl, bn, nullptr, true, s);   // B -> m_sk
+        launch_bconv(c, b.d_b_to_q.p, 0, 3 * B, sb, sq, b.b_to_q.split_kind, out, qn, fl, bn, nullptr, true, s);
+        SkArgs ka{out, msk, fl + (size_t)sb * n, c.d_mod.p, b.prod_b_mod_q.p, b.inv_prod_b_mod_msk, b.m_sk, n, qn, n, bn};
+        hipLaunchKernelGGL(sk_fix_kernel, dim3(n / 256, sq, 3 * B), dim3(256), 0, s, ka);
+        check_launch();
+    }
     PHA_API_END
 }
 

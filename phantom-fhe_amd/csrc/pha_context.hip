@@ -648,6 +648,14 @@ Behz &Context::behz() {
         b->prod_b_mod_q.upload(pb);
         b->t_q.upload(tq);
         b->t_q_shoup.upload(tqs);
+        // the same scales by limb of a [Q || Bsk] buffer (batched multiply: one inverse transform over both bases)
+        std::vector<u64> tqb(tq), tqbs(tqs);
+        for (uint32_t j = 0; j < b->size_bsk; j++) {
+            tqb.push_back(plain_t);
+            tqbs.push_back(h_shoup(plain_t, primes[b->aux0 + j]));
+        }
+        b->t_qb.upload(tqb);
+        b->t_qb_shoup.upload(tqbs);
     }
     const u64 inv_q_mt = h_invmod(prod_mod(0, size_q, m_tilde), m_tilde);
     b->neg_inv_prod_q_mod_mt = pair((m_tilde - inv_q_mt) % m_tilde, m_tilde);

@@ -182,6 +182,7 @@ struct Behz {
     DevBuf<u64> prod_q_mod_bsk;                          // [Bsk]
     DevBuf<u64> prod_b_mod_q;                            // [Q]
     DevBuf<u64> t_q, t_q_shoup, t_bsk, t_bsk_shoup;      // t with its Shoup quotient per limb (iNTT scale)
+    DevBuf<u64> t_qb, t_qb_shoup;                        // the same over [Q || Bsk] (batched multiply)
     u64x2 neg_inv_prod_q_mod_mt{}, inv_prod_b_mod_msk{};
 };
 
@@ -433,6 +434,8 @@ void build_bconv_var1(Context &c, BConv &b, const std::vector<uint32_t> &ip, con
 void describe_conv(const BConv &b, DevBuf<BConvDev> &out);
 void launch_tensor(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, size_t mod_start, bool square,
                    hipStream_t s, size_t poly_limbs = 0);
+void launch_tensor_batched(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, uint32_t remap_from, uint32_t remap_add,
+                           bool square, size_t batch, hipStream_t s);
 void launch_add(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, size_t mod_start, hipStream_t s);
 
 void register_context(Context *c, bool alive);   // live-context list walked by the per-thread arena reaper

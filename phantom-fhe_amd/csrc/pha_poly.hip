@@ -21,6 +21,7 @@ struct EwArgs {
     uint32_t poly_limbs;  // limbs between two polynomials of a ciphertext (0 = limbs)
     size_t za, zb, zr, zr2;   // blockIdx.z (batched tensor product): elements between consecutive ciphertexts of a / b / r / r2
     const FpInfo *fpinfo;     // [prime]: limbs below 2^50 form the tensor product in FP64 (r04)
+    uint32_t remap_from, remap_add;   // limbs >= remap_from use table row mod_start + limb + remap_add ([Q || R] buffers, as LimbSel; 0, 0 = off)
 };
 
 // EW_TENSOR_NT (r06): the tensor product of a BATCH of ciphertexts: every word is read once and written once and the batch is larger
@@ -51,7 +52,8 @@ __device__ __forceinline__ void st2(u64 *p, u64x2 v) {
 template <int OP>
 __global__ __launch_bounds__(kEwThreads) void ew_kernel(const EwArgs k) {
     const uint32_t limb = blockIdx.y;
-    const DModulus m = k.mod[k.mod_start + limb];
+    const uint32_t row = k.mod_start + limb + (limb >= k.remap_from ? k.remap_add : 0);
+    const DModulus m = k.mod[row];
     const u64 q = m.value;
     const size_t idx = (size_t)limb * k.n + ((size_t)blockIdx.x * kEwThreads + threadIdx.x) * kEwPerThread;
     const size_t rc = (size_t)(k.poly_limbs ? k.poly_limbs : k.limbs) * k.n;  // stride between the polynomials of a ciphertext
@@ -87,9 +89,9 @@ __global__ __launch_bounds__(kEwThreads) void ew_kernel(const EwArgs k) {
         constexpr bool NT = OP == EW_TENSOR_NT;
         u64x2 c00 = ld2<NT>(ka + idx), c01 = ld2<NT>(ka + idx + rc), c10 = ld2<NT>(kb + idx), c11 = ld2<NT>(kb + idx + rc);
         u64x2 d0, d1, d2;
-        if (k.fpinfo && k.fpinfo[k.mod_start + limb].ok) {   // (uniform) r04: three exact FP64 products (fp_tensor_2x2, pha_arith.h) instead of
+        if (k.fpinfo && k.fpinfo[row].ok) {   // (uniform) r04: three exact FP64 products (fp_tensor_2x2, pha_arith.h) instead of
             // three Barrett-128 multiplies on 32-bit halves (~115 vector instructions per coefficient -> ~50); the same residues as :487-:494
-            const FpInfo fi = k.fpinfo[k.mod_start + limb];
+            const FpInfo fi = k.fpinfo[row];
             const FpMod fm{fi.q, fi.qinv, false, false};
             u64 e[6];
             fp_tensor_2x2(c00.x, c01.x, c10.x, c11.x, fm, e[0], e[1], e[2]);
@@ -111,18 +113,21 @@ __global__ __launch_bounds__(kEwThreads) void ew_kernel(const EwArgs k) {
         st2<NT>(kr + idx + rc, d1);
         st2<NT>(kr2 ? kr2 + idx : kr + idx + 2 * rc, d2);
     } else if (OP == EW_SQUARE) {  // tensor_square_2x2_rns_poly :500-529
-        u64x2 c0 = ld2(k.a + idx), c1 = ld2(k.a + idx + rc);
+        const size_t z = blockIdx.z;   // a batch of ciphertexts (za = zr = 0 for one)
+        const u64 *ka = k.a + z * k.za;
+        u64 *kr = k.r + z * k.zr;
+        u64x2 c0 = ld2(ka + idx), c1 = ld2(ka + idx + rc);
         u64x2 d0, d1, d2;
-        if (k.fpinfo && k.fpinfo[k.mod_start + limb].ok) {   // (uniform) the FP64 form: c0^2, 2 c0 c1, c1^2 (fp_square_2x2)
-            const FpInfo fi = k.fpinfo[k.mod_start + limb];
+        if (k.fpinfo && k.fpinfo[row].ok) {   // (uniform) the FP64 form: c0^2, 2 c0 c1, c1^2 (fp_square_2x2)
+            const FpInfo fi = k.fpinfo[row];
             const FpMod fm{fi.q, fi.qinv, false, false};
             u64 e[6];
             fp_square_2x2(c0.x, c1.x, fm, e[0], e[1], e[2]);
             fp_square_2x2(c0.y, c1.y, fm, e[3], e[4], e[5]);
             d0 = u64x2{e[0], e[3]}; d1 = u64x2{e[1], e[4]}; d2 = u64x2{e[2], e[5]};
-            st2(k.r + idx, d0);
-            st2(k.r + idx + rc, d1);
-            st2(k.r + idx + 2 * rc, d2);
+            st2(kr + idx, d0);
+            st2(kr + idx + rc, d1);
+            st2(kr + idx + 2 * rc, d2);
             return;
         }
         d0.x = mul_mod(c0.x, c0.x, m); d0.y = mul_mod(c0.y, c0.y, m);
@@ -132,9 +137,9 @@ __global__ __launch_bounds__(kEwThreads) void ew_kernel(const EwArgs k) {
         mul128(c0.y, c1.y, lo, hi);
         d1.y = barrett128(lo << 1, (hi << 1) | (lo >> 63), m);
         d2.x = mul_mod(c1.x, c1.x, m); d2.y = mul_mod(c1.y, c1.y, m);
-        st2(k.r + idx, d0);
-        st2(k.r + idx + rc, d1);
-        st2(k.r + idx + 2 * rc, d2);
+        st2(kr + idx, d0);
+        st2(kr + idx + rc, d1);
+        st2(kr + idx + 2 * rc, d2);
     }
 }
 
@@ -168,6 +173,33 @@ void launch_tensor(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs,
     k.mod_start = (uint32_t)mod_start;
     dim3 grid((unsigned)(c.n / (kEwThreads * kEwPerThread)), (unsigned)limbs);
     if (square) hipLaunchKernelGGL((ew_kernel<EW_SQUARE>), grid, dim3(kEwThreads), 0, s, k);
+    else hipLaunchKernelGGL((ew_kernel<EW_TENSOR>), grid, dim3(kEwThreads), 0, s, k);
+    check_launch();
+}
+
+// Batched BFV multiply (pha_behz.hip): the tensor product of `batch` ciphertext pairs over [Q || aux] working buffers in ONE launch.
+// a, b: [batch][2][limbs][N]; r: [batch][3][limbs][N]; limbs >= remap_from take table row limb + remap_add (LimbSel's remap), so
+// the Q rows and the auxiliary rows (R or Bsk) need no launch of their own.  From two pairs on the streams are nontemporal
+// (EW_TENSOR_NT above); squaring (a == b) reads each operand once.
+void launch_tensor_batched(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, uint32_t remap_from, uint32_t remap_add,
+                           bool square, size_t batch, hipStream_t s) {
+    if (limbs == 0 || batch == 0) return;
+    if (batch > 65535) throw std::invalid_argument("batch out of range");
+    const size_t last = limbs - 1 + (limbs - 1 >= remap_from ? remap_add : 0);
+    if (last >= c.rows || (remap_from && remap_from - 1 >= c.rows)) throw std::invalid_argument("modulus index out of range");
+    EwArgs k{};
+    k.a = a; k.b = b; k.r = r;
+    k.remap_from = remap_from;
+    k.remap_add = remap_add;
+    k.za = k.zb = 2 * limbs * c.n;
+    k.zr = 3 * limbs * c.n;
+    k.mod = c.d_mod.p;
+    k.fpinfo = c.d_fpinfo.p;
+    k.n = (uint32_t)c.n;
+    k.limbs = (uint32_t)limbs;
+    dim3 grid((unsigned)(c.n / (kEwThreads * kEwPerThread)), (unsigned)limbs, (unsigned)batch);
+    if (square) hipLaunchKernelGGL((ew_kernel<EW_SQUARE>), grid, dim3(kEwThreads), 0, s, k);
+    else if (batch >= 2) hipLaunchKernelGGL((ew_kernel<EW_TENSOR_NT>), grid, dim3(kEwThreads), 0, s, k);
     else hipLaunchKernelGGL((ew_kernel<EW_TENSOR>), grid, dim3(kEwThreads), 0, s, k);
     check_launch();
 }

@@ -356,6 +356,40 @@ class PhantomContext:
         """bfv_multiply_hps under hps_overq_leveled with size_Q - size_Ql levels dropped; buffers over the full base Q."""
         _lib.check(self._L.pha_bfv_multiply_hps_overq_leveled(self._h, size_Ql, _ptr(ct1), _ptr(ct2), _ptr(dst), _stream()))
 
+    def _bfv_batch(self, ct1, ct2, dst):
+        """Batch size of ct1, ct2 [B][2][Q][N] -> dst [B][3][Q][N] (None: the library refuses the null pointer)."""
+        if ct1 is None or ct2 is None or dst is None:
+            return 1
+        shape = (2, self.size_Q, self.n)
+        if ct1.dim() != 4 or tuple(ct1.shape[1:]) != shape or tuple(ct2.shape) != tuple(ct1.shape):
+            raise ValueError("ct1 and ct2 must be [batch][2][Q][N] with the same batch")
+        if tuple(dst.shape) != (ct1.shape[0], 3, self.size_Q, self.n):
+            raise ValueError("dst must be [batch][3][Q][N]")
+        return ct1.shape[0]
+
+    def bfv_multiply_behz_batched(self, ct1, ct2, dst, chunk=0):
+        """Extension: bfv_multiply_behz over a batch, ct1, ct2 [B][2][Q][N] -> dst [B][3][Q][N]; ciphertext b has the single
+        entry's bits.  `chunk` pairs per set of launches (0: the library's default); the same tensor twice squares."""
+        batch = self._bfv_batch(ct1, ct2, dst)
+        if batch == 0:      # an empty batch: nothing to do (empty tensors have no device pointer to hand over)
+            return
+        _lib.check(self._L.pha_bfv_multiply_behz_batched(self._h, _ptr(ct1), _ptr(ct2), _ptr(dst), batch, chunk, _stream()))
+
+    def bfv_multiply_hps_batched(self, ct1, ct2, dst, chunk=0):
+        """Extension: bfv_multiply_hps (mul_tech hps) over a batch; shapes and chunk as bfv_multiply_behz_batched."""
+        batch = self._bfv_batch(ct1, ct2, dst)
+        if batch == 0:      # an empty batch: nothing to do (empty tensors have no device pointer to hand over)
+            return
+        _lib.check(self._L.pha_bfv_multiply_hps_batched(self._h, _ptr(ct1), _ptr(ct2), _ptr(dst), batch, chunk, _stream()))
+
+    def bfv_multiply_hps_overq_batched(self, size_Ql, ct1, ct2, dst, chunk=0):
+        """Extension: hps_overq (size_Ql == |Q|) or hps_overq_leveled (size_Ql < |Q|) over a batch; buffers over the full base Q."""
+        batch = self._bfv_batch(ct1, ct2, dst)
+        if batch == 0:      # an empty batch: nothing to do (empty tensors have no device pointer to hand over)
+            return
+        _lib.check(self._L.pha_bfv_multiply_hps_overq_batched(self._h, size_Ql, _ptr(ct1), _ptr(ct2), _ptr(dst), batch, chunk,
+                                                              _stream()))
+
     def bfv_mul_relin_hps_overq_leveled(self, size_Ql, ct1, ct2, rlk_ptrs, dst):
         """bfv_mul_relin_hps with levels dropped (src/evaluate.cu:822-1027); dst [2][Q][N]."""
         _lib.check(self._L.pha_bfv_mul_relin_hps_overq_leveled(self._h, size_Ql, _ptr(ct1), _ptr(ct2), _ptr(rlk_ptrs), _ptr(dst), _stream()))

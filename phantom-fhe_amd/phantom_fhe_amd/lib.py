@@ -60,6 +60,9 @@ _SIGS = {
     "pha_bfv_multiply_hps_overq": [vp, vp, vp, vp, vp],
     "pha_bfv_multiply_hps_overq_leveled": [vp, sz, vp, vp, vp, vp],
     "pha_bfv_mul_relin_hps_overq_leveled": [vp, sz, vp, vp, vp, vp, vp],
+    "pha_bfv_multiply_behz_batched": [vp, vp, vp, vp, sz, sz, vp],
+    "pha_bfv_multiply_hps_batched": [vp, vp, vp, vp, sz, sz, vp],
+    "pha_bfv_multiply_hps_overq_batched": [vp, sz, vp, vp, vp, sz, sz, vp],
     "pha_scaleAndRound_HPS_Q_Ql": [vp, sz, vp, vp, vp],
     "pha_ExpandCRTBasis_Ql_Q": [vp, sz, vp, vp, vp],
     "pha_keyswitch_inplace_bfv_leveled": [vp, sz, vp, vp, vp, vp],
