@@ -324,6 +324,35 @@ int pha_keyswitch_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint6
  * res01 [batch][2][L][N] receives (c0, c1), res2 [batch][L][N] receives c2; res01 may alias operand1 */
 int pha_tensor_prod_2x2_batched(pha_context_t ctx, const uint64_t *operand1, const uint64_t *operand2, uint64_t *res01,
                                 uint64_t *res2, size_t coeff_mod_size, size_t batch, void *stream);
+/* Extension (no reference launcher; the reference composes tensor_prod_2x2_rns_poly src/polymath.cu:463-496 with
+ * add_rns_poly :41-56): for every g < batch
+ *   (res01[g][0], res01[g][1], res2[g]) = sum over k < terms of tensor_prod_2x2(op1[g][k], op2[g][k])
+ * operand ciphertext (g, k) of opX starts at opX + g * opX_batch_stride + k * opX_term_stride (64-bit words) and is
+ * [2][L][N], NTT form, canonical; res01 [batch][2][L][N], res2 [batch][L][N] (the layout of pha_tensor_prod_2x2_batched).
+ * One launch; the sums stay in registers and every output word is the canonical residue of the sum, so the result is word for
+ * word tensor_prod_2x2 followed by add in any order, and terms == 1 gives the words of pha_tensor_prod_2x2_batched.  A batch
+ * stride of 0 shares that operand between all groups (rows of a matrix against one vector).  Refused (status -1, nothing
+ * launched): terms == 0, coeff_mod_size out of range, an odd stride (16-byte loads), a term stride below 2 * L * N with
+ * terms > 1, an output that overlaps an operand ciphertext.  batch == 0 does nothing. */
+int pha_tensor_prod_2x2_sum_batched(pha_context_t ctx, const uint64_t *op1, const uint64_t *op2, uint64_t *res01, uint64_t *res2,
+                                    size_t coeff_mod_size, size_t terms, size_t batch,
+                                    size_t op1_term_stride, size_t op1_batch_stride,
+                                    size_t op2_term_stride, size_t op2_batch_stride, void *stream);
+/* Encrypted inner products with ONE key switch per sum (lazy relinearization), operands and strides as above with L = size_Ql.
+ * ckks: dst [batch][2][Ql-1][N] = rescale( S01[g] + keyswitch(S2[g]) ), S = the sum above; bit-identical to
+ * pha_tensor_prod_2x2_sum_batched followed by pha_keyswitch_rescale_batched.  `chunk` groups go through one set of launches
+ * (0: the library's default, 8); the working buffers are sized by the chunk and every chunk size gives the same bits.  The
+ * operands are only read; dst must not overlap them. */
+int pha_inner_product_relin_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *op1, const uint64_t *op2,
+                                            size_t terms, size_t batch, size_t op1_term_stride, size_t op1_batch_stride,
+                                            size_t op2_term_stride, size_t op2_batch_stride, const uint64_t *const *rlk,
+                                            uint64_t *dst, size_t chunk, void *stream);
+/* ckks / bgv, no rescale: dst [batch][2][Ql][N] = S01[g] + keyswitch(S2[g]) (pha_keyswitch_inplace_batched on dst, into which
+ * (c0, c1) of the sums are written directly).  bfv is refused: a bfv product is not an NTT-form tensor product. */
+int pha_inner_product_relin_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *op1, const uint64_t *op2, size_t terms,
+                                    size_t batch, size_t op1_term_stride, size_t op1_batch_stride, size_t op2_term_stride,
+                                    size_t op2_batch_stride, const uint64_t *const *rlk, int scheme, uint64_t *dst,
+                                    size_t chunk, void *stream);
 /* phantom::hoisting_inplace (include/evaluate.cuh:233-241, src/evaluate.cu:1670-1866) on raw buffers:
  * ct [2][Ql][N] <- sum over the n_elts Galois elements of rotate(ct).  galois_elts is a HOST array;
  * glk is a HOST array of n_elts DEVICE pointer tables (PhantomRelinKey::public_keys_ptr() of each

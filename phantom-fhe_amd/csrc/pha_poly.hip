@@ -3,6 +3,9 @@
 // Reference: src/polymath.cu (one coefficient per thread, `twr = tid / N`, DModulus re-read per
 // thread).  Here the limb is blockIdx.y, so the modulus and its Barrett ratio sit in SGPRs, and
 // every thread moves two adjacent coefficients with 16-byte accesses (pure HBM streaming).
+#include <algorithm>
+#include <cstdint>
+
 #include "../../include/phantom_amd.h"
 #include "pha_internal.h"
 
@@ -204,6 +207,142 @@ void launch_tensor_batched(Context &c, const u64 *a, const u64 *b, u64 *r, size_
     check_launch();
 }
 
+// ---- summed 2 x 2 tensor product (extension; lazy relinearization: sum the size-3 products, key-switch once per sum) ------------
+// For every group g = blockIdx.z: (res01[g][0], res01[g][1], res2[g]) = sum over k < terms of tensor_prod_2x2(a[g][k], b[g][k]), the
+// canonical residue of the sum in every word -- what tensor_prod_2x2_rns_poly (polymath.cu:463-496) followed by add_rns_poly
+// (:41-56) gives in any order of addition.  One launch; the limb is blockIdx.y (modulus in SGPRs), two adjacent coefficients per
+// thread, the loop over terms inside the thread.  Per term a thread reads four 16-byte words and writes nothing: the three sums stay
+// in registers and are reduced once per `per` terms, not once per term.
+//
+// With d0 = sum a0 b0, d2 = sum a1 b1 and M = sum (a0 + a1)(b0 + b1) as INTEGERS, d1 = M - d0 - d2 >= 0 exactly (Karatsuba on the
+// sums: three products per coefficient and term), so only the three final values are reduced.
+//
+// Integer limbs: 128-bit accumulators (mac128: v_mad_u64_u32 chains), one barrett128 per accumulator and flush -- it reduces ANY
+// 128-bit value (the quotient estimate floor(x floor(2^128 / q) / 2^128) is short by at most 1).  Terms per flush, for q < 2^b
+// (b = bit length of q, read from the modulus, not assumed): a0 + a1 and b0 + b1 are at most 2q - 2, one M product is at most
+// (2q - 2)^2 = 4q^2 - 8q + 4, and M restarts after a flush from r0 + r1 + r2 <= 3q - 3 (the residues it stands for), so after T
+// more terms M <= 3q + T (4q^2 - 8q + 4) < T 4q^2 < T 2^(2b + 2).  T = 2^(126 - 2b) keeps that below 2^128: 16 terms for the 61-bit
+// primes (p61_a2), 64 at 60 bits, 2^26 at 50 bits (capped at 2^20); d0 and d2 (products below q^2) are smaller still.
+//
+// FP64 limbs (fpinfo.ok: q < 2^50): every product is reduced on the spot by fp_mulmod_light to an exact integer of a few q, as in
+// fp_tensor_2x2 -- a double cannot hold the unreduced product -- and what is deferred is the re-centring and the canonical
+// conversion: the centred values are summed in doubles, exact while the magnitude stays below 2^53.  Bounds for q < 2^b, b <= 50:
+// a0 b0 and a1 b1 reduce to at most 0.875 q (pha_arith.h); for (a0 + a1)(b0 + b1), both factors below 2q, h = fl(Y W) < 2^(2b + 2),
+// the quotient rint(fl(h fl(1/q))) is off by at most 3 * 2^-53 * 4q + 0.5 <= 2 (q <= 2^50), so |h - c q| <= 2q, and the error term
+// l = Y W - h is at most ulp(h) / 2 <= 2^(2b - 52) <= q / 4: each M term is an exact integer of magnitude at most 2.25 q (2.5 q is
+// what the interval below allows for).  A flush is fp_reduce (|result| <= q / 2 + 1 for |x| < 2^52.6), so T terms after one leave
+// |M| <= q / 2 + 1 + T 2.5 q, and T = floor((14 * 2^(52 - b) - 6) / 25) keeps that below 1.4 * 2^52 < 2^52.5: 2 terms at 50 bits,
+// 4 at 49, 2293 at 40.  The last flush is followed by d1 = M - d0 - d2 (at most 1.5 q + 3) and fp_to_canon of the three.
+//
+// Loads are nontemporal: every operand word is read exactly once (B_NT = false: operand b is shared by all groups -- batch stride
+// 0 -- and keeps the default policy so that later groups may find it in the cache).  Stores follow EW_TENSOR_NT's rule by what reads
+// the result next, the key switch: a result the Infinity Cache holds (one ciphertext at C3, 71 MB) is stored with the default
+// policy, a larger one (ST_NT) streams past it.
+struct SumArgs {
+    const u64 *a, *b;
+    u64 *r01, *r2;
+    const DModulus *mod;
+    const FpInfo *fpinfo;
+    uint32_t n, limbs, terms;
+    size_t ta, za, tb, zb;   // words between consecutive terms / groups of a and b
+};
+
+__device__ __forceinline__ void sub128(u64 &lo, u64 &hi, u64 blo, u64 bhi) {   // (hi:lo) -= (bhi:blo), no borrow out
+    hi -= bhi + (lo < blo);
+    lo -= blo;
+}
+
+template <bool B_NT, bool ST_NT>
+__global__ __launch_bounds__(kEwThreads) void tensor_sum_kernel(const SumArgs k) {
+    const uint32_t limb = blockIdx.y;
+    const DModulus m = k.mod[limb];
+    const u64 q = m.value;
+    const size_t z = blockIdx.z;
+    const size_t idx = (size_t)limb * k.n + ((size_t)blockIdx.x * kEwThreads + threadIdx.x) * kEwPerThread;
+    const size_t rc = (size_t)k.limbs * k.n;
+    const u64 *pa = k.a + z * k.za + idx, *pb = k.b + z * k.zb + idx;
+    const int bits = 64 - __clzll((long long)q);   // q < 2^bits
+    u64x2 d0, d1, d2;
+    uint32_t t = 0;
+    if (k.fpinfo[limb].ok) {   // (uniform)
+        const FpInfo fi = k.fpinfo[limb];
+        const FpMod fm{fi.q, fi.qinv, false, false};
+        const u64 room = (14ull << (52 - bits)) - 6;          // bits <= 50
+        const uint32_t per = (uint32_t)(room / 25 < (1u << 20) ? room / 25 : (1u << 20));
+        double s0x = 0.0, s0y = 0.0, s2x = 0.0, s2y = 0.0, smx = 0.0, smy = 0.0;
+        do {
+            const uint32_t end = k.terms - t < per ? k.terms : t + per;
+#pragma unroll 2
+            for (; t < end; t++, pa += k.ta, pb += k.tb) {
+                const u64x2 c00 = ld2<true>(pa), c01 = ld2<true>(pa + rc), c10 = ld2<B_NT>(pb), c11 = ld2<B_NT>(pb + rc);
+                const double x0 = fp_from_canon(c00.x), x1 = fp_from_canon(c01.x), y0 = fp_from_canon(c10.x), y1 = fp_from_canon(c11.x);
+                s0x += fp_mulmod_light(x0, y0, fm);
+                s2x += fp_mulmod_light(x1, y1, fm);
+                smx += fp_mulmod_light(x0 + x1, y0 + y1, fm);
+                const double u0 = fp_from_canon(c00.y), u1 = fp_from_canon(c01.y), v0 = fp_from_canon(c10.y), v1 = fp_from_canon(c11.y);
+                s0y += fp_mulmod_light(u0, v0, fm);
+                s2y += fp_mulmod_light(u1, v1, fm);
+                smy += fp_mulmod_light(u0 + u1, v0 + v1, fm);
+            }
+            s0x = fp_reduce(s0x, fm); s0y = fp_reduce(s0y, fm);
+            s2x = fp_reduce(s2x, fm); s2y = fp_reduce(s2y, fm);
+            smx = fp_reduce(smx, fm); smy = fp_reduce(smy, fm);
+        } while (t < k.terms);
+        d0 = u64x2{fp_to_canon(s0x, fm), fp_to_canon(s0y, fm)};
+        d1 = u64x2{fp_to_canon(smx - s0x - s2x, fm), fp_to_canon(smy - s0y - s2y, fm)};
+        d2 = u64x2{fp_to_canon(s2x, fm), fp_to_canon(s2y, fm)};
+    } else {
+        const int sh = 126 - 2 * bits;
+        const uint32_t per = sh <= 0 ? 1u : (sh >= 20 ? 1u << 20 : 1u << sh);
+        u64 a0x = 0, a0y = 0, a2x = 0, a2y = 0, amx = 0, amy = 0;      // low words; high words below
+        u64 h0x = 0, h0y = 0, h2x = 0, h2y = 0, hmx = 0, hmy = 0;
+        for (;;) {
+            const uint32_t end = k.terms - t < per ? k.terms : t + per;
+#pragma unroll 2
+            for (; t < end; t++, pa += k.ta, pb += k.tb) {
+                const u64x2 c00 = ld2<true>(pa), c01 = ld2<true>(pa + rc), c10 = ld2<B_NT>(pb), c11 = ld2<B_NT>(pb + rc);
+                mac128(c00.x, c10.x, a0x, h0x);
+                mac128(c01.x, c11.x, a2x, h2x);
+                mac128(c00.x + c01.x, c10.x + c11.x, amx, hmx);   // unreduced sums, as polymath.cu:487 (q < 2^63)
+                mac128(c00.y, c10.y, a0y, h0y);
+                mac128(c01.y, c11.y, a2y, h2y);
+                mac128(c00.y + c01.y, c10.y + c11.y, amy, hmy);
+            }
+            sub128(amx, hmx, a0x, h0x); sub128(amx, hmx, a2x, h2x);   // d1 = M - d0 - d2 as integers
+            sub128(amy, hmy, a0y, h0y); sub128(amy, hmy, a2y, h2y);
+            d0 = u64x2{barrett128(a0x, h0x, m), barrett128(a0y, h0y, m)};
+            d1 = u64x2{barrett128(amx, hmx, m), barrett128(amy, hmy, m)};
+            d2 = u64x2{barrett128(a2x, h2x, m), barrett128(a2y, h2y, m)};
+            if (t >= k.terms) break;
+            // restart from the residues: d0, d2, and M = d0 + d1 + d2 (carried into the high word: 3q may pass 2^64 at 63 bits)
+            a0x = d0.x; a0y = d0.y; a2x = d2.x; a2y = d2.y;
+            h0x = h0y = h2x = h2y = 0;
+            amx = d0.x + d1.x; hmx = amx < d0.x; amx += d2.x; hmx += amx < d2.x;
+            amy = d0.y + d1.y; hmy = amy < d0.y; amy += d2.y; hmy += amy < d2.y;
+        }
+    }
+    u64 *r01 = k.r01 + z * 2 * rc + idx;
+    st2<ST_NT>(r01, d0);
+    st2<ST_NT>(r01 + rc, d1);
+    st2<ST_NT>(k.r2 + z * rc + idx, d2);
+}
+
+// results up to this size are left to the Infinity Cache (256 MB) for the key switch that reads them next; larger ones stream past
+constexpr size_t kSumCachedResultBytes = (size_t)128 << 20;
+
+// launch only: the callers have validated (sum_check below)
+static void launch_tensor_sum(Context &c, const u64 *op1, const u64 *op2, u64 *res01, u64 *res2, size_t cms, size_t terms, size_t batch,
+                              size_t t1, size_t b1, size_t t2, size_t b2, hipStream_t s) {
+    SumArgs k{op1, op2, res01, res2, c.d_mod.p, c.d_fpinfo.p, (uint32_t)c.n, (uint32_t)cms, (uint32_t)terms, t1, b1, t2, b2};
+    const dim3 grid((unsigned)(c.n / (kEwThreads * kEwPerThread)), (unsigned)cms, (unsigned)batch), block(kEwThreads);
+    const bool st_nt = batch * 3 * cms * c.n * sizeof(u64) > kSumCachedResultBytes, b_nt = !(b2 == 0 && batch > 1);
+    if (b_nt && st_nt) hipLaunchKernelGGL((tensor_sum_kernel<true, true>), grid, block, 0, s, k);
+    else if (b_nt) hipLaunchKernelGGL((tensor_sum_kernel<true, false>), grid, block, 0, s, k);
+    else if (st_nt) hipLaunchKernelGGL((tensor_sum_kernel<false, true>), grid, block, 0, s, k);
+    else hipLaunchKernelGGL((tensor_sum_kernel<false, false>), grid, block, 0, s, k);
+    check_launch();
+}
+
 // used by pha_rns.hip
 void launch_add(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, size_t mod_start, hipStream_t s) {
     EwArgs k{};
@@ -217,6 +356,73 @@ using namespace pha;
 
 static void need(const void *p) {
     if (!p) throw std::invalid_argument("null device pointer");
+}
+
+// ---- summed tensor product and the inner-product entries (extension) ------------------------------------------------------------
+static bool ranges_overlap(const u64 *a, size_t na, const u64 *b, size_t nb) { return a < b + nb && b < a + na; }
+
+// does out [out_words] touch any operand ciphertext (2 L N words at op + g * bs + k * ts)?  The span of all of them first: the
+// usual call is answered by one comparison
+static bool touches_operand(const u64 *out, size_t out_words, const u64 *op, size_t terms, size_t batch, size_t ts, size_t bs,
+                            size_t ct_words) {
+    const size_t groups = bs ? batch : 1;
+    if (!ranges_overlap(out, out_words, op, (groups - 1) * bs + (terms - 1) * ts + ct_words)) return false;
+    for (size_t g = 0; g < groups; g++)
+        for (size_t k = 0; k < terms; k++)
+            if (ranges_overlap(out, out_words, op + g * bs + k * ts, ct_words)) return true;
+    return false;
+}
+
+// the refusals the three entries share (everything but their outputs)
+static void sum_check(Context &c, const u64 *op1, const u64 *op2, size_t cms, size_t terms, size_t batch, size_t t1, size_t b1,
+                      size_t t2, size_t b2) {
+    if (terms == 0) throw std::invalid_argument("terms must be at least 1");
+    if (terms > 0xffffffffull) throw std::invalid_argument("terms out of range");
+    if (cms == 0 || cms > c.rows) throw std::invalid_argument("coeff_mod_size out of range");
+    if (batch > 65535) throw std::invalid_argument("batch out of range");
+    if ((t1 | b1 | t2 | b2) & 1) throw std::invalid_argument("strides must be even (16-byte loads)");
+    if ((reinterpret_cast<uintptr_t>(op1) | reinterpret_cast<uintptr_t>(op2)) & 15)
+        throw std::invalid_argument("buffers must be 16-byte aligned");
+    if (terms > 1 && (t1 < 2 * cms * c.n || t2 < 2 * cms * c.n))
+        throw std::invalid_argument("term stride below 2 * L * N: the terms of an operand overlap");
+}
+
+static void sum_check_output(Context &c, const char *name, const u64 *out, size_t out_words, const u64 *op1, const u64 *op2, size_t cms,
+                             size_t terms, size_t batch, size_t t1, size_t b1, size_t t2, size_t b2) {
+    if (reinterpret_cast<uintptr_t>(out) & 15) throw std::invalid_argument("buffers must be 16-byte aligned");
+    const size_t ct_words = 2 * cms * c.n;
+    if (batch && (touches_operand(out, out_words, op1, terms, batch, t1, b1, ct_words) ||
+                  touches_operand(out, out_words, op2, terms, batch, t2, b2, ct_words)))
+        throw std::invalid_argument(std::string(name) + " must not overlap an operand ciphertext");
+}
+
+// strict mode: every distinct operand ciphertext, in runs of at most 65534 polynomials per count (grid z); never skipped
+static void sum_strict(Context &c, const char *what, const u64 *op, size_t cms, size_t terms, size_t batch, size_t ts, size_t bs,
+                       hipStream_t s) {
+    if (!strict_mode()) return;
+    const size_t ln = cms * c.n, groups = bs ? batch : 1;
+    for (size_t g = 0; g < groups; g++) {
+        const u64 *base = op + g * bs;
+        if (terms == 1 || ts == 2 * ln) {   // dense terms: [terms][2] polynomials in a row
+            for (size_t k0 = 0; k0 < terms; k0 += 32767)
+                strict_operand(c, what, base + k0 * 2 * ln, rows_plain(0, cms), (uint32_t)(2 * std::min<size_t>(32767, terms - k0)), ln, s);
+        } else {                            // c0 of every term, then c1 of every term
+            for (size_t half = 0; half < 2; half++)
+                for (size_t k0 = 0; k0 < terms; k0 += 65535)
+                    strict_operand(c, what, base + half * ln + k0 * ts, rows_plain(0, cms), (uint32_t)std::min<size_t>(65535, terms - k0), ts, s);
+        }
+    }
+}
+
+constexpr size_t kInnerProductChunk = 8;   // groups per set of launches, as the batched BFV multiplies (pha_behz.hip: kBfvBatchChunk)
+
+// groups per set of launches of the two whole-operation entries: what the batched key switch takes in one call
+static size_t inner_product_chunk(Context &c, size_t size_Ql, size_t chunk, size_t batch) {
+    if (chunk == 0) chunk = kInnerProductChunk;
+    chunk = std::min<size_t>(std::min(chunk, batch), 1024);
+    const size_t beta = c.tool((uint32_t)size_Ql).beta;
+    while (chunk > 1 && (beta * chunk > 65535 || 2 * chunk > 65535)) chunk /= 2;
+    return chunk;
 }
 
 extern "C" {
@@ -313,6 +519,92 @@ int pha_tensor_prod_2x2_batched(pha_context_t ctx, const uint64_t *op1, const ui
     k.zr2 = ln;
     if (batch >= 2) launch_ew<EW_TENSOR_NT>(ctx->c, k, cms, 0, as_stream(stream), batch);
     else launch_ew<EW_TENSOR>(ctx->c, k, cms, 0, as_stream(stream), batch);
+    PHA_API_END
+}
+int pha_tensor_prod_2x2_sum_batched(pha_context_t ctx, const uint64_t *op1, const uint64_t *op2, uint64_t *res01, uint64_t *res2,
+                                    size_t cms, size_t terms, size_t batch, size_t op1_term_stride, size_t op1_batch_stride,
+                                    size_t op2_term_stride, size_t op2_batch_stride, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    need(op1); need(op2); need(res01); need(res2);
+    Context &c = ctx->c;
+    sum_check(c, op1, op2, cms, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride);
+    const size_t ln = cms * c.n;
+    sum_check_output(c, "res01", res01, batch * 2 * ln, op1, op2, cms, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride,
+                     op2_batch_stride);
+    sum_check_output(c, "res2", res2, batch * ln, op1, op2, cms, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride,
+                     op2_batch_stride);
+    if (batch == 0) return 0;
+    sum_strict(c, "tensor_prod_2x2_sum operand1", op1, cms, terms, batch, op1_term_stride, op1_batch_stride, as_stream(stream));
+    sum_strict(c, "tensor_prod_2x2_sum operand2", op2, cms, terms, batch, op2_term_stride, op2_batch_stride, as_stream(stream));
+    launch_tensor_sum(c, op1, op2, res01, res2, cms, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride,
+                      as_stream(stream));
+    PHA_API_END
+}
+
+// The two whole operations: the summed tensor product of a chunk of groups, then ONE batched key switch for the chunk (the key
+// switch is linear: relinearizing the sum is relinearizing every product, at 1 / terms of the cost).  The working buffers are this
+// call's own (scratch_outer: the key switch uses the stream's arena) and sized by the chunk; nothing is copied.
+int pha_inner_product_relin_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *op1, const uint64_t *op2, size_t terms,
+                                            size_t batch, size_t op1_term_stride, size_t op1_batch_stride, size_t op2_term_stride,
+                                            size_t op2_batch_stride, const uint64_t *const *rlk, uint64_t *dst, size_t chunk,
+                                            void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    need(op1); need(op2); need(rlk); need(dst);
+    Context &c = ctx->c;
+    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("size_Ql out of range");
+    if (c.size_p == 0) throw std::invalid_argument("context has no special modulus");
+    if (size_Ql < 2) throw std::invalid_argument("cannot rescale the last remaining modulus");
+    sum_check(c, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride);
+    const size_t ql_n = size_Ql * c.n, out_n = (size_Ql - 1) * c.n;
+    sum_check_output(c, "dst", dst, batch * 2 * out_n, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride,
+                     op2_batch_stride);
+    if (batch == 0) return 0;
+    hipStream_t s = as_stream(stream);
+    sum_strict(c, "tensor_prod_2x2_sum operand1", op1, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, s);
+    sum_strict(c, "tensor_prod_2x2_sum operand2", op2, size_Ql, terms, batch, op2_term_stride, op2_batch_stride, s);
+    const size_t C = inner_product_chunk(c, size_Ql, chunk, batch);
+    u64 *s01 = c.scratch_outer(stream, C * 3 * ql_n), *s2 = s01 + C * 2 * ql_n;   // the sums of a chunk: [C][2][Ql][N] | [C][Ql][N]
+    for (size_t b0 = 0; b0 < batch; b0 += C) {
+        const size_t B = std::min(C, batch - b0);
+        launch_tensor_sum(c, op1 + b0 * op1_batch_stride, op2 + b0 * op2_batch_stride, s01, s2, size_Ql, terms, B, op1_term_stride,
+                          op1_batch_stride, op2_term_stride, op2_batch_stride, s);
+        const int rc = pha_keyswitch_rescale_batched(ctx, size_Ql, s01, s2, B, rlk, dst + b0 * 2 * out_n, stream);
+        if (rc != 0) return rc;   // (its message is the last error)
+    }
+    PHA_API_END
+}
+
+int pha_inner_product_relin_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *op1, const uint64_t *op2, size_t terms,
+                                    size_t batch, size_t op1_term_stride, size_t op1_batch_stride, size_t op2_term_stride,
+                                    size_t op2_batch_stride, const uint64_t *const *rlk, int scheme, uint64_t *dst, size_t chunk,
+                                    void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    need(op1); need(op2); need(rlk); need(dst);
+    Context &c = ctx->c;
+    if (scheme == PHA_SCHEME_BFV)
+        throw std::invalid_argument("inner product of bfv ciphertexts is not supported: a bfv product is not an NTT-form tensor product");
+    if (scheme != PHA_SCHEME_CKKS && scheme != PHA_SCHEME_BGV) throw std::invalid_argument("unsupported scheme");
+    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("size_Ql out of range");
+    if (c.size_p == 0) throw std::invalid_argument("context has no special modulus");
+    if (scheme == PHA_SCHEME_BGV && !c.tool((uint32_t)size_Ql).bgv_ready)
+        throw std::invalid_argument("bgv needs a plain modulus (pha_context_set_plain_modulus)");
+    sum_check(c, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride);
+    const size_t ql_n = size_Ql * c.n;
+    sum_check_output(c, "dst", dst, batch * 2 * ql_n, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride,
+                     op2_batch_stride);
+    if (batch == 0) return 0;
+    hipStream_t s = as_stream(stream);
+    sum_strict(c, "tensor_prod_2x2_sum operand1", op1, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, s);
+    sum_strict(c, "tensor_prod_2x2_sum operand2", op2, size_Ql, terms, batch, op2_term_stride, op2_batch_stride, s);
+    const size_t C = inner_product_chunk(c, size_Ql, chunk, batch);
+    u64 *s2 = c.scratch_outer(stream, C * ql_n);   // c2 of a chunk's sums; (c0, c1) go straight into dst, which the key switch completes in place
+    for (size_t b0 = 0; b0 < batch; b0 += C) {
+        const size_t B = std::min(C, batch - b0);
+        launch_tensor_sum(c, op1 + b0 * op1_batch_stride, op2 + b0 * op2_batch_stride, dst + b0 * 2 * ql_n, s2, size_Ql, terms, B,
+                          op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride, s);
+        const int rc = pha_keyswitch_inplace_batched(ctx, size_Ql, dst + b0 * 2 * ql_n, s2, B, rlk, scheme, stream);
+        if (rc != 0) return rc;   // (its message is the last error)
+    }
     PHA_API_END
 }
 int pha_tensor_square_2x2_rns_poly(pha_context_t ctx, const uint64_t *op, uint64_t *res, size_t cms,

@@ -339,6 +339,46 @@ class PhantomContext:
         _lib.check(self._L.pha_tensor_prod_2x2_batched(self._h, _ptr(op1), _ptr(op2), _ptr(res01), _ptr(res2), cms,
                                                        batch, _stream()))
 
+    def _sum_strides(self, op1, op2, cms, terms, batch, strides):
+        """(op1 term, op1 batch, op2 term, op2 batch) strides in 64-bit words.  None: the dense layout, op1 [batch][terms][2][L][N]
+        and op2 the same or, with one dimension fewer, [terms][2][L][N] shared by all groups (batch stride 0)."""
+        if strides is not None:
+            t1, b1, t2, b2 = (int(v) for v in strides)
+            return t1, b1, t2, b2
+        ct = 2 * cms * self.n
+        dense = (batch, terms, 2, cms, self.n)
+        if op1 is None or op2 is None:          # the library refuses the null pointer
+            return ct, terms * ct, ct, terms * ct
+        if tuple(op1.shape) != dense:
+            raise ValueError("op1 must be [batch][terms][2][L][N] (or pass strides)")
+        if tuple(op2.shape) == dense:
+            return ct, terms * ct, ct, terms * ct
+        if tuple(op2.shape) == dense[1:]:
+            return ct, terms * ct, ct, 0
+        raise ValueError("op2 must be [batch][terms][2][L][N] or, shared by all groups, [terms][2][L][N] (or pass strides)")
+
+    def tensor_prod_2x2_sum_batched(self, op1, op2, res01, res2, cms, terms, batch, strides=None):
+        """Extension: for every group g < batch, (res01[g], res2[g]) = sum over k < terms of tensor_prod_2x2(op1[g][k], op2[g][k]) in
+        one launch, every word the canonical residue of the sum; res01 [batch][2][L][N], res2 [batch][L][N].  strides: see
+        _sum_strides (with explicit strides op1 / op2 may be views into larger buffers)."""
+        t1, b1, t2, b2 = self._sum_strides(op1, op2, cms, terms, batch, strides)
+        _lib.check(self._L.pha_tensor_prod_2x2_sum_batched(self._h, _ptr(op1), _ptr(op2), _ptr(res01), _ptr(res2), cms, terms, batch,
+                                                           t1, b1, t2, b2, _stream()))
+
+    def inner_product_relin_rescale_batched(self, size_Ql, op1, op2, terms, batch, rlk_ptrs, dst, strides=None, chunk=0):
+        """Extension (ckks): dst [batch][2][Ql-1][N] = rescale(relinearize(sum over k of op1[g][k] * op2[g][k])) with ONE key switch per
+        sum; bit-identical to tensor_prod_2x2_sum_batched followed by keyswitch_rescale_batched.  `chunk` groups per set of launches
+        (0: the library's default)."""
+        t1, b1, t2, b2 = self._sum_strides(op1, op2, size_Ql, terms, batch, strides)
+        _lib.check(self._L.pha_inner_product_relin_rescale_batched(self._h, size_Ql, _ptr(op1), _ptr(op2), terms, batch, t1, b1, t2, b2,
+                                                                   _ptr(rlk_ptrs), _ptr(dst), chunk, _stream()))
+
+    def inner_product_relin_batched(self, size_Ql, op1, op2, terms, batch, rlk_ptrs, scheme, dst, strides=None, chunk=0):
+        """Extension (ckks / bgv), no rescale: dst [batch][2][Ql][N] = relinearize(sum over k of op1[g][k] * op2[g][k])."""
+        t1, b1, t2, b2 = self._sum_strides(op1, op2, size_Ql, terms, batch, strides)
+        _lib.check(self._L.pha_inner_product_relin_batched(self._h, size_Ql, _ptr(op1), _ptr(op2), terms, batch, t1, b1, t2, b2,
+                                                           _ptr(rlk_ptrs), int(scheme), _ptr(dst), chunk, _stream()))
+
     def bfv_multiply_behz(self, ct1, ct2, dst):
         """bfv_multiply_behz (src/evaluate.cu:447-548): [2][Q][N] x [2][Q][N] -> [3][Q][N], coefficient form."""
         _lib.check(self._L.pha_bfv_multiply_behz(self._h, _ptr(ct1), _ptr(ct2), _ptr(dst), _stream()))
