@@ -353,6 +353,34 @@ int pha_inner_product_relin_batched(pha_context_t ctx, size_t size_Ql, const uin
                                     size_t batch, size_t op1_term_stride, size_t op1_batch_stride, size_t op2_term_stride,
                                     size_t op2_batch_stride, const uint64_t *const *rlk, int scheme, uint64_t *dst,
                                     size_t chunk, void *stream);
+/* Extension (no reference launcher; the reference composes multiply_rns_poly src/polymath.cu:156-172 with add_rns_poly :41-56 /
+ * multiply_and_add_rns_poly :225-244, then rescale_to_next / mod_switch_to_next): plaintext-weighted sums of ciphertexts, for
+ * every g < batch and both polynomials p
+ *   res[g][p] = acc[g][p] + sum over k < terms of plain[g][k] (.) ct[g][k][p]          (acc == NULL: no addend)
+ * operand (g, k) starts at base + g * batch_stride + k * term_stride (64-bit words); plain (g, k) is [L][N], ct (g, k) and
+ * acc (g) are [2][L][N], NTT form, canonical; res [batch][2][L][N].  One launch; the sums stay in registers and every output
+ * word is the canonical residue of the sum, so the result is word for word multiply followed by add in any order, and terms == 1
+ * without acc gives the words of pha_multiply_rns_poly applied to each polynomial.  A batch stride of 0 shares that operand
+ * between all groups (shared ct: rows of a matrix against one vector; shared plain: one layer applied to a batch of inputs).
+ * res may be exactly acc when acc_batch_stride == 2 * L * N (accumulate in place); no other overlap of an output with an
+ * operand is allowed.  Refused (status -1, nothing launched): a null required pointer, terms == 0, coeff_mod_size out of
+ * range, an odd stride (16-byte loads), a plain term stride below L * N or a ct term stride below 2 * L * N with terms > 1, a
+ * forbidden overlap.  batch == 0 does nothing. */
+int pha_multiply_plain_sum_batched(pha_context_t ctx, const uint64_t *plain, const uint64_t *ct, const uint64_t *acc,
+                                   uint64_t *res, size_t coeff_mod_size, size_t terms, size_t batch,
+                                   size_t plain_term_stride, size_t plain_batch_stride,
+                                   size_t ct_term_stride, size_t ct_batch_stride, size_t acc_batch_stride, void *stream);
+/* The sum above with L = size_Ql followed by ONE level drop per sum: dst [batch][2][Ql-1][N] = rescale(S[g]) for ckks
+ * (pha_divide_and_round_q_last_ntt) or mod_switch(S[g]) for bgv (pha_mod_t_and_divide_q_last_ntt); bit-identical to
+ * pha_multiply_plain_sum_batched followed by that entry with cipher_size = 2 * batch.  `chunk` groups go through one set of
+ * launches (0: the library's default, 8); the work buffer is sized by the chunk, nothing is copied, and every chunk size gives
+ * the same bits.  The operands are only read; dst must not overlap them.  Also refused: size_Ql < 2, bgv without a plain
+ * modulus, and bfv, whose plaintext product is not an NTT-form product of stored operands. */
+int pha_plain_inner_product_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *plain, const uint64_t *ct,
+                                            const uint64_t *acc, size_t terms, size_t batch,
+                                            size_t plain_term_stride, size_t plain_batch_stride,
+                                            size_t ct_term_stride, size_t ct_batch_stride, size_t acc_batch_stride,
+                                            int scheme, uint64_t *dst, size_t chunk, void *stream);
 /* phantom::hoisting_inplace (include/evaluate.cuh:233-241, src/evaluate.cu:1670-1866) on raw buffers:
  * ct [2][Ql][N] <- sum over the n_elts Galois elements of rotate(ct).  galois_elts is a HOST array;
  * glk is a HOST array of n_elts DEVICE pointer tables (PhantomRelinKey::public_keys_ptr() of each

@@ -8,6 +8,7 @@
 
 #include "../../include/phantom_amd.h"
 #include "pha_internal.h"
+#include "pha_plain_sum.h"
 
 namespace pha {
 
@@ -343,6 +344,84 @@ static void launch_tensor_sum(Context &c, const u64 *op1, const u64 *op2, u64 *r
     check_launch();
 }
 
+// ---- plaintext-weighted sum of ciphertexts (extension; the linear layer with plaintext weights: one rescale per sum) --------------
+// For every group g = blockIdx.z and both polynomials p: res[g][p] = acc[g][p] + sum over k < terms of plain[g][k] (.) ct[g][k][p]
+// (acc optional), the canonical residue of the sum in every word -- what multiply_rns_poly (polymath.cu:156-172) followed by
+// add_rns_poly (:41-56), or multiply_and_add_rns_poly (:225-244), gives in any order.  The geometry is tensor_sum_kernel's: one
+// launch, the limb is blockIdx.y (modulus in SGPRs), two adjacent coefficients per thread, the loop over terms inside the thread.
+// Per term a thread reads three 16-byte words (the plaintext's and the two polynomials') and writes nothing; the four sums (c0 and
+// c1 of the two coefficients) stay in registers.  The thread program, its two back ends (128-bit integer accumulators; exact
+// centred doubles on the limbs below 2^50) and the derivation of the terms per flush are in pha_plain_sum.h, which the host can
+// compile (tests/emu/emu_plain_sum.cpp): 64 terms per flush at 61 bits and 256 at 60 bits (integer), 5 at 50 bits, 11 at 49 and
+// 6552 at 40 (FP64).
+//
+// Cache policy, as above: operand words read once are loaded nontemporally (acc always is); an operand shared by all groups
+// (batch stride 0 with batch > 1: PL_NT / CT_NT false) keeps the default policy so that later groups may find it in the cache;
+// the result is stored with the default policy up to kSumCachedResultBytes and nontemporally (ST_NT) above it.
+struct PlainSumArgs {
+    const u64 *plain, *ct, *acc;   // acc may be null
+    u64 *res;
+    const DModulus *mod;
+    const FpInfo *fpinfo;
+    uint32_t n, limbs, terms;
+    size_t tp, zp, tc, zc, za;     // words between consecutive terms / groups of plain and ct, groups of acc
+};
+
+template <bool PL_NT, bool CT_NT>
+struct PlainSumSrc {
+    const u64 *pp, *pc;
+    size_t tp, tc, rc;
+    __device__ __forceinline__ void next(u64x2 &w, u64x2 &c0, u64x2 &c1) {
+        w = ld2<PL_NT>(pp);
+        c0 = ld2<CT_NT>(pc);
+        c1 = ld2<CT_NT>(pc + rc);
+        pp += tp;
+        pc += tc;
+    }
+};
+
+template <bool PL_NT, bool CT_NT, bool ST_NT>
+__global__ __launch_bounds__(kEwThreads, 8) void plain_sum_kernel(const PlainSumArgs k) {   // 8 waves per SIMD: at most 64 VGPRs
+    const uint32_t limb = blockIdx.y;
+    const DModulus m = k.mod[limb];
+    const size_t z = blockIdx.z;
+    const size_t idx = (size_t)limb * k.n + ((size_t)blockIdx.x * kEwThreads + threadIdx.x) * kEwPerThread;
+    const size_t rc = (size_t)k.limbs * k.n;
+    PlainSumSrc<PL_NT, CT_NT> src{k.plain + z * k.zp + idx, k.ct + z * k.zc + idx, k.tp, k.tc, rc};
+    u64x2 a0{0, 0}, a1{0, 0}, r0, r1;
+    if (k.acc) {   // (uniform)
+        const u64 *pa = k.acc + z * k.za + idx;
+        a0 = ld2<true>(pa);
+        a1 = ld2<true>(pa + rc);
+    }
+    PlainSumNoProbe probe;
+    if (k.fpinfo[limb].ok) {   // (uniform)
+        const FpInfo fi = k.fpinfo[limb];
+        plain_sum_fp(src, k.terms, FpMod{fi.q, fi.qinv, false, false}, modulus_bits(m.value), a0, a1, r0, r1, probe);
+    } else {
+        plain_sum_int(src, k.terms, m, a0, a1, r0, r1, probe);
+    }
+    u64 *r = k.res + z * 2 * rc + idx;   // (res == acc: this thread has read these very words above)
+    st2<ST_NT>(r, r0);
+    st2<ST_NT>(r + rc, r1);
+}
+
+// launch only: the callers have validated (plain_sum_check below)
+static void launch_plain_sum(Context &c, const u64 *plain, const u64 *ct, const u64 *acc, u64 *res, size_t cms, size_t terms,
+                             size_t batch, size_t tp, size_t bp, size_t tc, size_t bc, size_t ba, hipStream_t s) {
+    PlainSumArgs k{plain, ct, acc, res, c.d_mod.p, c.d_fpinfo.p, (uint32_t)c.n, (uint32_t)cms, (uint32_t)terms, tp, bp, tc, bc, ba};
+    const dim3 grid((unsigned)(c.n / (kEwThreads * kEwPerThread)), (unsigned)cms, (unsigned)batch), block(kEwThreads);
+    const bool st_nt = batch * 2 * cms * c.n * sizeof(u64) > kSumCachedResultBytes;
+    const bool pl_nt = !(bp == 0 && batch > 1), ct_nt = !(bc == 0 && batch > 1);
+#define PHA_PLAIN_SUM_LAUNCH(P, C, S) hipLaunchKernelGGL((plain_sum_kernel<P, C, S>), grid, block, 0, s, k)
+    if (pl_nt && ct_nt) { if (st_nt) PHA_PLAIN_SUM_LAUNCH(true, true, true); else PHA_PLAIN_SUM_LAUNCH(true, true, false); }
+    else if (pl_nt) { if (st_nt) PHA_PLAIN_SUM_LAUNCH(true, false, true); else PHA_PLAIN_SUM_LAUNCH(true, false, false); }
+    else if (ct_nt) { if (st_nt) PHA_PLAIN_SUM_LAUNCH(false, true, true); else PHA_PLAIN_SUM_LAUNCH(false, true, false); }
+    else { if (st_nt) PHA_PLAIN_SUM_LAUNCH(false, false, true); else PHA_PLAIN_SUM_LAUNCH(false, false, false); }
+#undef PHA_PLAIN_SUM_LAUNCH
+    check_launch();
+}
+
 // used by pha_rns.hip
 void launch_add(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, size_t mod_start, hipStream_t s) {
     EwArgs k{};
@@ -424,6 +503,51 @@ static size_t inner_product_chunk(Context &c, size_t size_Ql, size_t chunk, size
     while (chunk > 1 && (beta * chunk > 65535 || 2 * chunk > 65535)) chunk /= 2;
     return chunk;
 }
+
+// ---- plaintext-weighted sums (extension) -----------------------------------------------------------------------------------------
+// the refusals the two entries share (everything but their outputs); plaintext (g, k) is L N words at plain + g * bp + k * tp,
+// ciphertext (g, k) 2 L N words at ct + g * bc + k * tc, acc (g) 2 L N words at acc + g * ba
+static void plain_sum_check(Context &c, const u64 *plain, const u64 *ct, const u64 *acc, size_t cms, size_t terms, size_t batch,
+                            size_t tp, size_t bp, size_t tc, size_t bc, size_t ba) {
+    if (terms == 0) throw std::invalid_argument("terms must be at least 1");
+    if (terms > 0xffffffffull) throw std::invalid_argument("terms out of range");
+    if (cms == 0 || cms > c.rows) throw std::invalid_argument("coeff_mod_size out of range");
+    if (batch > 65535) throw std::invalid_argument("batch out of range");
+    if ((tp | bp | tc | bc | ba) & 1) throw std::invalid_argument("strides must be even (16-byte loads)");
+    if ((reinterpret_cast<uintptr_t>(plain) | reinterpret_cast<uintptr_t>(ct) | reinterpret_cast<uintptr_t>(acc)) & 15)
+        throw std::invalid_argument("buffers must be 16-byte aligned");
+    if (terms > 1 && tp < cms * c.n) throw std::invalid_argument("plain term stride below L * N: the terms of plain overlap");
+    if (terms > 1 && tc < 2 * cms * c.n) throw std::invalid_argument("ct term stride below 2 * L * N: the terms of ct overlap");
+}
+
+// an output may not touch a plaintext, a ciphertext or an addend; `inplace`: out IS acc (same layout), which the kernel allows
+static void plain_sum_check_output(Context &c, const char *name, const u64 *out, size_t out_words, const u64 *plain, const u64 *ct,
+                                   const u64 *acc, bool inplace, size_t cms, size_t terms, size_t batch, size_t tp, size_t bp,
+                                   size_t tc, size_t bc, size_t ba) {
+    if (reinterpret_cast<uintptr_t>(out) & 15) throw std::invalid_argument("buffers must be 16-byte aligned");
+    if (batch == 0) return;
+    const size_t ln = cms * c.n;
+    if (touches_operand(out, out_words, plain, terms, batch, tp, bp, ln))
+        throw std::invalid_argument(std::string(name) + " must not overlap a plaintext operand");
+    if (touches_operand(out, out_words, ct, terms, batch, tc, bc, 2 * ln))
+        throw std::invalid_argument(std::string(name) + " must not overlap an operand ciphertext");
+    if (acc && !inplace && touches_operand(out, out_words, acc, 1, batch, 0, ba, 2 * ln))
+        throw std::invalid_argument(std::string(name) + " must not overlap acc (other than res == acc with a stride of 2 * L * N)");
+}
+
+// strict mode: every distinct buffer of the three operands, in pieces of at most 65535 polynomials per count (grid z); never skipped
+static void plain_sum_strict(Context &c, const u64 *plain, const u64 *ct, const u64 *acc, size_t cms, size_t terms, size_t batch,
+                             size_t tp, size_t bp, size_t tc, size_t bc, size_t ba, hipStream_t s) {
+    if (!strict_mode()) return;
+    for (size_t g = 0; g < (bp ? batch : 1); g++)
+        for (size_t k0 = 0; k0 < terms; k0 += 65535)
+            strict_operand(c, "multiply_plain_sum plain", plain + g * bp + k0 * tp, rows_plain(0, cms),
+                           (uint32_t)std::min<size_t>(65535, terms - k0), tp, s);
+    sum_strict(c, "multiply_plain_sum ct", ct, cms, terms, batch, tc, bc, s);
+    if (acc) sum_strict(c, "multiply_plain_sum acc", acc, cms, 1, batch, 0, ba, s);
+}
+
+constexpr size_t kPlainSumChunk = 8;   // groups per set of launches of the rescale entry, as kInnerProductChunk
 
 extern "C" {
 
@@ -603,6 +727,66 @@ int pha_inner_product_relin_batched(pha_context_t ctx, size_t size_Ql, const uin
         launch_tensor_sum(c, op1 + b0 * op1_batch_stride, op2 + b0 * op2_batch_stride, dst + b0 * 2 * ql_n, s2, size_Ql, terms, B,
                           op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride, s);
         const int rc = pha_keyswitch_inplace_batched(ctx, size_Ql, dst + b0 * 2 * ql_n, s2, B, rlk, scheme, stream);
+        if (rc != 0) return rc;   // (its message is the last error)
+    }
+    PHA_API_END
+}
+int pha_multiply_plain_sum_batched(pha_context_t ctx, const uint64_t *plain, const uint64_t *ct, const uint64_t *acc, uint64_t *res,
+                                   size_t cms, size_t terms, size_t batch, size_t plain_term_stride, size_t plain_batch_stride,
+                                   size_t ct_term_stride, size_t ct_batch_stride, size_t acc_batch_stride, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    need(plain); need(ct); need(res);
+    Context &c = ctx->c;
+    plain_sum_check(c, plain, ct, acc, cms, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride,
+                    acc_batch_stride);
+    const size_t ln = cms * c.n;
+    const bool inplace = acc && res == acc && acc_batch_stride == 2 * ln;
+    plain_sum_check_output(c, "res", res, batch * 2 * ln, plain, ct, acc, inplace, cms, terms, batch, plain_term_stride,
+                           plain_batch_stride, ct_term_stride, ct_batch_stride, acc_batch_stride);
+    if (batch == 0) return 0;
+    hipStream_t s = as_stream(stream);
+    plain_sum_strict(c, plain, ct, acc, cms, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride,
+                     acc_batch_stride, s);
+    launch_plain_sum(c, plain, ct, acc, res, cms, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride,
+                     acc_batch_stride, s);
+    PHA_API_END
+}
+
+// The whole operation: the sums of a chunk of groups into this call's own work buffer (scratch_outer: the level drop uses the
+// stream's arena), then the EXISTING level drop over the chunk's 2 * chunk polynomials straight into dst.  Nothing is copied.
+int pha_plain_inner_product_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *plain, const uint64_t *ct,
+                                            const uint64_t *acc, size_t terms, size_t batch, size_t plain_term_stride,
+                                            size_t plain_batch_stride, size_t ct_term_stride, size_t ct_batch_stride,
+                                            size_t acc_batch_stride, int scheme, uint64_t *dst, size_t chunk, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    need(plain); need(ct); need(dst);
+    Context &c = ctx->c;
+    if (scheme == PHA_SCHEME_BFV)
+        throw std::invalid_argument("plaintext inner product of bfv ciphertexts is not supported: a bfv plaintext product is not an "
+                                    "NTT-form product of stored operands");
+    if (scheme != PHA_SCHEME_CKKS && scheme != PHA_SCHEME_BGV) throw std::invalid_argument("unsupported scheme");
+    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("size_Ql out of range");
+    if (size_Ql < 2) throw std::invalid_argument("cannot rescale the last remaining modulus");
+    if (scheme == PHA_SCHEME_BGV && !c.tool((uint32_t)size_Ql).bgv_ready)
+        throw std::invalid_argument("bgv needs a plain modulus (pha_context_set_plain_modulus)");
+    plain_sum_check(c, plain, ct, acc, size_Ql, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride,
+                    acc_batch_stride);
+    const size_t ql_n = size_Ql * c.n, out_n = (size_Ql - 1) * c.n;
+    plain_sum_check_output(c, "dst", dst, batch * 2 * out_n, plain, ct, acc, false, size_Ql, terms, batch, plain_term_stride,
+                           plain_batch_stride, ct_term_stride, ct_batch_stride, acc_batch_stride);
+    if (batch == 0) return 0;
+    hipStream_t s = as_stream(stream);
+    plain_sum_strict(c, plain, ct, acc, size_Ql, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride,
+                     acc_batch_stride, s);
+    const size_t C = std::min<size_t>(std::min(chunk ? chunk : kPlainSumChunk, batch), 32767);   // 2 C polynomials per level drop
+    u64 *work = c.scratch_outer(stream, C * 2 * ql_n);   // the sums of a chunk: [C][2][Ql][N]
+    for (size_t b0 = 0; b0 < batch; b0 += C) {
+        const size_t B = std::min(C, batch - b0);
+        launch_plain_sum(c, plain + b0 * plain_batch_stride, ct + b0 * ct_batch_stride, acc ? acc + b0 * acc_batch_stride : nullptr, work,
+                         size_Ql, terms, B, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride, acc_batch_stride, s);
+        const int rc = scheme == PHA_SCHEME_CKKS
+                           ? pha_divide_and_round_q_last_ntt(ctx, size_Ql, work, 2 * B, dst + b0 * 2 * out_n, stream)
+                           : pha_mod_t_and_divide_q_last_ntt(ctx, size_Ql, work, 2 * B, dst + b0 * 2 * out_n, stream);
         if (rc != 0) return rc;   // (its message is the last error)
     }
     PHA_API_END

@@ -379,6 +379,47 @@ class PhantomContext:
         _lib.check(self._L.pha_inner_product_relin_batched(self._h, size_Ql, _ptr(op1), _ptr(op2), terms, batch, t1, b1, t2, b2,
                                                            _ptr(rlk_ptrs), int(scheme), _ptr(dst), chunk, _stream()))
 
+    def _plain_sum_strides(self, plain, ct, cms, terms, batch, strides):
+        """(plain term, plain batch, ct term, ct batch, acc batch) strides in 64-bit words.  None: the dense layout, plain
+        [batch][terms][L][N], ct [batch][terms][2][L][N] and acc [batch][2][L][N]; plain or ct with one dimension fewer
+        ([terms]...) is shared by all groups (batch stride 0)."""
+        if strides is not None:
+            tp, bp, tc, bc, ba = (int(v) for v in strides)
+            return tp, bp, tc, bc, ba
+        ln = cms * self.n
+        if plain is None or ct is None:         # the library refuses the null pointer
+            return ln, terms * ln, 2 * ln, terms * 2 * ln, 2 * ln
+        dense_p, dense_c = (batch, terms, cms, self.n), (batch, terms, 2, cms, self.n)
+        if tuple(plain.shape) == dense_p:
+            bp = terms * ln
+        elif tuple(plain.shape) == dense_p[1:]:
+            bp = 0
+        else:
+            raise ValueError("plain must be [batch][terms][L][N] or, shared by all groups, [terms][L][N] (or pass strides)")
+        if tuple(ct.shape) == dense_c:
+            bc = terms * 2 * ln
+        elif tuple(ct.shape) == dense_c[1:]:
+            bc = 0
+        else:
+            raise ValueError("ct must be [batch][terms][2][L][N] or, shared by all groups, [terms][2][L][N] (or pass strides)")
+        return ln, bp, 2 * ln, bc, 2 * ln
+
+    def multiply_plain_sum_batched(self, plain, ct, acc, res, cms, terms, batch, strides=None):
+        """Extension: for every group g < batch, res[g] = acc[g] + sum over k < terms of plain[g][k] (.) ct[g][k] (both polynomials)
+        in one launch, every word the canonical residue of the sum; acc may be None, res [batch][2][L][N] may be acc itself.
+        strides: see _plain_sum_strides (with explicit strides the operands may be views into larger buffers)."""
+        tp, bp, tc, bc, ba = self._plain_sum_strides(plain, ct, cms, terms, batch, strides)
+        _lib.check(self._L.pha_multiply_plain_sum_batched(self._h, _ptr(plain), _ptr(ct), _ptr(acc), _ptr(res), cms, terms, batch,
+                                                          tp, bp, tc, bc, ba, _stream()))
+
+    def plain_inner_product_rescale_batched(self, size_Ql, plain, ct, acc, terms, batch, scheme, dst, strides=None, chunk=0):
+        """Extension (ckks / bgv): dst [batch][2][Ql-1][N] = the level drop (rescale / mod switch) of the sums above, ONE per sum;
+        bit-identical to multiply_plain_sum_batched followed by divide_and_round_q_last_ntt / mod_t_and_divide_q_last_ntt over
+        2 * batch polynomials.  `chunk` groups per set of launches (0: the library's default)."""
+        tp, bp, tc, bc, ba = self._plain_sum_strides(plain, ct, size_Ql, terms, batch, strides)
+        _lib.check(self._L.pha_plain_inner_product_rescale_batched(self._h, size_Ql, _ptr(plain), _ptr(ct), _ptr(acc), terms, batch,
+                                                                   tp, bp, tc, bc, ba, int(scheme), _ptr(dst), chunk, _stream()))
+
     def bfv_multiply_behz(self, ct1, ct2, dst):
         """bfv_multiply_behz (src/evaluate.cu:447-548): [2][Q][N] x [2][Q][N] -> [3][Q][N], coefficient form."""
         _lib.check(self._L.pha_bfv_multiply_behz(self._h, _ptr(ct1), _ptr(ct2), _ptr(dst), _stream()))

@@ -58,6 +58,8 @@ _SIGS = {
     "pha_tensor_prod_2x2_sum_batched": [vp, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, sz, vp],
     "pha_inner_product_relin_rescale_batched": [vp, sz, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, sz, vp],
     "pha_inner_product_relin_batched": [vp, sz, vp, vp, sz, sz, sz, sz, sz, sz, vp, C.c_int, vp, sz, vp],
+    "pha_multiply_plain_sum_batched": [vp, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, sz, sz, vp],
+    "pha_plain_inner_product_rescale_batched": [vp, sz, vp, vp, vp, sz, sz, sz, sz, sz, sz, sz, C.c_int, vp, sz, vp],
     "pha_bfv_multiply_behz": [vp, vp, vp, vp, vp],
     "pha_bfv_multiply_hps": [vp, vp, vp, vp, vp],
     "pha_bfv_multiply_hps_overq": [vp, vp, vp, vp, vp],
