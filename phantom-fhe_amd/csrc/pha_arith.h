@@ -148,6 +148,34 @@ PHA_HD void mac128(u64 a, u64 b, u64 &lo, u64 &hi) {
     hi += ph + (lo < pl);
 }
 
+// Unreduced 128-bit sums of a key-switch inner product: two adjacent coefficients (0, 1) times the two key components (b -> sums a*,
+// a -> sums b*).  A sum holds floor(2^128 / q^2) - 1 products of residues below q before reduce().
+struct KeyAcc {
+    u64 a0l = 0, a0h = 0, a1l = 0, a1h = 0, b0l = 0, b0h = 0, b1l = 0, b1h = 0;
+    // += (v0, v1) * key: kb / ka hold the key's b / a words of the two coefficients
+    PHA_HD void mac(u64 v0, u64 v1, u64x2 kb, u64x2 ka) {
+        mac128(v0, kb.x, a0l, a0h);
+        mac128(v1, kb.y, a1l, a1h);
+        mac128(v0, ka.x, b0l, b0h);
+        mac128(v1, ka.y, b1l, b1h);
+    }
+    // += (s, t) * w: reduced sums of both components times one weight per coefficient
+    PHA_HD void mac_weighted(u64x2 s, u64x2 t, u64x2 w) {
+        mac128(s.x, w.x, a0l, a0h);
+        mac128(s.y, w.y, a1l, a1h);
+        mac128(t.x, w.x, b0l, b0h);
+        mac128(t.y, w.y, b1l, b1h);
+    }
+    // start from the reduced sums of an earlier launch (split calls)
+    PHA_HD void seed(u64x2 p0, u64x2 p1) {
+        a0l = p0.x; a1l = p0.y; b0l = p1.x; b1l = p1.y;
+    }
+    PHA_HD void reduce(const DModulus &m, u64x2 &r0, u64x2 &r1) const {
+        r0 = u64x2{barrett128(a0l, a0h, m), barrett128(a1l, a1h, m)};
+        r1 = u64x2{barrett128(b0l, b0h, m), barrett128(b1l, b1h, m)};
+    }
+};
+
 // ---- gfx950-tuned lazy Shoup multiply ---------------------------------------------------------------
 // v_mul_hi_u32 issues at 1/8 of the FP32 rate on gfx950, v_mad_u64_u32 at 1/4 and delivers the full
 // 64-bit product (profiles/r01_microbench_gfx950.txt), so the quotient estimate is built from three

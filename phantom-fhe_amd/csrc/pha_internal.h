@@ -8,6 +8,7 @@
 #include <stdexcept>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -409,6 +410,46 @@ struct ModupConvArgs {
     bool moddown = false;             // r06, plain mod-down form: as the rescale form without the last-limb fold (every row is an output limb)
 };
 bool modup_conv_strided(Context &c, u64 *digits, const LimbSel &sel, const NttExtra &x, const ModupConvArgs &m, hipStream_t s);
+
+// ---- key-switch building blocks of pha_rns.hip that pha_hoist.hip calls too ----------------------------------------------
+bool ntt_domain_scheme(int scheme);   // ckks / bgv: true, bfv: false; throws on anything else
+void check_level(Context &c, size_t size_Ql, bool need_p);
+bool overlaps(const u64 *a, size_t na, const u64 *b, size_t nb);
+// DRNSTool::modup rns_bconv.cu:530-627.  All beta digits go through ONE base-conversion launch and ONE
+// forward-NTT launch pair (blockIdx.z = digit; digit z skips its own limbs, ntt_modup.cu:422).
+// `batch` ciphertexts at once: cks / t_cks are [batch][Ql][N], dst is [batch][beta][QlP][N].
+// cks_stride: elements between the c2 polynomials of consecutive ciphertexts (0 = dense, Ql * N)
+// fused_ip != null (one ciphertext): the forward transform's contiguous pass carries the key inner product
+// (modup_ntt_inner_prod): cx is produced here, the digits' own limbs are neither copied nor transformed, and the function
+// returns true; on false (shape without a fused form) nothing but the conversion has happened... the caller must not rely on
+// that: it passes fused_ip only when fusable_ip() says so.
+// own_in_place (r06; NTT-form schemes, batched key switches): the digits' own limbs are NOT copied into dst -- the caller's inner product
+// reads them from cks (InnerArgs::own); dst's own-limb rows stay unwritten and nothing reads them (the forward transform skips them)
+void modup(Context &c, Tool &t, u64 *dst, const u64 *cks, int scheme, u64 *t_cks, hipStream_t s, uint32_t batch = 1,
+           size_t cks_stride = 0, const ModupIpArgs *fused_ip = nullptr, bool own_in_place = false);
+// DRNSTool::moddown_from_NTT rns_bconv.cu:776-828 for `polys` polynomials cx + z*cx_stride at once.
+// accumulate = false: ct_z = result (the reference call).  accumulate = true: ct_z += result, i.e. the
+// add_to_ct_kernel of keyswitch_inplace (rns_bconv.cu:763-769) fused into the NTT epilogue.
+// folded (ckks): the special limbs of cx already went through the inverse transform's contiguous pass (modup_inner_prod).
+// coeff_input (bfv only): DRNSTool::moddown rns_bconv.cu:712-761 -- cx is already in coefficient form, no inverse transform.
+void moddown_from_ntt(Context &c, Tool &t, u64 *ct, size_t ct_stride, u64 *cx, size_t cx_stride, uint32_t polys, int scheme,
+                      bool accumulate, u64 *delta, hipStream_t s, bool folded = false, bool coeff_input = false);
+// coefficient-domain automorphism X -> X^galois_elt (src/galois.cu:11-39) of `polys` polynomials of `cms` limbs from row mod_start
+void launch_galois_coeff(Context &c, u64 *dst, const u64 *src, uint32_t galois_elt, size_t cms, size_t mod_start, size_t polys,
+                         hipStream_t s);
+
+// calls fn(std::integral_constant<int, B>{}) with B = beta for the digit counts kernels are instantiated for (1..4) and B = FALLBACK
+// for any other: 4 where the caller has made sure that beta <= 4, 0 (the kernels' run-time digit loop) elsewhere
+template <int FALLBACK, class F>
+inline void with_beta(uint32_t beta, F &&fn) {
+    switch (beta) {
+        case 1: fn(std::integral_constant<int, 1>{}); break;
+        case 2: fn(std::integral_constant<int, 2>{}); break;
+        case 3: fn(std::integral_constant<int, 3>{}); break;
+        case 4: fn(std::integral_constant<int, 4>{}); break;
+        default: fn(std::integral_constant<int, FALLBACK>{}); break;
+    }
+}
 
 // shared launchers (pha_rns.hip / pha_poly.hip)
 // optional epilogue of a conversion: store dst_j (+)= (cx_j - converted_j) * cst_j instead of converted_j (BFV mod-down)

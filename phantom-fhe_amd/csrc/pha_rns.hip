@@ -483,19 +483,14 @@ __global__ __launch_bounds__(256) void inner_prod_kernel(const InnerArgs k) {
     const size_t coeff = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
     const size_t c2_id = (size_t)nid * k.n + coeff;
     const size_t evk_id = (size_t)twr * k.n + coeff;
-    u64 a0l = 0, a0h = 0, a1l = 0, a1h = 0, b0l = 0, b0h = 0, b1l = 0, b1h = 0;
+    KeyAcc acc;
     for (uint32_t i = 0; i < k.beta; i++) {
         const u64 *key = k.evks[i];
         const u64x2 v = *reinterpret_cast<const u64x2 *>(k.t_mod_up + (size_t)i * k.qlp_n + c2_id);
-        const u64x2 kb = *reinterpret_cast<const u64x2 *>(key + evk_id);
-        const u64x2 ka = *reinterpret_cast<const u64x2 *>(key + evk_id + k.qp_n);
-        mac128(v.x, kb.x, a0l, a0h);
-        mac128(v.y, kb.y, a1l, a1h);
-        mac128(v.x, ka.x, b0l, b0h);
-        mac128(v.y, ka.y, b1l, b1h);
+        acc.mac(v.x, v.y, *reinterpret_cast<const u64x2 *>(key + evk_id), *reinterpret_cast<const u64x2 *>(key + evk_id + k.qp_n));
     }
-    u64x2 r0{barrett128(a0l, a0h, m), barrett128(a1l, a1h, m)};
-    u64x2 r1{barrett128(b0l, b0h, m), barrett128(b1l, b1h, m)};
+    u64x2 r0, r1;
+    acc.reduce(m, r0, r1);
     inner_fix(k, nid, m, coeff, 0, r0, r1);
     *reinterpret_cast<u64x2 *>(k.cx + c2_id) = r0;
     *reinterpret_cast<u64x2 *>(k.cx + c2_id + k.qlp_n) = r1;
@@ -560,487 +555,20 @@ __global__ __launch_bounds__(256) void inner_prod_batched_kernel(const InnerArgs
         const u64 *mu = k.t_mod_up + (size_t)b * BETA * k.qlp_n + c2_id;
         const u64 *own = k.own + (size_t)b * k.own_stride + c2_id;
         u64 *cx = k.cx + (size_t)b * 2 * k.qlp_n + c2_id;
-        u64 a0l = 0, a0h = 0, a1l = 0, a1h = 0, b0l = 0, b0h = 0, b1l = 0, b1h = 0;
+        KeyAcc acc;
 #pragma unroll
         for (int i = 0; i < BETA; i++) {
             const u64x2 v = gload2<true>(reinterpret_cast<const u64x2 *>(mine[i] ? own : mu + (size_t)i * k.qlp_n));
-            mac128(v.x, kb[i].x, a0l, a0h);
-            mac128(v.y, kb[i].y, a1l, a1h);
-            mac128(v.x, ka[i].x, b0l, b0h);
-            mac128(v.y, ka[i].y, b1l, b1h);
+            acc.mac(v.x, v.y, kb[i], ka[i]);
         }
-        u64x2 r0{barrett128(a0l, a0h, m), barrett128(a1l, a1h, m)};
-        u64x2 r1{barrett128(b0l, b0h, m), barrett128(b1l, b1h, m)};
+        u64x2 r0, r1;
+        acc.reduce(m, r0, r1);
         inner_fix(k, nid, m, coeff, b, r0, r1);
         gstore2<true>(reinterpret_cast<u64x2 *>(cx), r0);
         gstore2<true>(reinterpret_cast<u64x2 *>(cx + k.qlp_n), r1);
     }
 }
 
-// ---- hoisted rotations (src/evaluate.cu:1670-1866): for every output coefficient, sum over the Galois
-//      elements e and digits b of  modup_b[perm_e[k]] * key_{e,b}[k].  The reference materialises the
-//      permuted digits and adds per-element inner products; here the permutation is a gather inside ONE
-//      inner-product kernel and the accumulation over elements stays in the 128-bit registers
-//      (n_elts * beta * 2^120 < 2^128 needs n_elts * beta < 256; larger sets are split by the driver). ----
-struct HoistArgs {
-    u64 *cx;                          // [2][QlP][N]
-    const u64 *t_mod_up;              // [beta][QlP][N]
-    const u64 *const *const *keys;    // device array [n_elts] of device arrays [beta] of keys [2][QP][N]
-    const uint32_t *const *tables;    // device array [n_elts] of NTT-domain permutation tables
-    const DModulus *mod;
-    const uint32_t *qlp_prime;
-    uint32_t n, beta, n_elts, accumulate;  // accumulate: add to what cx already holds (split calls)
-    size_t qlp_n, qp_n;
-};
-// BETA is a template parameter and every load of an element (2 x BETA gathered digit words, 4 x BETA key words, the next element's
-// permutation entry) is issued before the first multiply (r03: the run-time digit loop serialised one memory round trip per digit)
-template <int BETA>
-__global__ __launch_bounds__(256) void hoist_inner_prod_kernel(const HoistArgs k) {
-    const uint32_t nid = blockIdx.y;
-    const uint32_t twr = k.qlp_prime[nid];
-    const DModulus m = k.mod[twr];
-    const size_t coeff = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
-    const size_t out_id = (size_t)nid * k.n + coeff;
-    const size_t evk_id = (size_t)twr * k.n + coeff;
-    u64 a0l = 0, a0h = 0, a1l = 0, a1h = 0, b0l = 0, b0h = 0, b1l = 0, b1h = 0;
-    if (k.accumulate) {
-        const u64x2 p0 = *reinterpret_cast<const u64x2 *>(k.cx + out_id);
-        const u64x2 p1 = *reinterpret_cast<const u64x2 *>(k.cx + out_id + k.qlp_n);
-        a0l = p0.x; a1l = p0.y; b0l = p1.x; b1l = p1.y;
-    }
-    uint2 idx = *reinterpret_cast<const uint2 *>(k.tables[0] + coeff);
-    for (uint32_t e = 0; e < k.n_elts; e++) {
-        const uint2 idx_next = *reinterpret_cast<const uint2 *>(k.tables[e + 1 < k.n_elts ? e + 1 : e] + coeff);
-        const u64 *const *keys = k.keys[e];
-        u64 v0[BETA], v1[BETA];
-        u64x2 kb[BETA], ka[BETA];
-#pragma unroll
-        for (int i = 0; i < BETA; i++) {
-            const u64 *digit = k.t_mod_up + (size_t)i * k.qlp_n + (size_t)nid * k.n;
-            const u64 *key = keys[i];
-            v0[i] = digit[idx.x];
-            v1[i] = digit[idx.y];
-            kb[i] = *reinterpret_cast<const u64x2 *>(key + evk_id);
-            ka[i] = *reinterpret_cast<const u64x2 *>(key + evk_id + k.qp_n);
-        }
-#pragma unroll
-        for (int i = 0; i < BETA; i++) {
-            mac128(v0[i], kb[i].x, a0l, a0h);
-            mac128(v1[i], kb[i].y, a1l, a1h);
-            mac128(v0[i], ka[i].x, b0l, b0h);
-            mac128(v1[i], ka[i].y, b1l, b1h);
-        }
-        idx = idx_next;
-    }
-    *reinterpret_cast<u64x2 *>(k.cx + out_id) = u64x2{barrett128(a0l, a0h, m), barrett128(a1l, a1h, m)};
-    *reinterpret_cast<u64x2 *>(k.cx + out_id + k.qlp_n) = u64x2{barrett128(b0l, b0h, m), barrett128(b1l, b1h, m)};
-}
-// any number of digits (run-time loop)
-__global__ __launch_bounds__(256) void hoist_inner_prod_generic_kernel(const HoistArgs k) {
-    const uint32_t nid = blockIdx.y;
-    const uint32_t twr = k.qlp_prime[nid];
-    const DModulus m = k.mod[twr];
-    const size_t coeff = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
-    const size_t out_id = (size_t)nid * k.n + coeff;
-    const size_t evk_id = (size_t)twr * k.n + coeff;
-    u64 a0l = 0, a0h = 0, a1l = 0, a1h = 0, b0l = 0, b0h = 0, b1l = 0, b1h = 0;
-    if (k.accumulate) {
-        const u64x2 p0 = *reinterpret_cast<const u64x2 *>(k.cx + out_id);
-        const u64x2 p1 = *reinterpret_cast<const u64x2 *>(k.cx + out_id + k.qlp_n);
-        a0l = p0.x; a1l = p0.y; b0l = p1.x; b1l = p1.y;
-    }
-    for (uint32_t e = 0; e < k.n_elts; e++) {
-        const uint2 idx = *reinterpret_cast<const uint2 *>(k.tables[e] + coeff);
-        const u64 *const *keys = k.keys[e];
-        for (uint32_t i = 0; i < k.beta; i++) {
-            const u64 *digit = k.t_mod_up + (size_t)i * k.qlp_n + (size_t)nid * k.n;
-            const u64 v0 = digit[idx.x], v1 = digit[idx.y];
-            const u64 *key = keys[i];
-            const u64x2 kb = *reinterpret_cast<const u64x2 *>(key + evk_id);
-            const u64x2 ka = *reinterpret_cast<const u64x2 *>(key + evk_id + k.qp_n);
-            mac128(v0, kb.x, a0l, a0h);
-            mac128(v1, kb.y, a1l, a1h);
-            mac128(v0, ka.x, b0l, b0h);
-            mac128(v1, ka.y, b1l, b1h);
-        }
-    }
-    *reinterpret_cast<u64x2 *>(k.cx + out_id) = u64x2{barrett128(a0l, a0h, m), barrett128(a1l, a1h, m)};
-    *reinterpret_cast<u64x2 *>(k.cx + out_id + k.qlp_n) = u64x2{barrett128(b0l, b0h, m), barrett128(b1l, b1h, m)};
-}
-
-// dst[limb][k] = sum_e src[limb][perm_e[k]] mod q  (c0 part of hoisting for ckks / bgv)
-__global__ __launch_bounds__(256) void hoist_c0_kernel(u64 *dst, const u64 *src, const uint32_t *const *tables,
-                                                       uint32_t n_elts, const DModulus *mod, uint32_t n) {
-    const uint32_t limb = blockIdx.y;
-    const u64 q = mod[limb].value;
-    const uint32_t coeff = blockIdx.x * 256 + threadIdx.x;
-    u64 acc = 0;
-    for (uint32_t e = 0; e < n_elts; e++) acc = add_mod(acc, src[(size_t)limb * n + tables[e][coeff]], q);
-    dst[(size_t)limb * n + coeff] = acc;
-}
-
-// ---- weighted hoisted rotations (BASELINE config 5, build-defined: no reference counterpart): as above with a
-//      plaintext weight per Galois element, multiplied in before the shared mod-down:
-//      cx[k] = sum_e w_e[k] * (sum_b modup_b[perm_e[k]] * key_{e,b}[k] mod q).  The per-element inner product
-//      is reduced once (Barrett) so that the weighted sum fits the 128-bit accumulator again. ----
-struct HoistWArgs {
-    HoistArgs h;
-    const u64 *const *weights;        // device array [n_elts] of weights [QlP][N] (NTT form)
-};
-template <int BETA>   // 0: run-time digit loop
-__global__ __launch_bounds__(256) void hoist_weighted_inner_prod_kernel(const HoistWArgs kw) {
-    const HoistArgs &k = kw.h;
-    const uint32_t nid = blockIdx.y;
-    const uint32_t twr = k.qlp_prime[nid];
-    const DModulus m = k.mod[twr];
-    const size_t coeff = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
-    const size_t out_id = (size_t)nid * k.n + coeff;
-    const size_t evk_id = (size_t)twr * k.n + coeff;
-    u64 a0l = 0, a0h = 0, a1l = 0, a1h = 0, b0l = 0, b0h = 0, b1l = 0, b1h = 0;
-    if (k.accumulate) {
-        const u64x2 p0 = *reinterpret_cast<const u64x2 *>(k.cx + out_id);
-        const u64x2 p1 = *reinterpret_cast<const u64x2 *>(k.cx + out_id + k.qlp_n);
-        a0l = p0.x; a1l = p0.y; b0l = p1.x; b1l = p1.y;
-    }
-    uint2 idx = *reinterpret_cast<const uint2 *>(k.tables[0] + coeff);
-    for (uint32_t e = 0; e < k.n_elts; e++) {
-        const uint2 idx_next = *reinterpret_cast<const uint2 *>(k.tables[e + 1 < k.n_elts ? e + 1 : e] + coeff);
-        const u64 *const *keys = k.keys[e];
-        const u64x2 w = *reinterpret_cast<const u64x2 *>(kw.weights[e] + out_id);
-        u64 s0l = 0, s0h = 0, s1l = 0, s1h = 0, t0l = 0, t0h = 0, t1l = 0, t1h = 0;
-        if constexpr (BETA > 0) {   // every load of the element before the first multiply
-            u64 v0[BETA], v1[BETA];
-            u64x2 kb[BETA], ka[BETA];
-#pragma unroll
-            for (int i = 0; i < BETA; i++) {
-                const u64 *digit = k.t_mod_up + (size_t)i * k.qlp_n + (size_t)nid * k.n;
-                const u64 *key = keys[i];
-                v0[i] = digit[idx.x];
-                v1[i] = digit[idx.y];
-                kb[i] = *reinterpret_cast<const u64x2 *>(key + evk_id);
-                ka[i] = *reinterpret_cast<const u64x2 *>(key + evk_id + k.qp_n);
-            }
-#pragma unroll
-            for (int i = 0; i < BETA; i++) {
-                mac128(v0[i], kb[i].x, s0l, s0h);
-                mac128(v1[i], kb[i].y, s1l, s1h);
-                mac128(v0[i], ka[i].x, t0l, t0h);
-                mac128(v1[i], ka[i].y, t1l, t1h);
-            }
-        } else {
-            for (uint32_t i = 0; i < k.beta; i++) {
-                const u64 *digit = k.t_mod_up + (size_t)i * k.qlp_n + (size_t)nid * k.n;
-                const u64 v0 = digit[idx.x], v1 = digit[idx.y];
-                const u64 *key = keys[i];
-                const u64x2 kb = *reinterpret_cast<const u64x2 *>(key + evk_id);
-                const u64x2 ka = *reinterpret_cast<const u64x2 *>(key + evk_id + k.qp_n);
-                mac128(v0, kb.x, s0l, s0h);
-                mac128(v1, kb.y, s1l, s1h);
-                mac128(v0, ka.x, t0l, t0h);
-                mac128(v1, ka.y, t1l, t1h);
-            }
-        }
-        mac128(barrett128(s0l, s0h, m), w.x, a0l, a0h);
-        mac128(barrett128(s1l, s1h, m), w.y, a1l, a1h);
-        mac128(barrett128(t0l, t0h, m), w.x, b0l, b0h);
-        mac128(barrett128(t1l, t1h, m), w.y, b1l, b1h);
-        idx = idx_next;
-    }
-    *reinterpret_cast<u64x2 *>(k.cx + out_id) = u64x2{barrett128(a0l, a0h, m), barrett128(a1l, a1h, m)};
-    *reinterpret_cast<u64x2 *>(k.cx + out_id + k.qlp_n) = u64x2{barrett128(b0l, b0h, m), barrett128(b1l, b1h, m)};
-}
-
-// dst[p][limb][k] = sum_e w_e[limb][k] * src[p][limb][perm_e[k]] mod q.  blockIdx.z = polynomial: c0 takes every
-// element, c1 only the main-diagonal ones (Galois element 1, identity permutation), whose list starts at first_c1.
-__global__ __launch_bounds__(256) void hoist_weighted_c_kernel(u64 *dst, const u64 *src, const uint32_t *const *tables,
-                                                               const u64 *const *weights, uint32_t n_elts,
-                                                               uint32_t first_c1, const DModulus *mod, uint32_t n,
-                                                               size_t poly_stride) {
-    const uint32_t limb = blockIdx.y, p = blockIdx.z;
-    const DModulus m = mod[limb];
-    const uint32_t coeff = blockIdx.x * 256 + threadIdx.x;
-    const size_t id = (size_t)limb * n + coeff;
-    u64 lo = 0, hi = 0;
-    uint32_t terms = 0;
-    for (uint32_t e = p ? first_c1 : 0; e < n_elts; e++) {
-        mac128(src[p * poly_stride + (size_t)limb * n + tables[e][coeff]], weights[e][id], lo, hi);
-        if (++terms == 48) {           // products of two 61-bit residues: 48 * 2^122 stays below 2^128
-            lo = barrett128(lo, hi, m);
-            hi = 0;
-            terms = 1;
-        }
-    }
-    dst[p * poly_stride + id] = barrett128(lo, hi, m);
-}
-
-// CPT consecutive words as one access
-template <int CPT>
-__device__ __forceinline__ void load_words(const u64 *p, u64 (&v)[CPT]) {
-    if constexpr (CPT == 2) {
-        const u64x2 t = *reinterpret_cast<const u64x2 *>(p);
-        v[0] = t.x;
-        v[1] = t.y;
-    } else {
-        v[0] = *p;
-    }
-}
-template <int CPT>
-__device__ __forceinline__ void store_words(u64 *p, const u64 (&v)[CPT]) {
-    if constexpr (CPT == 2) *reinterpret_cast<u64x2 *>(p) = u64x2{v[0], v[1]};
-    else *p = v[0];
-}
-
-// ---- baby-step / giant-step form of the weighted hoisted rotations (BASELINE config 5, build-defined) -----------------------
-//      out = sum_i rot_{G_i}( sum_j w_ij (.) rot_{B_j}(ct) ):  d = ng * nb diagonals from nb - 1 baby keys and ng - 1 giant keys
-//      instead of d - 1 keys (24 GB of Galois keys per 128-diagonal block at C3 -> 4 GB).  "Double hoisting": the baby rotations
-//      share ONE mod-up of c1 and their inner products stay in the extended base [Q_l || P]; every giant step i weights them with
-//      its own plaintexts w_ij (given over [Q_l || P], as in pha_hoisting_weighted) and pays one mod-down; the giant rotations
-//      share ONE final mod-down of the sum of their inner products.
-// One thread = one coefficient of one limb; the accumulators of NG giant steps live in registers, so the baby keys, the gathered
-// digits and the per-baby Barrett reductions are paid once for all of them.
-struct BsgsArgs {
-    u64 *acc;                         // [ng][2][QlP][N]
-    const u64 *t_mod_up;              // [beta][QlP][N]
-    const u64 *const *const *keys;    // device [nb]: key table of baby j ([beta] keys), null for the identity
-    const uint32_t *const *tables;    // device [nb]: NTT-domain permutation of baby j
-    const u64 *const *weights;        // device [ng][nb]: w_ij over [QlP][N], null = no such term
-    const DModulus *mod;
-    const uint32_t *qlp_prime;
-    uint32_t n, beta, nb, g0;         // g0: first giant step of this launch
-    size_t qlp_n, qp_n;
-    const u64 *cc;                    // the input ciphertext (c0, c1), [2][Ql][N]
-    const u64x2 *p_mod_q;             // [Ql] P mod q_j with its Shoup quotient
-    uint32_t ql;
-    size_t ql_n;
-    const FpInfo *fpinfo;             // [prime]: limbs below 2^50 accumulate in doubles (r04)
-};
-// The c0 / c1 terms ride in the same accumulators: on a data limb j the value added is P * x mod q_j, which the mod-down that
-// follows (it divides by P exactly: (cx_j - conv(cx_P)_j) P^-1) turns back into x, and on the P limbs P * x = 0 -- so
-// moddown(acc + P * y) = moddown(acc) + y, word for word what a separate weighted sum over Q_l would add afterwards.
-// Every load of a baby step (3 gathered digits, the c0 word, 2 x BETA key words, NG weights, the next step's permutation
-// entry) is issued before the first multiply: the first version branched per giant step on a null weight and looped over the
-// digits at run time, which serialised ~12 memory round trips per baby step (2.9 TB/s); missing weights now point at a zero
-// plane supplied by the driver.
-// r04: limbs whose prime is below 2^50 run the same sums in FP64 (pha_arith.h: residues as doubles with integer values, every
-// product an exact fp_mulmod_light).  A 128-bit multiply-accumulate costs ~12 vector instructions on 32-bit halves and the two
-// Barrett reductions per baby step ~55; here a product-and-add is 7 FP64 operations and there is nothing to reduce at the end of a
-// step but two re-centrings: ~210 instead of ~340 instructions per baby step at NG = 8, and 2 NG instead of 4 NG accumulator
-// register pairs.  Magnitudes: gathered digits, key words and weights are canonical (< q), so a digit product is below 0.875 q and
-// BETA + 1 of them below 4.4 q; s and t are re-centred (<= q/2), a weighted term is then below 0.69 q, and the accumulators are
-// re-centred every 8 baby steps (0.5 + 8 x 0.69 = 6.0 q < 8 q = 2^53): every value is an exact integer, the stored residues are
-// the ones the integer form stores.
-template <int NG, int BETA>
-__device__ __forceinline__ void hoist_bsgs_body_fp(const BsgsArgs &k, uint32_t nid, uint32_t twr, const FpInfo fi) {
-    const FpMod fm{fi.q, fi.qinv, false, false};
-    const size_t coeff = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t out_id = (size_t)nid * k.n + coeff;
-    const size_t evk_id = (size_t)twr * k.n + coeff;
-    const bool data_limb = nid < k.ql;          // uniform
-    const double pqd = data_limb ? fp_from_canon(k.p_mod_q[nid].x) : 0.0;
-    const u64 *cc0 = k.cc + (size_t)(data_limb ? nid : 0) * k.n;
-    double al[NG], bl[NG];
-#pragma unroll
-    for (int g = 0; g < NG; g++) al[g] = bl[g] = 0.0;
-    uint32_t idx = k.tables[0][coeff];
-    for (uint32_t j = 0; j < k.nb; j++) {
-        const u64 *const *keys = k.keys[j];
-        const uint32_t idx_next = k.tables[j + 1 < k.nb ? j + 1 : j][coeff];
-        u64 wv[NG];
-#pragma unroll
-        for (int g = 0; g < NG; g++) wv[g] = k.weights[(size_t)(k.g0 + g) * k.nb + j][out_id];
-        const u64 x0 = cc0[idx];
-        double s, t;
-        if (keys) {   // uniform
-            u64 v[BETA], kb[BETA], ka[BETA];
-#pragma unroll
-            for (int i = 0; i < BETA; i++) {
-                const u64 *key = keys[i];
-                v[i] = k.t_mod_up[(size_t)i * k.qlp_n + (size_t)nid * k.n + idx];
-                kb[i] = key[evk_id];
-                ka[i] = key[evk_id + k.qp_n];
-            }
-            s = data_limb ? fp_mulmod_light(fp_from_canon(x0), pqd, fm) : 0.0;   // + P * rot_j(c0)
-            t = 0.0;
-#pragma unroll
-            for (int i = 0; i < BETA; i++) {
-                const double vd = fp_from_canon(v[i]);
-                s += fp_mulmod_light(vd, fp_from_canon(kb[i]), fm);
-                t += fp_mulmod_light(vd, fp_from_canon(ka[i]), fm);
-            }
-        } else {      // identity baby step: (P c0, P c1) on the data limbs, nothing on the P limbs
-            s = data_limb ? fp_mulmod_light(fp_from_canon(x0), pqd, fm) : 0.0;
-            t = data_limb ? fp_mulmod_light(fp_from_canon(k.cc[k.ql_n + (size_t)nid * k.n + idx]), pqd, fm) : 0.0;
-        }
-        s = fp_reduce(s, fm);
-        t = fp_reduce(t, fm);
-#pragma unroll
-        for (int g = 0; g < NG; g++) {
-            const double wd = fp_from_canon(wv[g]);
-            al[g] += fp_mulmod_light(s, wd, fm);
-            bl[g] += fp_mulmod_light(t, wd, fm);
-        }
-        if ((j & 7u) == 7u) {   // (uniform)
-#pragma unroll
-            for (int g = 0; g < NG; g++) {
-                al[g] = fp_reduce(al[g], fm);
-                bl[g] = fp_reduce(bl[g], fm);
-            }
-        }
-        idx = idx_next;
-    }
-#pragma unroll
-    for (int g = 0; g < NG; g++) {
-        u64 *acc = k.acc + (size_t)(k.g0 + g) * 2 * k.qlp_n + out_id;
-        acc[0] = fp_to_canon(al[g], fm);
-        acc[k.qlp_n] = fp_to_canon(bl[g], fm);
-    }
-}
-
-// integer limbs: accumulators [goff, goff + NG) of the launch
-template <int NG, int BETA>
-__device__ __forceinline__ void hoist_bsgs_body_int(const BsgsArgs &k, uint32_t nid, uint32_t twr, uint32_t goff) {
-    const DModulus m = k.mod[twr];
-    const size_t coeff = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t out_id = (size_t)nid * k.n + coeff;
-    const size_t evk_id = (size_t)twr * k.n + coeff;
-    const bool data_limb = nid < k.ql;          // uniform
-    const u64x2 pq = data_limb ? k.p_mod_q[nid] : u64x2{0, 0};
-    const u64 *cc0 = k.cc + (size_t)(data_limb ? nid : 0) * k.n;   // (P limbs: any valid row, the value is multiplied by 0)
-    u64 al[NG], ah[NG], bl[NG], bh[NG];
-#pragma unroll
-    for (int g = 0; g < NG; g++) al[g] = ah[g] = bl[g] = bh[g] = 0;
-    uint32_t idx = k.tables[0][coeff];
-    for (uint32_t j = 0; j < k.nb; j++) {
-        const u64 *const *keys = k.keys[j];
-        const uint32_t idx_next = k.tables[j + 1 < k.nb ? j + 1 : j][coeff];
-        // loads first
-        u64 wv[NG];
-#pragma unroll
-        for (int g = 0; g < NG; g++) wv[g] = k.weights[(size_t)(k.g0 + goff + g) * k.nb + j][out_id];
-        const u64 x0 = cc0[idx];
-        u64 s, t;
-        if (keys) {   // uniform
-            u64 v[BETA], kb[BETA], ka[BETA];
-#pragma unroll
-            for (int i = 0; i < BETA; i++) {
-                const u64 *key = keys[i];
-                v[i] = k.t_mod_up[(size_t)i * k.qlp_n + (size_t)nid * k.n + idx];
-                kb[i] = key[evk_id];
-                ka[i] = key[evk_id + k.qp_n];
-            }
-            u64 sl = 0, sh = 0, tl = 0, th = 0;
-#pragma unroll
-            for (int i = 0; i < BETA; i++) {
-                mac128(v[i], kb[i], sl, sh);
-                mac128(v[i], ka[i], tl, th);
-            }
-            s = barrett128(sl, sh, m);
-            t = barrett128(tl, th, m);
-            if (data_limb) s = add_mod(s, shoup(x0, pq, m.value), m.value);          // + P * rot_j(c0)
-        } else {      // identity baby step: (P c0, P c1) on the data limbs, nothing on the P limbs
-            s = data_limb ? shoup(x0, pq, m.value) : 0;
-            t = data_limb ? shoup(k.cc[k.ql_n + (size_t)nid * k.n + idx], pq, m.value) : 0;
-        }
-#pragma unroll
-        for (int g = 0; g < NG; g++) {
-            mac128(s, wv[g], al[g], ah[g]);
-            mac128(t, wv[g], bl[g], bh[g]);
-        }
-        idx = idx_next;
-    }
-#pragma unroll
-    for (int g = 0; g < NG; g++) {
-        u64 *acc = k.acc + (size_t)(k.g0 + goff + g) * 2 * k.qlp_n + out_id;
-        acc[0] = barrett128(al[g], ah[g], m);
-        acc[k.qlp_n] = barrett128(bl[g], bh[g], m);
-    }
-}
-
-// NG accumulators per launch.  NG = 16 (r04): the FP64 limbs keep 16 (block, giant step) accumulators in 32 register pairs, so the
-// baby keys are streamed once per 16 / ng row blocks; an integer limb would need 64 pairs for that and walks its baby steps twice
-// with 8 accumulators each instead (16 of 60 limbs at the C3 set).
-template <int NG, int BETA>
-__global__ __launch_bounds__(256) void hoist_bsgs_inner_prod_kernel(const BsgsArgs k) {
-    const uint32_t nid = blockIdx.y;
-    const uint32_t twr = k.qlp_prime[nid];
-    if (k.fpinfo) {   // (uniform) FP64 limbs
-        const FpInfo fi = k.fpinfo[twr];
-        if (fi.ok) {
-            hoist_bsgs_body_fp<NG, BETA>(k, nid, twr, fi);
-            return;
-        }
-    }
-    if constexpr (NG > 8) {
-        hoist_bsgs_body_int<8, BETA>(k, nid, twr, 0);
-        hoist_bsgs_body_int<NG - 8, BETA>(k, nid, twr, 8);
-    } else {
-        hoist_bsgs_body_int<NG, BETA>(k, nid, twr, 0);
-    }
-}
-
-// giant steps, part 1: ct0 = sum_i B_i0[perm_Gi], ct1 = sum over the identity giant steps of B_i1, and the dense operands
-// g1[z] = B_i1[perm_Gi] of the keyed giant steps (z = their rank among the keyed ones)
-// blockIdx.z = row block: its ng giant steps start at B + z * ng * 2 polynomials, its nk operands at g1 + z * nk, its output at ct + 2 z
-__global__ __launch_bounds__(256) void bsgs_combine_kernel(u64 *ct, u64 *g1, const u64 *B, const uint32_t *const *tables,
-                                                           const uint32_t *keyed_rank, uint32_t ng, uint32_t nk, const DModulus *mod,
-                                                           uint32_t n, size_t poly_stride) {
-    const uint32_t limb = blockIdx.y;
-    ct += (size_t)blockIdx.z * 2 * poly_stride;
-    g1 += (size_t)blockIdx.z * nk * poly_stride;
-    B += (size_t)blockIdx.z * ng * 2 * poly_stride;
-    const u64 q = mod[limb].value;
-    const uint32_t coeff = blockIdx.x * 256 + threadIdx.x;
-    const size_t id = (size_t)limb * n + coeff;
-    u64 r0 = 0, r1 = 0;
-    for (uint32_t i = 0; i < ng; i++) {
-        const uint32_t from = tables[i][coeff];
-        const u64 *b = B + (size_t)(2 * i) * poly_stride + (size_t)limb * n;
-        r0 = add_mod(r0, b[from], q);
-        const uint32_t z = keyed_rank[i];
-        if (z == 0xffffffffu) r1 = add_mod(r1, b[poly_stride + coeff], q);     // identity giant step
-        else g1[(size_t)z * poly_stride + id] = b[poly_stride + from];
-    }
-    ct[id] = r0;
-    ct[poly_stride + id] = r1;
-}
-
-// giant steps, part 2: cx = sum_z <modup(g1[z]), key_z> in one pass (the inner products of nk key switches that share a mod-down)
-struct MultiInnerArgs {
-    u64 *cx;                        // [2][QlP][N]
-    const u64 *t_mod_up;            // [nk][beta][QlP][N]
-    const u64 *const *const *keys;  // device [nk] -> [beta]
-    const DModulus *mod;
-    const uint32_t *qlp_prime;
-    uint32_t n, beta, nk;
-    size_t qlp_n, qp_n;
-};
-__global__ __launch_bounds__(256) void inner_prod_multi_kernel(const MultiInnerArgs kk) {   // blockIdx.z = row block
-    MultiInnerArgs k = kk;
-    k.cx += (size_t)blockIdx.z * 2 * k.qlp_n;
-    k.t_mod_up += (size_t)blockIdx.z * k.nk * k.beta * k.qlp_n;
-    const uint32_t nid = blockIdx.y;
-    const uint32_t twr = k.qlp_prime[nid];
-    const DModulus m = k.mod[twr];
-    const size_t coeff = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
-    const size_t c2_id = (size_t)nid * k.n + coeff;
-    const size_t evk_id = (size_t)twr * k.n + coeff;
-    u64 a0l = 0, a0h = 0, a1l = 0, a1h = 0, b0l = 0, b0h = 0, b1l = 0, b1h = 0;
-    for (uint32_t z = 0; z < k.nk; z++) {
-        const u64 *const *keys = k.keys[z];
-        for (uint32_t i = 0; i < k.beta; i++) {
-            const u64 *key = keys[i];
-            const u64x2 v = *reinterpret_cast<const u64x2 *>(k.t_mod_up + ((size_t)z * k.beta + i) * k.qlp_n + c2_id);
-            const u64x2 kb = *reinterpret_cast<const u64x2 *>(key + evk_id);
-            const u64x2 ka = *reinterpret_cast<const u64x2 *>(key + evk_id + k.qp_n);
-            mac128(v.x, kb.x, a0l, a0h);
-            mac128(v.y, kb.y, a1l, a1h);
-            mac128(v.x, ka.x, b0l, b0h);
-            mac128(v.y, ka.y, b1l, b1h);
-        }
-    }
-    *reinterpret_cast<u64x2 *>(k.cx + c2_id) = u64x2{barrett128(a0l, a0h, m), barrett128(a1l, a1h, m)};
-    *reinterpret_cast<u64x2 *>(k.cx + c2_id + k.qlp_n) = u64x2{barrett128(b0l, b0h, m), barrett128(b1l, b1h, m)};
-}
 
 // ---- (cx - delta) * c element-wise: moddown_kernel rns_bconv.cu:680-689 and
 //      divide_and_round_q_last_kernel rns.cu:1082-1108 (REDUCE_LAST) ---------------------------------
@@ -1198,6 +726,13 @@ __global__ __launch_bounds__(256) void galois_coeff_kernel(u64 *dst, const u64 *
     dst[(size_t)limb * n + coeff] = v;
 }
 
+void launch_galois_coeff(Context &c, u64 *dst, const u64 *src, uint32_t galois_elt, size_t cms, size_t mod_start, size_t polys,
+                         hipStream_t s) {
+    hipLaunchKernelGGL(galois_coeff_kernel, dim3((unsigned)(c.n / 256), (unsigned)cms, (unsigned)polys), dim3(256), 0, s, dst, src,
+                       c.d_mod.p, (uint32_t)mod_start, inv_mod_2n(galois_elt, c.n), (uint32_t)c.n);
+    check_launch();
+}
+
 // Galois automorphism of a batch of size-2 ciphertexts laid out for the key switch that follows it (rotate_internal /
 // apply_galois_inplace, src/evaluate.cu:1567-1624): polynomial 0 goes to dst_ct[b][0], dst_ct[b][1] is zeroed and polynomial 1
 // goes to the dense key-switch operand dst_c2[b] -- one kernel instead of permutation + memset + two strided copies.
@@ -1238,30 +773,22 @@ __global__ __launch_bounds__(256) void galois_split_kernel(u64 *dst_ct, u64 *dst
 // ------------------------------------------------------------------------------------------------
 // drivers
 // ------------------------------------------------------------------------------------------------
-static bool ntt_domain_scheme(int scheme) {
+bool ntt_domain_scheme(int scheme) {
     if (scheme == PHA_SCHEME_CKKS || scheme == PHA_SCHEME_BGV) return true;
     if (scheme == PHA_SCHEME_BFV) return false;
     throw std::invalid_argument("unsupported scheme");
 }
 
-// DRNSTool::modup rns_bconv.cu:530-627.  All beta digits go through ONE base-conversion launch and ONE
-// forward-NTT launch pair (blockIdx.z = digit; digit z skips its own limbs, ntt_modup.cu:422).
-// `batch` ciphertexts at once: cks / t_cks are [batch][Ql][N], dst is [batch][beta][QlP][N].
-// cks_stride: elements between the c2 polynomials of consecutive ciphertexts (0 = dense, Ql * N)
-// fused_ip != null (one ciphertext): the forward transform's contiguous pass carries the key inner product
-// (modup_ntt_inner_prod): cx is produced here, the digits' own limbs are neither copied nor transformed, and the function
-// returns true; on false (shape without a fused form) nothing but the conversion has happened... the caller must not rely on
-// that: it passes fused_ip only when fusable_ip() says so.
+// fused_ip may be passed to modup (pha_internal.h) only for the shapes that have a fused form
 static bool fusable_ip(Context &c, Tool &t) { return t.alpha > 1 && c.log_n >= 14 && c.log_n <= 17 && t.beta <= 4; }
 // r06: batched key switches of the NTT-form schemes leave the digits' own limbs where they are (modup's own_in_place + InnerArgs::own):
 // the batched inner product kernel is the one that knows how to read them from c2
 static bool own_in_place_ok(const Tool &t, int scheme, uint32_t batch) {
     return (scheme == PHA_SCHEME_CKKS || scheme == PHA_SCHEME_BGV) && batch > 1 && t.alpha > 1 && t.beta <= 4;
 }
-// own_in_place (r06; NTT-form schemes, batched key switches): the digits' own limbs are NOT copied into dst -- the caller's inner product
-// reads them from cks (InnerArgs::own); dst's own-limb rows stay unwritten and nothing reads them (the forward transform skips them)
-static void modup(Context &c, Tool &t, u64 *dst, const u64 *cks, int scheme, u64 *t_cks, hipStream_t s,
-                  uint32_t batch = 1, size_t cks_stride = 0, const ModupIpArgs *fused_ip = nullptr, bool own_in_place = false) {
+// (described with its declaration in pha_internal.h)
+void modup(Context &c, Tool &t, u64 *dst, const u64 *cks, int scheme, u64 *t_cks, hipStream_t s, uint32_t batch, size_t cks_stride,
+           const ModupIpArgs *fused_ip, bool own_in_place) {
     const size_t n = c.n;
     const uint32_t ql = t.size_ql, qlp = t.size_qlp, alpha = t.alpha;
     const bool ntt_dom = ntt_domain_scheme(scheme);
@@ -1344,6 +871,19 @@ static u64 h_invmod_p(Context &c, uint32_t limb) {
     return h_invmod(p, q);
 }
 
+// The fused-rescale fix-up fields of InnerArgs / ModupIpArgs (pha_keyswitch_rescale): the last data limb of cx receives
+// ct_last + cx_last * P^-1; fix_ct = null: off
+template <class Args>
+static void set_last_limb_fix(Context &c, Tool &t, const u64 *fix_ct, Args &k) {
+    k.fix_limb = 0xffffffffu;
+    if (!fix_ct) return;
+    const u64 pinv_last = h_invmod_p(c, t.size_ql - 1);
+    k.fix_limb = t.size_ql - 1;
+    k.fix_cst = u64x2{pinv_last, h_shoup(pinv_last, c.primes[t.size_ql - 1])};
+    k.fix_ct = fix_ct;
+    k.fix_ct_stride = (size_t)t.size_ql * c.n;
+}
+
 // mod-up + inner product of ONE ciphertext: the fused form where the shape has one, else the two steps.  fix_ct as in inner_prod.
 static void inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const u64 *const *rlk, hipStream_t s, uint32_t batch = 1,
                        const u64 *fix_ct = nullptr, const u64 *own = nullptr, size_t own_stride = 0);
@@ -1359,14 +899,7 @@ static bool modup_inner_prod(Context &c, Tool &t, u64 *cx, u64 *t_mod_up, const 
     }
     ModupIpArgs ip{};
     ip.cx = cx; ip.evks = rlk; ip.qlp_n = (size_t)t.size_qlp * c.n; ip.qp_n = (size_t)c.size_qp * c.n;
-    ip.fix_limb = 0xffffffffu;
-    if (fix_ct) {
-        const u64 pinv_last = h_invmod_p(c, t.size_ql - 1);
-        ip.fix_limb = t.size_ql - 1;
-        ip.fix_cst = u64x2{pinv_last, h_shoup(pinv_last, c.primes[t.size_ql - 1])};
-        ip.fix_ct = fix_ct;
-        ip.fix_ct_stride = (size_t)t.size_ql * c.n;
-    }
+    set_last_limb_fix(c, t, fix_ct, ip);
     if (fold_inverse) {
         ip.inv_from = t.size_ql;
         ip.inv_lead = fix_ct ? t.size_ql - 1 : 0xffffffffu;
@@ -1384,25 +917,13 @@ static void inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const 
     InnerArgs k{};
     k.cx = cx; k.t_mod_up = t_mod_up; k.evks = rlk; k.mod = c.d_mod.p; k.qlp_prime = t.d_qlp_prime.p;
     k.n = (uint32_t)c.n; k.beta = t.beta; k.qlp_n = (size_t)t.size_qlp * c.n; k.qp_n = (size_t)c.size_qp * c.n;
-    k.fix_limb = 0xffffffffu;
+    set_last_limb_fix(c, t, fix_ct, k);
     k.fpinfo = c.d_fpinfo.p;
     if (own && !(batch > 1 && t.beta <= 4)) throw std::logic_error("inner_prod: own limbs in place need the batched kernel");
     k.own = own; k.own_stride = own_stride; k.alpha = t.alpha; k.ql = t.size_ql;
-    if (fix_ct) {
-        const u64 pinv_last = h_invmod_p(c, t.size_ql - 1);
-        k.fix_limb = t.size_ql - 1;
-        k.fix_cst = u64x2{pinv_last, h_shoup(pinv_last, c.primes[t.size_ql - 1])};
-        k.fix_ct = fix_ct;
-        k.fix_ct_stride = (size_t)t.size_ql * c.n;
-    }
     const dim3 grid((unsigned)(c.n / 512), t.size_qlp), block(256);
     if (batch > 1 && t.beta <= 4) {  // key limbs stay in registers across the ciphertexts
-        switch (t.beta) {
-            case 1: hipLaunchKernelGGL(inner_prod_batched_kernel<1>, grid, block, 0, s, k, batch); break;
-            case 2: hipLaunchKernelGGL(inner_prod_batched_kernel<2>, grid, block, 0, s, k, batch); break;
-            case 3: hipLaunchKernelGGL(inner_prod_batched_kernel<3>, grid, block, 0, s, k, batch); break;
-            default: hipLaunchKernelGGL(inner_prod_batched_kernel<4>, grid, block, 0, s, k, batch); break;
-        }
+        with_beta<4>(t.beta, [&](auto B) { hipLaunchKernelGGL(inner_prod_batched_kernel<decltype(B)::value>, grid, block, 0, s, k, batch); });
         check_launch();
         return;
     }
@@ -1415,14 +936,9 @@ static void inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const 
     }
 }
 
-// DRNSTool::moddown_from_NTT rns_bconv.cu:776-828 for `polys` polynomials cx + z*cx_stride at once.
-// accumulate = false: ct_z = result (the reference call).  accumulate = true: ct_z += result, i.e. the
-// add_to_ct_kernel of keyswitch_inplace (rns_bconv.cu:763-769) fused into the NTT epilogue.
-// folded (ckks): the special limbs of cx already went through the inverse transform's contiguous pass (modup_inner_prod).
-// coeff_input (bfv only): DRNSTool::moddown rns_bconv.cu:712-761 -- cx is already in coefficient form, no inverse transform.
-static void moddown_from_ntt(Context &c, Tool &t, u64 *ct, size_t ct_stride, u64 *cx, size_t cx_stride,
-                             uint32_t polys, int scheme, bool accumulate, u64 *delta, hipStream_t s, bool folded = false,
-                             bool coeff_input = false) {
+// (described with its declaration in pha_internal.h)
+void moddown_from_ntt(Context &c, Tool &t, u64 *ct, size_t ct_stride, u64 *cx, size_t cx_stride, uint32_t polys, int scheme,
+                      bool accumulate, u64 *delta, hipStream_t s, bool folded, bool coeff_input) {
     const size_t n = c.n;
     const uint32_t ql = t.size_ql, qlp = t.size_qlp;
     NttExtra xb;
@@ -1613,10 +1129,12 @@ static void keyswitch_rescale(Context &c, Tool &t, const u64 *ct, const u64 *c2,
     ntt_forward(c, tmp, tmp, dst, plain_sel(0, nl), EPI_FWD_KSRESCALE, x, s);
 }
 
-static void check_level(Context &c, size_t size_Ql, bool need_p) {
+void check_level(Context &c, size_t size_Ql, bool need_p) {
     if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("size_Ql out of range");
     if (need_p && c.size_p == 0) throw std::invalid_argument("context has no special modulus");
 }
+
+bool overlaps(const u64 *a, size_t na, const u64 *b, size_t nb) { return a < b + nb && b < a + na; }
 
 }  // namespace pha
 
@@ -1746,8 +1264,6 @@ int pha_keyswitch_inplace_batched(pha_context_t ctx, size_t size_Ql, uint64_t *c
     PHA_API_END
 }
 
-static bool overlaps(const u64 *a, size_t na, const u64 *b, size_t nb) { return a < b + nb && b < a + na; }
-
 int pha_keyswitch_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, const uint64_t *c2, size_t batch,
                                   const uint64_t *const *rlk, uint64_t *dst, void *stream) {
     PHA_CTX_BEGIN(ctx)
@@ -1869,325 +1385,6 @@ int pha_relinearize_rotate_batched(pha_context_t ctx, size_t size_Ql, const uint
             PHA_HIP(hipStreamWaitEvent(s, c.lanes.join[l], 0));
         }
     }
-    PHA_API_END
-}
-
-int pha_hoisting(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const uint32_t *galois_elts, size_t n_elts,
-                 const uint64_t *const *const *glk, int scheme, void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    need(ct); need(galois_elts); need(glk);
-    if (n_elts == 0) throw std::invalid_argument("steps must not be empty");
-    Context &c = ctx->c;
-    check_level(c, size_Ql, true);
-    Tool &t = c.tool((uint32_t)size_Ql);
-    hipStream_t s = as_stream(stream);
-    if (strict_mode()) {
-        strict_operand(c, "hoisting ct", ct, rows_plain(0, size_Ql), 2, size_Ql * c.n, s);
-        for (size_t e = 0; e < n_elts; e++)
-            if (glk[e]) strict_keys(c, "hoisting Galois key", glk[e], t.beta, (uint32_t)size_Ql, s);
-    }
-    const size_t n = c.n, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n;
-    const bool ntt_dom = ntt_domain_scheme(scheme);
-    // per-element device tables: permutation tables and key pointer tables
-    std::vector<const uint32_t *> h_tabs(n_elts);
-    for (size_t e = 0; e < n_elts; e++) {
-        if (!glk[e]) throw std::logic_error("Galois key not present in hoisting");
-        h_tabs[e] = c.galois_table(galois_elts[e]);
-    }
-    // scratch: c0 copy [Ql][N] | tmp / delta [2][Ql][N] | mod-up [beta][QlP][N] | acc_cx [2][QlP][N] | pointer tables
-    const size_t ptr_words = 2 * n_elts;
-    u64 *base = c.scratch(stream, 3 * ql_n + (size_t)t.beta * qlp_n + 2 * qlp_n + ptr_words);
-    u64 *c0 = base, *tmp = c0 + ql_n, *t_mod_up = tmp + 2 * ql_n, *acc_cx = t_mod_up + (size_t)t.beta * qlp_n;
-    u64 *d_ptrs = acc_cx + 2 * qlp_n;
-    PHA_HIP(hipMemcpyAsync(d_ptrs, h_tabs.data(), n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(d_ptrs + n_elts, glk, n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
-    const uint32_t *const *d_tabs = reinterpret_cast<const uint32_t *const *>(d_ptrs);
-    const u64 *const *const *d_keys = reinterpret_cast<const u64 *const *const *>(d_ptrs + n_elts);
-
-    PHA_HIP(hipMemcpyAsync(c0, ct, ql_n * sizeof(u64), hipMemcpyDeviceToDevice, s));
-    // one mod-up of c1 shared by every rotation (evaluate.cu:1758-1760)
-    modup(c, t, t_mod_up, ct + ql_n, scheme, tmp, s);
-    // all rotations' inner products in one kernel; the unreduced 128-bit accumulators hold floor(2^128 / q_max^2) - 1
-    // products (255 for primes up to 60 bits, 63 for the 61-bit primes the context also accepts)
-    u64 qmax = 0;
-    for (uint32_t i = 0; i < c.size_qp; i++) qmax = std::max(qmax, c.primes[i]);
-    int qbits = 0;
-    while (qbits < 64 && (qmax >> qbits)) qbits++;
-    const size_t max_terms = qbits >= 64 ? 1 : ((size_t)1 << std::min(20, 128 - 2 * qbits)) - 1;
-    const size_t per_call = std::max<size_t>(1, max_terms / t.beta);
-    for (size_t e0 = 0; e0 < n_elts; e0 += per_call) {
-        HoistArgs k{};
-        k.cx = acc_cx; k.t_mod_up = t_mod_up; k.keys = d_keys + e0; k.tables = d_tabs + e0; k.mod = c.d_mod.p;
-        k.qlp_prime = t.d_qlp_prime.p; k.n = (uint32_t)n; k.beta = t.beta;
-        k.n_elts = (uint32_t)std::min(per_call, n_elts - e0); k.accumulate = e0 ? 1 : 0;
-        k.qlp_n = qlp_n; k.qp_n = (size_t)c.size_qp * n;
-        const dim3 hgrid((unsigned)(n / 512), t.size_qlp), hblock(256);
-        switch (t.beta) {
-            case 1: hipLaunchKernelGGL(hoist_inner_prod_kernel<1>, hgrid, hblock, 0, s, k); break;
-            case 2: hipLaunchKernelGGL(hoist_inner_prod_kernel<2>, hgrid, hblock, 0, s, k); break;
-            case 3: hipLaunchKernelGGL(hoist_inner_prod_kernel<3>, hgrid, hblock, 0, s, k); break;
-            case 4: hipLaunchKernelGGL(hoist_inner_prod_kernel<4>, hgrid, hblock, 0, s, k); break;
-            default: hipLaunchKernelGGL(hoist_inner_prod_generic_kernel, hgrid, hblock, 0, s, k); break;
-        }
-        check_launch();
-    }
-    // ct0 <- sum_e galois_e(c0) ; ct1 <- 0 ; then both += moddown(acc_cx) (fused into the NTT epilogue)
-    if (ntt_dom) {
-        hipLaunchKernelGGL(hoist_c0_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql), dim3(256), 0, s, ct, c0,
-                           d_tabs, (uint32_t)n_elts, c.d_mod.p, (uint32_t)n);
-        check_launch();
-    } else {
-        PHA_HIP(hipMemsetAsync(ct, 0, ql_n * sizeof(u64), s));
-        for (size_t e = 0; e < n_elts; e++) {  // coefficient-domain automorphism (src/galois.cu:20-39)
-            hipLaunchKernelGGL(galois_coeff_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql), dim3(256), 0, s,
-                               tmp, c0, c.d_mod.p, 0u, inv_mod_2n(galois_elts[e], n), (uint32_t)n);
-            check_launch();
-            launch_add(c, ct, tmp, ct, size_Ql, 0, s);
-        }
-    }
-    PHA_HIP(hipMemsetAsync(ct + ql_n, 0, ql_n * sizeof(u64), s));
-    moddown_from_ntt(c, t, ct, ql_n, acc_cx, qlp_n, 2, scheme, true, tmp, s);
-    PHA_API_END
-}
-
-int pha_hoisting_weighted(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const uint32_t *galois_elts, size_t n_elts,
-                          const uint64_t *const *const *glk, const uint64_t *const *weights, int scheme, void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    need(ct); need(galois_elts); need(glk); need(weights);
-    if (n_elts == 0) throw std::invalid_argument("steps must not be empty");
-    if (!ntt_domain_scheme(scheme)) throw std::invalid_argument("weighted hoisting takes NTT-form ciphertexts (ckks / bgv)");
-    Context &c = ctx->c;
-    check_level(c, size_Ql, true);
-    Tool &t = c.tool((uint32_t)size_Ql);
-    hipStream_t s = as_stream(stream);
-    if (strict_mode()) {
-        strict_operand(c, "hoisting ct", ct, rows_plain(0, size_Ql), 2, size_Ql * c.n, s);
-        for (size_t e = 0; e < n_elts; e++) {
-            if (glk[e]) strict_keys(c, "hoisting Galois key", glk[e], t.beta, (uint32_t)size_Ql, s);
-            if (weights[e]) strict_operand(c, "hoisting weight", weights[e], rows_qlp(t.size_ql, c.size_q, c.size_p), 1, 0, s);
-        }
-    }
-    const size_t n = c.n, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n;
-    // order the elements: key-switched ones first, main-diagonal ones (element 1, no key) last
-    std::vector<const void *> tabs, keys, w_ks, w_all;
-    std::vector<size_t> order;
-    for (int pass = 0; pass < 2; pass++)
-        for (size_t e = 0; e < n_elts; e++) {
-            if (!weights[e]) throw std::invalid_argument("null weight");
-            if ((galois_elts[e] == 1) == (pass == 1)) order.push_back(e);
-        }
-    size_t n_ks = 0;
-    for (size_t e : order) {
-        tabs.push_back(c.galois_table(galois_elts[e]));
-        w_all.push_back(weights[e]);
-        if (galois_elts[e] != 1) {
-            if (!glk[e]) throw std::logic_error("Galois key not present in hoisting");
-            keys.push_back(glk[e]);
-            n_ks++;
-        }
-    }
-    // scratch: (c0, c1) copy [2][Ql][N] | tmp / delta [2][Ql][N] | mod-up [beta][QlP][N] | acc_cx [2][QlP][N] | pointers
-    const size_t ptr_words = 3 * n_elts;
-    u64 *base = c.scratch(stream, 4 * ql_n + (size_t)t.beta * qlp_n + 2 * qlp_n + ptr_words);
-    u64 *cc = base, *tmp = cc + 2 * ql_n, *t_mod_up = tmp + 2 * ql_n, *acc_cx = t_mod_up + (size_t)t.beta * qlp_n;
-    u64 *d_ptrs = acc_cx + 2 * qlp_n;
-    PHA_HIP(hipMemcpyAsync(d_ptrs, tabs.data(), n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(d_ptrs + n_elts, w_all.data(), n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
-    if (n_ks) PHA_HIP(hipMemcpyAsync(d_ptrs + 2 * n_elts, keys.data(), n_ks * sizeof(void *), hipMemcpyHostToDevice, s));
-    const uint32_t *const *d_tabs = reinterpret_cast<const uint32_t *const *>(d_ptrs);
-    const u64 *const *d_w = reinterpret_cast<const u64 *const *>(d_ptrs + n_elts);
-    const u64 *const *const *d_keys = reinterpret_cast<const u64 *const *const *>(d_ptrs + 2 * n_elts);
-    PHA_HIP(hipMemcpyAsync(cc, ct, 2 * ql_n * sizeof(u64), hipMemcpyDeviceToDevice, s));
-    if (n_ks) {
-        modup(c, t, t_mod_up, ct + ql_n, scheme, tmp, s);
-        const size_t per_call = 63;    // weighted terms below 2^122 each (61-bit primes) in the 128-bit accumulator
-        for (size_t e0 = 0; e0 < n_ks; e0 += per_call) {
-            HoistWArgs kw{};
-            HoistArgs &k = kw.h;
-            k.cx = acc_cx; k.t_mod_up = t_mod_up; k.keys = d_keys + e0; k.tables = d_tabs + e0; k.mod = c.d_mod.p;
-            k.qlp_prime = t.d_qlp_prime.p; k.n = (uint32_t)n; k.beta = t.beta;
-            k.n_elts = (uint32_t)std::min(per_call, n_ks - e0); k.accumulate = e0 ? 1 : 0;
-            k.qlp_n = qlp_n; k.qp_n = (size_t)c.size_qp * n;
-            kw.weights = d_w + e0;
-            const dim3 hgrid((unsigned)(n / 512), t.size_qlp), hblock(256);
-            switch (t.beta) {
-                case 1: hipLaunchKernelGGL(hoist_weighted_inner_prod_kernel<1>, hgrid, hblock, 0, s, kw); break;
-                case 2: hipLaunchKernelGGL(hoist_weighted_inner_prod_kernel<2>, hgrid, hblock, 0, s, kw); break;
-                case 3: hipLaunchKernelGGL(hoist_weighted_inner_prod_kernel<3>, hgrid, hblock, 0, s, kw); break;
-                case 4: hipLaunchKernelGGL(hoist_weighted_inner_prod_kernel<4>, hgrid, hblock, 0, s, kw); break;
-                default: hipLaunchKernelGGL(hoist_weighted_inner_prod_kernel<0>, hgrid, hblock, 0, s, kw); break;
-            }
-            check_launch();
-        }
-    }
-    // ct0 <- sum_e w_e galois_e(c0), ct1 <- sum over the main-diagonal elements of w_e c1; then both += moddown(acc_cx)
-    hipLaunchKernelGGL(hoist_weighted_c_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql, 2), dim3(256), 0, s, ct, cc,
-                       d_tabs, d_w, (uint32_t)n_elts, (uint32_t)n_ks, c.d_mod.p, (uint32_t)n, ql_n);
-    check_launch();
-    if (n_ks) moddown_from_ntt(c, t, ct, ql_n, acc_cx, qlp_n, 2, scheme, true, tmp, s);
-    PHA_API_END
-}
-
-// Core of the baby-step / giant-step entries: `blocks` row blocks that share the input ciphertext and every Galois key.  Block r
-// with weights w[r][i][j] gives out[r] = sum_i rot_{G_i}(sum_j w[r][i][j] (.) rot_{B_j}(ct)).  The fused baby-step kernel treats
-// the (block, giant step) pairs as one list of accumulators, so the baby keys, the gathered digits and the per-baby reductions are
-// paid once for up to 8 of them; everything after it is batched over the blocks.  Every block's result is bit-identical to a
-// one-block call.
-static void bsgs_core(Context &c, Tool &t, const u64 *ct_in, size_t blocks, const uint32_t *baby_elts, size_t nb,
-                      const uint64_t *const *const *baby_glk, const uint32_t *giant_elts, size_t ng,
-                      const uint64_t *const *const *giant_glk, const uint64_t *const *weights, u64 *out, int scheme, void *stream) {
-    hipStream_t s = as_stream(stream);
-    const size_t n = c.n, size_Ql = t.size_ql, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n, G = blocks * ng;
-    if (strict_mode()) {
-        strict_operand(c, "hoisting ct", ct_in, rows_plain(0, size_Ql), 2, ql_n, s);
-        for (size_t j = 0; j < nb; j++)
-            if (baby_glk[j]) strict_keys(c, "baby-step Galois key", baby_glk[j], t.beta, (uint32_t)size_Ql, s);
-        for (size_t i = 0; i < ng; i++)
-            if (giant_glk[i]) strict_keys(c, "giant-step Galois key", giant_glk[i], t.beta, (uint32_t)size_Ql, s);
-        for (size_t i = 0; i < G * nb; i++)
-            if (weights[i]) strict_operand(c, "BSGS weight", weights[i], rows_qlp(t.size_ql, c.size_q, c.size_p), 1, 0, s);
-    }
-    // 128-bit accumulators: every weighted term is below 2^122 (61-bit primes), 63 of them fit; the giant inner products are
-    // plain products (2^120 each for 60-bit primes)
-    size_t nbk = 0, nk = 0;
-    for (size_t j = 0; j < nb; j++) {
-        if (baby_elts[j] != 1 && !baby_glk[j]) throw std::logic_error("Galois key not present in hoisting");
-        nbk += baby_elts[j] != 1;
-    }
-    for (size_t i = 0; i < ng; i++) {
-        if (giant_elts[i] != 1 && !giant_glk[i]) throw std::logic_error("Galois key not present in hoisting");
-        nk += giant_elts[i] != 1;
-    }
-    // what the unreduced 128-bit accumulators of the fused baby-step kernel hold: one s * w product per baby ENTRY (identity entries and
-    // repeated elements included) plus the P-scaled c0 / c1 term, each below q_max^2 -- floor(2^128 / q_max^2) - 1 terms (255 for
-    // primes up to 60 bits, 63 for the 61-bit primes the context also accepts); the giant steps' key products likewise
-    u64 qmax = 0;
-    for (uint32_t i = 0; i < c.size_qp; i++) qmax = std::max(qmax, c.primes[i]);
-    int qbits = 0;
-    while (qbits < 64 && (qmax >> qbits)) qbits++;
-    const size_t max_terms = qbits >= 64 ? 1 : ((size_t)1 << std::min(20, 128 - 2 * qbits)) - 1;
-    if (nb + 1 > max_terms || nk * t.beta > max_terms || nbk > 255)
-        throw std::invalid_argument("too many steps for one call: the 128-bit accumulators hold floor(2^128 / q_max^2) - 1 products (at most "
-                                    "254 baby entries for primes up to 60 bits, 62 for 61-bit primes)");
-    if (2 * G > 65535 || blocks * nk * t.beta > 65535) throw std::invalid_argument("too many row blocks for one call");
-    if (t.beta > 4) throw std::invalid_argument("more than 4 key-switch digits are not supported by the baby-step / giant-step form");
-    bool any_null = false;
-    for (size_t i = 0; i < G * nb; i++) any_null = any_null || !weights[i];
-    std::vector<const void *> h_btab(nb), h_bkeys(nb), h_gtab(ng), h_gkeys;
-    std::vector<uint32_t> h_rank(ng);
-    for (size_t j = 0; j < nb; j++) {
-        h_btab[j] = c.galois_table(baby_elts[j]);
-        h_bkeys[j] = baby_elts[j] == 1 ? nullptr : baby_glk[j];
-    }
-    for (size_t i = 0; i < ng; i++) {
-        h_gtab[i] = c.galois_table(giant_elts[i]);
-        h_rank[i] = giant_elts[i] == 1 ? 0xffffffffu : (uint32_t)h_gkeys.size();
-        if (giant_elts[i] != 1) h_gkeys.push_back(giant_glk[i]);
-    }
-    // scratch: cc [2][Ql][N] | tmp [max(2 G, blocks nk, 2 blocks)][Ql][N] | mod-up [beta][QlP][N] | acc [G][2][QlP][N] |
-    //          B [G][2][Ql][N] | g1 [blocks][nk][Ql][N] | giant mod-up [blocks][nk][beta][QlP][N] | cx [blocks][2][QlP][N] | tables
-    const size_t n_tmp = std::max<size_t>(2 * G, std::max<size_t>(blocks * nk, 2 * blocks));
-    const size_t ptr_words = 2 * nb + G * nb + 2 * ng + nk + (any_null ? qlp_n : 0);   // (+ a zero plane for the missing weights)
-    u64 *base = c.scratch(stream, 2 * ql_n + n_tmp * ql_n + (size_t)t.beta * qlp_n + G * 2 * qlp_n + G * 2 * ql_n + blocks * nk * ql_n +
-                                      blocks * nk * (size_t)t.beta * qlp_n + blocks * 2 * qlp_n + ptr_words);
-    u64 *cc = base, *tmp = cc + 2 * ql_n, *t_mod_up = tmp + n_tmp * ql_n, *acc = t_mod_up + (size_t)t.beta * qlp_n,
-        *B = acc + G * 2 * qlp_n, *g1 = B + G * 2 * ql_n, *mu_g = g1 + blocks * nk * ql_n,
-        *cxg = mu_g + blocks * nk * (size_t)t.beta * qlp_n, *d_ptrs = cxg + blocks * 2 * qlp_n;
-    u64 *p_btab = d_ptrs, *p_bkeys = p_btab + nb, *p_w = p_bkeys + nb, *p_gtab = p_w + G * nb, *p_rank = p_gtab + ng, *p_gkeys = p_rank + ng;
-    PHA_HIP(hipMemcpyAsync(p_btab, h_btab.data(), nb * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(p_bkeys, h_bkeys.data(), nb * sizeof(void *), hipMemcpyHostToDevice, s));
-    std::vector<const void *> h_w(weights, weights + G * nb);
-    if (any_null) {
-        u64 *zero = p_gkeys + nk;
-        PHA_HIP(hipMemsetAsync(zero, 0, qlp_n * sizeof(u64), s));
-        for (auto &w : h_w)
-            if (!w) w = zero;
-    }
-    PHA_HIP(hipMemcpyAsync(p_w, h_w.data(), G * nb * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(p_gtab, h_gtab.data(), ng * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(p_rank, h_rank.data(), ng * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    if (nk) PHA_HIP(hipMemcpyAsync(p_gkeys, h_gkeys.data(), nk * sizeof(void *), hipMemcpyHostToDevice, s));
-    const uint32_t *const *d_btab = reinterpret_cast<const uint32_t *const *>(p_btab);
-    const u64 *const *const *d_bkeys = reinterpret_cast<const u64 *const *const *>(p_bkeys);
-    const u64 *const *d_w = reinterpret_cast<const u64 *const *>(p_w);
-    const uint32_t *const *d_gtab = reinterpret_cast<const uint32_t *const *>(p_gtab);
-    const u64 *const *const *d_gkeys = reinterpret_cast<const u64 *const *const *>(p_gkeys);
-
-    PHA_HIP(hipMemcpyAsync(cc, ct_in, 2 * ql_n * sizeof(u64), hipMemcpyDeviceToDevice, s));   // (out may be ct_in: one-block in-place form)
-    // baby steps: one mod-up of c1, then every (block, giant step)'s weighted sum of the hoisted inner products (and of the c0 / c1
-    // terms, pre-multiplied by P) in one pass over the baby keys per 8 accumulators; B = moddown(acc), one batched launch set
-    if (nbk) modup(c, t, t_mod_up, cc + ql_n, scheme, tmp, s);
-    {
-        BsgsArgs k{};
-        k.acc = acc; k.t_mod_up = t_mod_up; k.keys = d_bkeys; k.tables = d_btab; k.weights = d_w; k.mod = c.d_mod.p;
-        k.qlp_prime = t.d_qlp_prime.p; k.n = (uint32_t)n; k.beta = t.beta; k.nb = (uint32_t)nb;
-        k.qlp_n = qlp_n; k.qp_n = (size_t)c.size_qp * n;
-        k.cc = cc; k.p_mod_q = t.p_mod_q2.p; k.ql = (uint32_t)size_Ql; k.ql_n = ql_n;
-        k.fpinfo = c.d_fpinfo.p;
-        const dim3 grid((unsigned)(n / 256), t.size_qlp), block(256);
-#define PHA_BSGS_GO(NG)                                                                                                   \
-    do {                                                                                                                  \
-        switch (t.beta) {                                                                                                 \
-            case 1: hipLaunchKernelGGL((hoist_bsgs_inner_prod_kernel<NG, 1>), grid, block, 0, s, k); break;              \
-            case 2: hipLaunchKernelGGL((hoist_bsgs_inner_prod_kernel<NG, 2>), grid, block, 0, s, k); break;              \
-            case 3: hipLaunchKernelGGL((hoist_bsgs_inner_prod_kernel<NG, 3>), grid, block, 0, s, k); break;              \
-            default: hipLaunchKernelGGL((hoist_bsgs_inner_prod_kernel<NG, 4>), grid, block, 0, s, k); break;             \
-        }                                                                                                                 \
-    } while (0)
-        for (size_t g0 = 0; g0 < G;) {
-            const size_t left = G - g0;
-            k.g0 = (uint32_t)g0;
-            if (left >= 16) { PHA_BSGS_GO(16); g0 += 16; }
-            else if (left >= 8) { PHA_BSGS_GO(8); g0 += 8; }
-            else if (left >= 4) { PHA_BSGS_GO(4); g0 += 4; }
-            else if (left >= 2) { PHA_BSGS_GO(2); g0 += 2; }
-            else { PHA_BSGS_GO(1); g0 += 1; }
-            check_launch();
-        }
-#undef PHA_BSGS_GO
-    }
-    moddown_from_ntt(c, t, B, ql_n, acc, qlp_n, (uint32_t)(2 * G), scheme, false, tmp, s);
-    // giant steps: permutations (every block in one launch), then per block ONE mod-down for the sum of its key-switch inner products
-    hipLaunchKernelGGL(bsgs_combine_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql, (unsigned)blocks), dim3(256), 0, s, out, g1, B,
-                       d_gtab, reinterpret_cast<const uint32_t *>(p_rank), (uint32_t)ng, (uint32_t)nk, c.d_mod.p, (uint32_t)n, ql_n);
-    check_launch();
-    if (nk) {
-        modup(c, t, mu_g, g1, scheme, tmp, s, (uint32_t)(blocks * nk));
-        MultiInnerArgs k{cxg, mu_g, d_gkeys, c.d_mod.p, t.d_qlp_prime.p, (uint32_t)n, t.beta, (uint32_t)nk, qlp_n, (size_t)c.size_qp * n};
-        hipLaunchKernelGGL(inner_prod_multi_kernel, dim3((unsigned)(n / 512), t.size_qlp, (unsigned)blocks), dim3(256), 0, s, k);
-        check_launch();
-        moddown_from_ntt(c, t, out, ql_n, cxg, qlp_n, (uint32_t)(2 * blocks), scheme, true, tmp, s);
-    }
-}
-
-int pha_hoisting_weighted_bsgs(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const uint32_t *baby_elts, size_t n_baby,
-                               const uint64_t *const *const *baby_glk, const uint32_t *giant_elts, size_t n_giant,
-                               const uint64_t *const *const *giant_glk, const uint64_t *const *weights, int scheme, void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    need(ct); need(baby_elts); need(baby_glk); need(giant_elts); need(giant_glk); need(weights);
-    if (n_baby == 0 || n_giant == 0) throw std::invalid_argument("steps must not be empty");
-    if (!ntt_domain_scheme(scheme)) throw std::invalid_argument("weighted hoisting takes NTT-form ciphertexts (ckks / bgv)");
-    Context &c = ctx->c;
-    check_level(c, size_Ql, true);
-    bsgs_core(c, c.tool((uint32_t)size_Ql), ct, 1, baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights, ct, scheme, stream);
-    PHA_API_END
-}
-
-int pha_hoisting_weighted_bsgs_blocks(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t n_blocks, const uint32_t *baby_elts,
-                                      size_t n_baby, const uint64_t *const *const *baby_glk, const uint32_t *giant_elts, size_t n_giant,
-                                      const uint64_t *const *const *giant_glk, const uint64_t *const *weights, uint64_t *out, int scheme,
-                                      void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    need(ct); need(baby_elts); need(baby_glk); need(giant_elts); need(giant_glk); need(weights); need(out);
-    if (n_blocks == 0) return 0;
-    if (n_baby == 0 || n_giant == 0) throw std::invalid_argument("steps must not be empty");
-    if (!ntt_domain_scheme(scheme)) throw std::invalid_argument("weighted hoisting takes NTT-form ciphertexts (ckks / bgv)");
-    Context &c = ctx->c;
-    check_level(c, size_Ql, true);
-    const size_t ql_n = size_Ql * c.n;
-    if (overlaps(out, n_blocks * 2 * ql_n, ct, 2 * ql_n)) throw std::invalid_argument("out must not overlap ct");
-    bsgs_core(c, c.tool((uint32_t)size_Ql), ct, n_blocks, baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights, out, scheme,
-              stream);
     PHA_API_END
 }
 
@@ -2314,8 +1511,7 @@ int pha_apply_galois_batched(pha_context_t ctx, const uint64_t *src, uint64_t *d
                                dst + p0 * c.n, src + p0 * c.n, tab, (uint32_t)c.n);
         }
     } else {
-        hipLaunchKernelGGL(galois_coeff_kernel, dim3((unsigned)(c.n / 256), (unsigned)cms, (unsigned)polys), dim3(256), 0,
-                           as_stream(stream), dst, src, c.d_mod.p, 0u, inv_mod_2n(galois_elt, c.n), (uint32_t)c.n);
+        launch_galois_coeff(c, dst, src, galois_elt, cms, 0, polys, as_stream(stream));
     }
     check_launch();
     PHA_API_END
@@ -2347,9 +1543,7 @@ int pha_apply_galois(pha_context_t ctx, const uint64_t *src, uint64_t *dst, uint
     Context &c = ctx->c;
     if (!(galois_elt & 1) || galois_elt >= 2 * c.n) throw std::invalid_argument("Galois element is not valid");
     if (mod_start + cms > c.size_qp) throw std::invalid_argument("modulus index out of range");
-    hipLaunchKernelGGL(galois_coeff_kernel, dim3((unsigned)(c.n / 256), (unsigned)cms), dim3(256), 0,
-                       as_stream(stream), dst, src, c.d_mod.p, (uint32_t)mod_start, inv_mod_2n(galois_elt, c.n), (uint32_t)c.n);
-    check_launch();
+    launch_galois_coeff(c, dst, src, galois_elt, cms, mod_start, 1, as_stream(stream));
     PHA_API_END
 }
 

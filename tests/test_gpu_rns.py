@@ -212,7 +212,10 @@ def test_galois(gpu):
 @pytest.mark.parametrize("name,scheme,ql,elts", [("hyb12_a2", O.CKKS, 6, [5, 25, 125]), ("hyb12_a2", O.CKKS, 3, [5]),
                                                  ("hyb12_a2", O.BFV, 6, [5, 8191]), ("c1_bfv4096", O.CKKS, 2, [5, 25]),
                                                  ("hyb12_a2", O.BGV, 6, [5, 25]),
-                                                 ("c3_ckks16", O.CKKS, 45, [5, 25, 125, 625])])
+                                                 ("c3_ckks16", O.CKKS, 45, [5, 25, 125, 625]),
+                                                 # 61-bit special primes: the 128-bit accumulators hold 63 products, beta = 3 -> 21
+                                                 # elements per launch, so 22 elements take a second launch that adds to the first
+                                                 ("p61_a2", O.CKKS, 6, [pow(5, i, 1 << 13) for i in range(1, 23)])])
 def test_hoisting(name, scheme, ql, elts, gpu):
     """hoisting_inplace (src/evaluate.cu:1670-1866): ct <- sum_e rotate_e(ct) with one shared mod-up."""
     import phantom_fhe_amd as P
@@ -225,10 +228,12 @@ def test_hoisting(name, scheme, ql, elts, gpu):
         ctx.set_plain_modulus(BGV_T)
         tool.set_plain_modulus(BGV_T)
     r = rng_for(70)
-    glk = [_keys(oc, r, primes, n, size_q, size_p) for _ in elts]
+    pool = [_keys(oc, r, primes, n, size_q, size_p) for _ in range(3 if len(elts) > 8 else len(elts))]
+    glk = [pool[i % len(pool)] for i in range(len(elts))]        # many elements: a few distinct keys, reused
     ct = np.stack([uniform_poly(r, primes[:ql], n) for _ in range(2)])
     d_ct = P.to_device(ct, gpu)
-    keys = [P.PhantomRelinKey.from_numpy(k, gpu) for k in glk]
+    dev_pool = [P.PhantomRelinKey.from_numpy(k, gpu) for k in pool]
+    keys = [dev_pool[i % len(pool)] for i in range(len(elts))]
     ctx.hoisting(ql, d_ct, elts, keys, scheme)
     ref = tool.hoisting(ct, elts, [[k[i] for i in range(tool.beta)] for k in glk], scheme)
     assert np.array_equal(P.to_host(d_ct), ref)
