@@ -19,8 +19,8 @@
  * library does not -- on limbs below 2^50 the dyadic, inner-product, hoisting and epilogue kernels compute in FP64 (exact only for
  * words below 2^52), so a non-canonical word there gives wrong residues WITHOUT an error.  Every word the library writes is
  * canonical, so chains of its own calls keep the precondition.  It is CHECKABLE (r06): pha_check_canonical / _keys count the
- * offending words of a buffer, and strict mode (PHA_STRICT=1 in the environment, or pha_set_strict) makes every entry point that
- * takes caller-supplied operands count first and return status -1 naming the operand instead of computing.
+ * offending words of a buffer, and strict mode (PHA_STRICT=1 in the environment, or pha_set_strict) makes the entry points listed
+ * at pha_set_strict count first and return status -1 naming the operand instead of computing.
  * Capturing calls into a hipGraph: warm the same call up once first (same level and batch: an arena grows on demand, and growth is
  * an allocation), and capture on an EXPLICIT stream -- the arenas behind NULL / hipStreamPerThread belong to the calling host thread
  * and are released when that thread exits, so a graph captured on them must not be replayed after the thread is gone.
@@ -54,9 +54,9 @@ const char *pha_last_error(void);
  * pha_check_canonical_keys: the limbs a key switch at level size_Ql READS of n_keys keys [2][size_QP][N] (rows 0 .. size_Ql - 1
  *   and the special rows), keys = DEVICE array of device pointers (PhantomRelinKey::public_keys_ptr()).
  * pha_set_strict(on): strict mode on / off for the process, returns the previous state.  Default: on iff PHA_STRICT=1 was in the
- *   environment when the library was first used.  In strict mode the dyadic, tensor, mod-up / inner-product / mod-down, key-switch
- *   and hoisting entries check ct / c2 / t_mod_up / keys / weights before they compute (one synchronising pass per operand) and
- *   fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
+ *   environment when the library was first used.  In strict mode the dyadic, tensor, mod-up / inner-product / mod-down, key-switch,
+ *   hoisting and BFV multiply entries check ct / c2 / t_mod_up / keys / weights / ct1 and ct2 before they compute (one
+ *   synchronising pass per operand) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
 int pha_check_canonical(pha_context_t ctx, const uint64_t *data, size_t coeff_modulus_size, size_t start_modulus_idx,
                         size_t size_P_tail, size_t polys, size_t poly_stride, uint64_t *bad_words, void *stream);
 int pha_check_canonical_keys(pha_context_t ctx, size_t size_Ql, const uint64_t *const *keys, size_t n_keys, uint64_t *bad_words,
@@ -429,7 +429,11 @@ int pha_generate_one_kswitch_key(pha_context_t ctx, const uint64_t *sk_ntt, cons
 /* bfv_multiply_behz (src/evaluate.cu:447-548), the 2 x 2 case at the top data level: ct1, ct2 [2][Q][N] in
  * coefficient form -> dst [3][Q][N] in coefficient form (ct1 == ct2 takes the squaring kernels, like the
  * reference).  Needs pha_context_set_plain_modulus; the auxiliary base Bsk u {m_tilde} (src/rns.cu:392-560) and
- * its NTT tables are built on first use.  dst must not alias the inputs. */
+ * its NTT tables are built on first use.
+ * ALL the BFV multiply entries, single-pair and batched: the inputs are only read; every pha_bfv_multiply_* entry refuses a dst
+ * that overlaps an input (status -1); in strict mode they and pha_bfv_mul_relin_hps_overq_leveled check both operands, named
+ * "<entry> ct1" / "<entry> ct2" with the entry's own name (without the pha_ prefix).  A single-pair entry is its batched
+ * pipeline at batch = 1. */
 int pha_bfv_multiply_behz(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst, void *stream);
 /* bfv_multiply_hps with mul_tech_type::hps (src/evaluate.cu:674-818; bConv_HPS src/rns_bconv.cu:248-372;
  * scaleAndRound_HPS_QR_R src/rns.cu:1700-1746): same shapes as pha_bfv_multiply_behz.  The base R (|Q| + 1 primes
@@ -456,13 +460,13 @@ int pha_bfv_mul_relin_hps_overq_leveled(pha_context_t ctx, size_t size_Ql, const
                                         const uint64_t *const *rlk, uint64_t *dst, void *stream);
 /* Extension (the reference loops over ciphertexts): the BFV multiplies over a batch of independent ciphertext pairs.
  * ct1, ct2 [batch][2][Q][N] -> dst [batch][3][Q][N] (the ct3 layout of pha_relinearize_rotate_batched), coefficient form over
- * the full base Q, canonical.  Ciphertext b of dst is bit-identical to what the matching single-pair entry returns for pair b.
+ * the full base Q, canonical.  Ciphertext b of dst is bit-identical to what the matching single-pair entry returns for pair b
+ * (the same pipeline at batch = 1).
  * `chunk` pairs (0 = the library's default, 8) go through one set of launches whose count does not depend on chunk, with no
  * device-to-device copies; the scratch is sized by chunk, not by batch, and every chunk gives the same bits.  ct1 == ct2 (the
  * same pointer) takes the squaring path for the whole batch (for hps_overq: the reference's squaring shortcut, as the single
- * entry keeps it).  The inputs are only read; dst overlapping an input is refused (status -1), as are null pointers, a missing
- * plain modulus and size_Ql outside [1, |Q|]; batch == 0 does nothing.  Unlike the single entries these check both operands in
- * strict mode ("<entry> ct1" / "<entry> ct2").  More than 32 limbs in a conversion's input base: those conversions run per
+ * entry keeps it).  Refused (status -1), besides what all the multiply entries refuse: null pointers, a missing plain modulus and
+ * size_Ql outside [1, |Q|]; batch == 0 does nothing.  More than 32 limbs in a conversion's input base: those conversions run per
  * polynomial (bConv_HPS's second branch), everything else stays batched.
  *   pha_bfv_multiply_hps_overq_batched: size_Ql == |Q| is hps_overq, size_Ql < |Q| is hps_overq_leveled with |Q| - size_Ql
  *   levels dropped (pha_bfv_multiply_hps_overq_leveled). */

@@ -83,33 +83,40 @@ __global__ __launch_bounds__(256) void sk_fix_kernel(SkArgs k) {
 }
 
 
-static LimbSel aux_sel(uint32_t count, uint32_t aux0) {  // a buffer of `count` limbs whose table rows start at aux0
-    LimbSel s = plain_sel(0, count);
-    s.remap_from = 0;
-    s.remap_add = aux0;
-    return s;
+// ---- the DRNSTool stages of the BEHZ multiply on `polys` polynomials per launch (blockIdx.z; strides in words).  The multiply
+//      runs them on the 2 B or 3 B polynomials of a chunk, the pha_* step entries at the end of this file on one. ----
+// fastbconv_m_tilde rns.cu:1249-1278: src [.][Q][N] -> dst [polys][Bsk + 1][N] packed.  Phase 1 with m_tilde * qhat^-1 (the
+// converter's own scale-in factors, Context::behz), one conversion for all Bsk + 1 outputs
+static void launch_fastbconv_m_tilde(Context &c, Behz &b, u64 *dst, const u64 *src, size_t src_stride, uint32_t polys, hipStream_t s) {
+    launch_bconv(c, b.d_q_to_bskmt.p, 0, polys, b.size_q, b.size_bsk + 1, b.q_to_bskmt.split_kind, dst, (size_t)(b.size_bsk + 1) * c.n,
+                 src, src_stride, nullptr, true, s);
 }
-
-// BEHZ_mul_1 evaluate.cu:404-441 for the two polynomials of one ciphertext
-static void behz_lift(Context &c, Behz &b, const u64 *ct, u64 *out_q, u64 *out_bsk, u64 *tmp, hipStream_t s) {
-    const uint32_t n = (uint32_t)c.n, sq = b.size_q, sk = b.size_bsk;
-    const size_t qn = (size_t)sq * n;
-    NttExtra xq;
-    xq.batch = 2;
-    xq.poly_stride = qn;
-    ntt_forward(c, ct, out_q, out_q, plain_sel(0, sq), EPI_FWD_CANON, xq, s);      // out of place: no copy of ct first
-    // (1) q -> Bsk u {m_tilde}: phase 1 with m_tilde * qhat^-1 (the converter's own scale-in factors, Context::behz), one
-    // conversion for all Bsk + 1 outputs
-    u64 *lift = tmp + 2 * qn;  // lift [2][Bsk + 1][N]
-    launch_bconv(c, b.d_q_to_bskmt.p, 0, 2, sq, sk + 1, b.q_to_bskmt.split_kind, lift, (size_t)(sk + 1) * n, ct, qn, nullptr, true, s);
-    // (2) small Montgomery reduction modulo q, switching to base Bsk
-    MrqArgs ma{out_bsk, lift, c.d_mod.p, b.prod_q_mod_bsk.p, b.inv_mt_mod_bsk.p, b.neg_inv_prod_q_mod_mt, b.aux0, sk, n};
-    hipLaunchKernelGGL(sm_mrq_kernel, dim3(n / 256, sk, 2), dim3(256), 0, s, ma);
+// sm_mrq rns.cu:1326-1338: src [polys][Bsk + 1][N] packed -> dst [.][Bsk][N]
+static void launch_sm_mrq(Context &c, Behz &b, u64 *dst, size_t dst_stride, const u64 *src, uint32_t polys, hipStream_t s) {
+    const uint32_t n = (uint32_t)c.n;
+    MrqArgs ma{dst, src, c.d_mod.p, b.prod_q_mod_bsk.p, b.inv_mt_mod_bsk.p, b.neg_inv_prod_q_mod_mt, b.aux0, b.size_bsk, n, dst_stride};
+    hipLaunchKernelGGL(sm_mrq_kernel, dim3(n / 256, b.size_bsk, polys), dim3(256), 0, s, ma);
     check_launch();
-    NttExtra xb;
-    xb.batch = 2;
-    xb.poly_stride = (size_t)sk * n;
-    ntt_forward(c, out_bsk, out_bsk, out_bsk, aux_sel(sk, b.aux0), EPI_FWD_CANON, xb, s);
+}
+// fast_floor rns.cu:1394-1419: (x_q [.][Q][N], x_bsk [.][Bsk][N]) -> dst [polys][Bsk][N] packed; conv [polys][Bsk][N] scratch
+static void launch_fast_floor(Context &c, Behz &b, u64 *dst, const u64 *x_q, size_t q_stride, const u64 *x_bsk, size_t bsk_stride,
+                              u64 *conv, uint32_t polys, hipStream_t s) {
+    const uint32_t n = (uint32_t)c.n;
+    const size_t bn = (size_t)b.size_bsk * n;
+    launch_bconv(c, b.d_q_to_bsk.p, 0, polys, b.size_q, b.size_bsk, b.q_to_bsk.split_kind, conv, bn, x_q, q_stride, nullptr, true, s);
+    FloorArgs fa{dst, x_bsk, conv, c.d_mod.p, b.inv_prod_q_mod_bsk.p, b.aux0, n, bn, bsk_stride, bn};
+    hipLaunchKernelGGL(fast_floor_kernel, dim3(n / 256, b.size_bsk, polys), dim3(256), 0, s, fa);
+    check_launch();
+}
+// fastbconv_sk rns.cu:1470-1510: x [polys][Bsk][N] packed (B limbs, then the m_sk limb) -> out_q [polys][Q][N] packed; msk [polys][N] scratch
+static void launch_fastbconv_sk(Context &c, Behz &b, u64 *out_q, const u64 *x, u64 *msk, uint32_t polys, hipStream_t s) {
+    const uint32_t n = (uint32_t)c.n;
+    const size_t qn = (size_t)b.size_q * n, bn = (size_t)b.size_bsk * n;
+    launch_bconv(c, b.d_b_to_msk.p, 0, polys, b.size_b, 1, b.b_to_msk.split_kind, msk, n, x, bn, nullptr, true, s);   // B -> m_sk
+    launch_bconv(c, b.d_b_to_q.p, 0, polys, b.size_b, b.size_q, b.b_to_q.split_kind, out_q, qn, x, bn, nullptr, true, s);
+    SkArgs ka{out_q, msk, x + (size_t)b.size_b * n, c.d_mod.p, b.prod_b_mod_q.p, b.inv_prod_b_mod_msk, b.m_sk, n, qn, n, bn};
+    hipLaunchKernelGGL(sk_fix_kernel, dim3(n / 256, b.size_q, polys), dim3(256), 0, s, ka);
+    check_launch();
 }
 
 // ---- HPS variant (mul_tech_type::hps): bConv_HPS src/rns_bconv.cu:248-372, scaleAndRound_HPS_QR_R src/rns.cu:1700-1746.
@@ -375,46 +382,6 @@ static LimbSel qr_sel(uint32_t size_q, uint32_t size_r, uint32_t aux0) {  // [Q 
 
 using namespace pha;
 
-extern "C" int pha_bfv_multiply_hps(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst,
-                                    void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    if (!ctx || !ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
-    Context &c = ctx->c;
-    Hps &h = c.hps();
-    hipStream_t s = as_stream(stream);
-    const uint32_t n = (uint32_t)c.n, sq = h.size_q, sr = h.size_r, sqr = sq + sr;
-    const size_t qn = (size_t)sq * n, rn = (size_t)sr * n, qrn = (size_t)sqr * n;
-    const bool square = ct1 == ct2;
-    // scratch: x1 [3][Q+R] | x2 [2][Q+R] | y [max(Q, R)] | tmp [3][R]
-    u64 *base = c.scratch(stream, 5 * qrn + std::max(qn, rn) + 3 * rn);
-    u64 *x1 = base, *x2 = x1 + 3 * qrn, *y = x2 + 2 * qrn, *tmp = y + std::max(qn, rn);
-    // lift every input polynomial from base Q to Q || R (evaluate.cu:702-716, :733-748)
-    for (int w = 0; w < (square ? 1 : 2); w++) {
-        const u64 *ct = w ? ct2 : ct1;
-        u64 *x = w ? x2 : x1;
-        for (uint32_t p = 0; p < 2; p++)
-            PHA_HIP(hipMemcpyAsync(x + p * qrn, ct + p * qn, qn * sizeof(u64), hipMemcpyDeviceToDevice, s));
-        bconv_hps(c, h.q_to_r, h.d_q_to_r.p, h.q_inv.p, h.alpha_q_mod_r.p, x + qn, ct, y, s, 2, qrn, qn);   // both polynomials
-        NttExtra xf;
-        xf.batch = 2;
-        xf.poly_stride = qrn;
-        ntt_forward(c, x, x, x, qr_sel(sq, sr, h.aux0), EPI_FWD_CANON, xf, s);
-    }
-    // tensor product over Q || R: the Q limbs and the R limbs live in different table rows
-    const u64 *rhs = square ? x1 : x2;
-    launch_tensor(c, x1, rhs, x1, sq, 0, square, s, sqr);
-    launch_tensor(c, x1 + qn, rhs + qn, x1 + qn, sr, h.aux0, square, s, sqr);
-    NttExtra xi;
-    xi.batch = 3;
-    xi.poly_stride = qrn;
-    ntt_inverse(c, x1, x1, x1, qr_sel(sq, sr, h.aux0), EPI_INV_CANON, xi, s);
-    // scale by t/Q and round into base R, then R -> Q (evaluate.cu:800-808): the three polynomials in one launch each
-    ScaleRoundArgs ka{tmp, x1, h.frac.p, h.div_mod_r.p, c.d_mod.p, sq, sr, h.aux0, n, rn, qrn};
-    launch_scale_round(c, ka, s, 3);
-    bconv_hps(c, h.r_to_q, h.d_r_to_q.p, h.r_inv.p, h.alpha_r_mod_q.p, dst, tmp, y, s, 3, qn, rn);
-    PHA_API_END
-}
-
 // ExpandCRTBasis_Ql_Q (src/rns.cu:1810-1836): the Ql limbs times the product of the dropped primes, the dropped limbs zero.
 // blockIdx.y over the |Q| limbs of dst; src has |Ql| limbs with the same limb pitch, so dst == src works in place.
 struct ExpandArgs {
@@ -457,60 +424,21 @@ static void launch_expand(Context &c, HpsQ &h, u64 *dst, const u64 *src, hipStre
     check_launch();
 }
 
-// bfv_multiply_hps with mul_tech hps_overq (h of the top level) or hps_overq_leveled with levels dropped (h of a lower level):
-// src/evaluate.cu:674-818, the overq branches :709-711, :745-751, :790-795.  Operands and result are over the full base Q.
-// ct1 == ct2 (the same pointer) is the reference's squaring shortcut (:720-731), kept as it is.
-static void hps_overq_multiply(Context &c, HpsQ &h, const u64 *ct1, const u64 *ct2, u64 *dst, void *stream,
-                               bool keep_c2_low = false) {
-    hipStream_t s = as_stream(stream);
-    const uint32_t n = (uint32_t)c.n, sq = h.size_q, sr = h.size_r, sqr = sq + sr, sqf = h.size_q_full;
-    const size_t qn = (size_t)sq * n, rn = (size_t)sr * n, qrn = (size_t)sqr * n, qfn = (size_t)sqf * n;
-    const bool square = ct1 == ct2;
-    // scratch: x1 [3][Ql+Rl] | x2 [2][Ql+Rl] | y [max(Q, Rl)]
-    u64 *base = c.scratch(stream, 5 * qrn + std::max(qfn, rn));
-    u64 *x1 = base, *x2 = x1 + 3 * qrn, *y = x2 + 2 * qrn;
-    for (uint32_t p = 0; p < 2; p++) {   // first operand: (scaled down to Ql when levels are dropped, :709-710) exact lift to Ql || Rl
-        if (h.drop) launch_scale_round_q(c, x1 + p * qrn, ct1 + p * qfn, h.frac_drop.p, h.div_mod_q_drop.p, sq, h.drop, s);
-        else PHA_HIP(hipMemcpyAsync(x1 + p * qrn, ct1 + p * qfn, qn * sizeof(u64), hipMemcpyDeviceToDevice, s));
-    }
-    bconv_hps(c, h.q_to_r, h.d_q_to_r.p, h.q_inv.p, h.alpha_q_mod_r.p, x1 + qn, x1, y, s, 2, qrn, qrn);
-    if (!square) {   // second operand: Q -> Rl by bConv_BEHZ_var1, then Rl -> Ql exactly (:745-751); both polynomials per launch
-        launch_bconv(c, h.d_q_to_r_var1.p, 0, 2, h.q_to_r_var1.isz, sr, h.q_to_r_var1.split_kind, x2 + qn, qrn, ct2, qfn, nullptr, true, s);
-        bconv_hps(c, h.r_to_q, h.d_r_to_q.p, h.r_inv.p, h.alpha_r_mod_q.p, x2, x2 + qn, y, s, 2, qrn, qrn);
-    }
-    NttExtra xf;
-    xf.batch = 2;
-    xf.poly_stride = qrn;
-    ntt_forward(c, x1, x1, x1, qr_sel(sq, sr, h.aux0), EPI_FWD_CANON, xf, s);
-    if (!square) ntt_forward(c, x2, x2, x2, qr_sel(sq, sr, h.aux0), EPI_FWD_CANON, xf, s);
-    const u64 *rhs = square ? x1 : x2;
-    launch_tensor(c, x1, rhs, x1, sq, 0, square, s, sqr);
-    launch_tensor(c, x1 + qn, rhs + qn, x1 + qn, sr, h.aux0, square, s, sqr);
-    NttExtra xi;
-    xi.batch = 3;
-    xi.poly_stride = qrn;
-    ntt_inverse(c, x1, x1, x1, qr_sel(sq, sr, h.aux0), EPI_INV_CANON, xi, s);
-    // scale by t / Rl and round straight into base Ql (:790-792; the three polynomials in one launch), expand to Q (:794-795)
-    launch_scale_round_q(c, dst, x1, h.frac.p, h.div_mod_q.p, sq, sr, s, 3, qfn, qrn);
-    for (uint32_t p = 0; p < 3; p++)
-        if (h.drop && !(keep_c2_low && p == 2)) launch_expand(c, h, dst + p * qfn, dst + p * qfn, s);   // (:957-958: c2 stays at level l)
+// dst[i] += src[i] * prod(dropped primes) on the Ql limbs only (ExpandCRTBasis_Ql_Q_add_to_ct, src/rns.cu:1838-1858)
+__global__ __launch_bounds__(256) void hps_expand_add_kernel(const ExpandArgs k) {
+    const uint32_t i = blockIdx.y, coeff = blockIdx.x * 256 + threadIdx.x;
+    const size_t id = (size_t)i * k.n + coeff;
+    const u64 q = k.mod[i].value;
+    k.dst[id] = add_mod(shoup(k.src[id], u64x2{k.c[i], k.c_shoup[i]}, q), k.dst[id], q);
 }
-
-extern "C" int pha_bfv_multiply_hps_overq(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst,
-                                          void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    if (!ctx || !ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
-    hps_overq_multiply(ctx->c, ctx->c.hps_overq(), ct1, ct2, dst, stream);
-    PHA_API_END
-}
-
-extern "C" int pha_bfv_multiply_hps_overq_leveled(pha_context_t ctx, size_t size_Ql, const uint64_t *ct1, const uint64_t *ct2,
-                                                  uint64_t *dst, void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    if (!ctx || !ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
-    if (size_Ql < 1 || size_Ql > ctx->c.size_q) throw std::invalid_argument("RNSBase is invalid");
-    hps_overq_multiply(ctx->c, ctx->c.hps_overq((uint32_t)size_Ql), ct1, ct2, dst, stream);
-    PHA_API_END
+// `polys` polynomials, dst spaced dst_stride words and src spaced src_stride (the kernel takes one polynomial)
+static void launch_expand_add(Context &c, HpsQ &h, u64 *dst, size_t dst_stride, const u64 *src, size_t src_stride, uint32_t polys,
+                              hipStream_t s) {
+    for (uint32_t p = 0; p < polys; p++) {
+        ExpandArgs ka{dst + p * dst_stride, src + p * src_stride, h.drop_mod_q.p, h.drop_mod_q_shoup.p, c.d_mod.p, h.size_q, (uint32_t)c.n};
+        hipLaunchKernelGGL(hps_expand_add_kernel, dim3((unsigned)(c.n / 256), h.size_q), dim3(256), 0, s, ka);
+        check_launch();
+    }
 }
 
 extern "C" int pha_scaleAndRound_HPS_Q_Ql(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream) {
@@ -529,39 +457,6 @@ extern "C" int pha_ExpandCRTBasis_Ql_Q(pha_context_t ctx, size_t size_Ql, uint64
     Context &c = ctx->c;
     if (size_Ql < 1 || size_Ql >= c.size_q) throw std::invalid_argument("at least one level has to be dropped");
     launch_expand(c, c.hps_overq((uint32_t)size_Ql), dst, src, as_stream(stream));
-    PHA_API_END
-}
-
-// dst[i] += src[i] * prod(dropped primes) on the Ql limbs only (ExpandCRTBasis_Ql_Q_add_to_ct, src/rns.cu:1838-1858)
-__global__ __launch_bounds__(256) void hps_expand_add_kernel(const ExpandArgs k) {
-    const uint32_t i = blockIdx.y, coeff = blockIdx.x * 256 + threadIdx.x;
-    const size_t id = (size_t)i * k.n + coeff;
-    const u64 q = k.mod[i].value;
-    k.dst[id] = add_mod(shoup(k.src[id], u64x2{k.c[i], k.c_shoup[i]}, q), k.dst[id], q);
-}
-
-// bfv_mul_relin_hps under hps_overq_leveled with levels dropped (src/evaluate.cu:822-1027): the product's c2 is left at
-// level l, key-switched there, and the results go onto the Ql limbs of (c0, c1).  dst [2][Q][N].
-extern "C" int pha_bfv_mul_relin_hps_overq_leveled(pha_context_t ctx, size_t size_Ql, const uint64_t *ct1, const uint64_t *ct2,
-                                                   const uint64_t *const *rlk, uint64_t *dst, void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    if (!ctx || !ct1 || !ct2 || !rlk || !dst) throw std::invalid_argument("null pointer");
-    Context &c = ctx->c;
-    if (size_Ql < 1 || size_Ql >= c.size_q) throw std::invalid_argument("at least one level has to be dropped");
-    HpsQ &h = c.hps_overq((uint32_t)size_Ql);
-    hipStream_t s = as_stream(stream);
-    const size_t n = c.n, qln = size_Ql * n, qfn = (size_t)c.size_q * n;
-    u64 *d3 = c.scratch_outer(stream, 3 * qfn + 2 * qln), *res = d3 + 3 * qfn;   // the inner calls use the stream's own arena
-    hps_overq_multiply(c, h, ct1, ct2, d3, stream, true);
-    PHA_HIP(hipMemsetAsync(res, 0, 2 * qln * sizeof(u64), s));
-    const int rc = pha_keyswitch_inplace(ctx, size_Ql, res, d3 + 2 * qfn, rlk, /*scheme bfv*/ 1, stream);
-    if (rc != 0) throw std::runtime_error(pha_last_error());
-    PHA_HIP(hipMemcpyAsync(dst, d3, 2 * qfn * sizeof(u64), hipMemcpyDeviceToDevice, s));
-    for (int p = 0; p < 2; p++) {
-        ExpandArgs ka{dst + (size_t)p * qfn, res + (size_t)p * qln, h.drop_mod_q.p, h.drop_mod_q_shoup.p, c.d_mod.p, h.size_q, (uint32_t)n};
-        hipLaunchKernelGGL(hps_expand_add_kernel, dim3((unsigned)(n / 256), h.size_q), dim3(256), 0, s, ka);
-        check_launch();
-    }
     PHA_API_END
 }
 
@@ -590,63 +485,16 @@ extern "C" int pha_keyswitch_inplace_bfv_leveled(pha_context_t ctx, size_t size_
     PHA_API_END
 }
 
-extern "C" int pha_bfv_multiply_behz(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst,
-                                     void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    if (!ctx || !ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
-    Context &c = ctx->c;
-    Behz &b = c.behz();
-    hipStream_t s = as_stream(stream);
-    const uint32_t n = (uint32_t)c.n, sq = b.size_q, sk = b.size_bsk, sb = b.size_b;
-    const size_t qn = (size_t)sq * n, bn = (size_t)sk * n;
-    const bool square = ct1 == ct2;
-    // scratch: q1 [3][Q] | b1 [3][Bsk] | q2 [2][Q] | b2 [2][Bsk] | tmp (y [2][Q] + lift [2][Bsk+1], later conv / floor)
-    const size_t tmp_words = std::max(2 * qn + 2 * (bn + n), 6 * bn + 3 * (size_t)n);
-    u64 *base = c.scratch(stream, 3 * qn + 3 * bn + 2 * qn + 2 * bn + tmp_words);
-    u64 *q1 = base, *b1 = q1 + 3 * qn, *q2 = b1 + 3 * bn, *b2 = q2 + 2 * qn, *tmp = b2 + 2 * bn;
-    behz_lift(c, b, ct1, q1, b1, tmp, s);
-    if (!square) behz_lift(c, b, ct2, q2, b2, tmp, s);
-    // step 4: tensor product in both bases (evaluate.cu:479-498)
-    launch_tensor(c, q1, square ? q1 : q2, q1, sq, 0, square, s);
-    launch_tensor(c, b1, square ? b1 : b2, b1, sk, b.aux0, square, s);
-    // steps 5-6: inverse transforms fused with the multiplication by t (:518-530)
-    NttExtra xq;
-    xq.batch = 3;
-    xq.poly_stride = qn;
-    xq.scale = b.t_q.p;
-    xq.scale_shoup = b.t_q_shoup.p;
-    ntt_inverse(c, q1, q1, q1, plain_sel(0, sq), EPI_INV_SCALE, xq, s);
-    NttExtra xb;
-    xb.batch = 3;
-    xb.poly_stride = bn;
-    xb.scale = b.t_bsk.p;
-    xb.scale_shoup = b.t_bsk_shoup.p;
-    ntt_inverse(c, b1, b1, b1, aux_sel(sk, b.aux0), EPI_INV_SCALE, xb, s);
-    // steps 7-8 for the three polynomials in one launch each
-    u64 *conv = tmp, *fl = tmp + 3 * bn, *msk = fl + 3 * bn;  // conv [3][Bsk][N], fl [3][Bsk][N], msk [3][N]
-    // step 7 fast_floor (rns.cu:1394-1419)
-    launch_bconv(c, b.d_q_to_bsk.p, 0, 3, sq, sk, b.q_to_bsk.split_kind, conv, bn, q1, qn, nullptr, true, s);
-    FloorArgs fa{fl, b1, conv, c.d_mod.p, b.inv_prod_q_mod_bsk.p, b.aux0, n, bn, bn, bn};
-    hipLaunchKernelGGL(fast_floor_kernel, dim3(n / 256, sk, 3), dim3(256), 0, s, fa);
-    check_launch();
-    // step 8 fastbconv_sk (rns.cu:1470-1510)
-    launch_bconv(c, b.d_b_to_msk.p, 0, 3, sb, 1, b.b_to_msk.split_kind, msk, n, fl, bn, nullptr, true, s);   // B -> m_sk
-    launch_bconv(c, b.d_b_to_q.p, 0, 3, sb, sq, b.b_to_q.split_kind, dst, qn, fl, bn, nullptr, true, s);
-    SkArgs ka{dst, msk, fl + (size_t)sb * n, c.d_mod.p, b.prod_b_mod_q.p, b.inv_prod_b_mod_msk, b.m_sk, n, qn, n, bn};
-    hipLaunchKernelGGL(sk_fix_kernel, dim3(n / 256, sq, 3), dim3(256), 0, s, ka);
-    check_launch();
-    PHA_API_END
-}
-
-// ---- batched BFV multiplies (extension: the reference loops over ciphertexts) -------------------------------------------------
+// ---- the BFV multiplies: ONE pipeline per variant, over `batch` independent pairs (the batched entries are an extension: the
+//      reference loops over ciphertexts; the single-pair entries are the same pipeline at batch = 1) ------------------------------
 // ct1, ct2 [batch][2][Q][N] -> dst [batch][3][Q][N], the ct3 layout of pha_relinearize_rotate_batched.  A chunk of C pairs goes
 // through ONE set of launches: every stage covers its 2C or 3C polynomials (blockIdx.z, or y for the scale-and-round kernels), so the
 // launch count does not depend on C, and there are no device-to-device copies.  Working buffers per chunk, L = |Q| + |aux| limbs:
 //   xa [C][2][L][N] | xb [C][2][L][N] | xp [C][3][L][N] | stage scratch
 // The operands' Q limbs are produced by the forward transform reading the caller's ciphertext out of place, the auxiliary limbs by
 // the conversion straight into place; the tensor product writes xp (its [3]-polynomial pitch is what every later stage and dst
-// share), in one launch over the Q rows and the auxiliary rows (launch_tensor_batched).  Every stage computes per coefficient
-// exactly what the single-pair entries compute, so ciphertext b of the result has the single entry's bits for pair b.
+// share), in one launch over the Q rows and the auxiliary rows (launch_tensor_batched).  Every stage works per coefficient, so
+// ciphertext b of a batch has the bits a single-pair call returns for pair b, whatever the chunk.
 //
 // Default pairs per chunk.  Measured at config 4 (N = 2^15, 30 data limbs, t = 1032193; B = 64, profiles/bfv_multiply_batched.md): per-op
 // time falls steeply from chunk 1 to 4 (HPS 0.376 -> 0.264 ms) and stays within 3 % from 4 to 64; 8 is the fastest for BEHZ (0.3005 ms)
@@ -656,7 +504,7 @@ constexpr size_t kBfvMaxChunk = 1024;   // 3 * chunk polynomials ride in grid z 
 
 static bool bfv_overlaps(const u64 *a, size_t na, const u64 *b, size_t nb) { return a < b + nb && b < a + na; }
 
-// refusals and strict checks shared by the three entries; returns the pairs per chunk
+// refusals and strict checks shared by every multiply entry (`name`: the entry, for the strict message); returns the pairs per chunk
 static size_t bfv_batched_begin(Context &c, const char *name, const u64 *ct1, const u64 *ct2, const u64 *dst, size_t batch,
                                 size_t chunk, hipStream_t s) {
     const size_t qn = (size_t)c.size_q * c.n;
@@ -690,15 +538,11 @@ static void lift_q_ntt(Context &c, const u64 *ct, size_t ct_stride, u64 *x, size
     ntt_forward(c, ct, x, x, plain_sel(0, sq), EPI_FWD_CANON, xq, s);
 }
 
-extern "C" int pha_bfv_multiply_hps_batched(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst,
-                                            size_t batch, size_t chunk, void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
-    if (batch == 0) return 0;
-    Context &c = ctx->c;
-    Hps &h = c.hps();
+// bfv_multiply_hps with mul_tech hps (src/evaluate.cu:674-818)
+static void hps_multiply(Context &c, Hps &h, const u64 *ct1, const u64 *ct2, u64 *dst, size_t batch, size_t chunk, const char *name,
+                         void *stream) {
     hipStream_t s = as_stream(stream);
-    const size_t C = bfv_batched_begin(c, "bfv_multiply_hps_batched", ct1, ct2, dst, batch, chunk, s);
+    const size_t C = bfv_batched_begin(c, name, ct1, ct2, dst, batch, chunk, s);
     const uint32_t n = (uint32_t)c.n, sq = h.size_q, sr = h.size_r, sqr = sq + sr;
     const size_t qn = (size_t)sq * n, rn = (size_t)sr * n, qrn = (size_t)sqr * n;
     const bool square = ct1 == ct2;
@@ -728,19 +572,16 @@ extern "C" int pha_bfv_multiply_hps_batched(pha_context_t ctx, const uint64_t *c
         launch_scale_round(c, ka, s, 3 * B);
         bconv_hps(c, h.r_to_q, h.d_r_to_q.p, h.r_inv.p, h.alpha_r_mod_q.p, dst + b0 * 3 * qn, tmp, y, s, 3 * B, qn, rn);
     }
-    PHA_API_END
 }
 
-extern "C" int pha_bfv_multiply_hps_overq_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct1, const uint64_t *ct2,
-                                                  uint64_t *dst, size_t batch, size_t chunk, void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
-    Context &c = ctx->c;
-    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("RNSBase is invalid");
-    if (batch == 0) return 0;
-    HpsQ &h = c.hps_overq((uint32_t)size_Ql);
+// bfv_multiply_hps with mul_tech hps_overq (h of the top level) or hps_overq_leveled with levels dropped (h of a lower level):
+// src/evaluate.cu:674-818, the overq branches :709-711, :745-751, :790-795.  Operands and result are over the full base Q.
+// ct1 == ct2 (the same pointer) is the reference's squaring shortcut (:720-731), kept as it is.  keep_c2_low (levels dropped,
+// batch == 1: bfv_mul_relin_hps, :957-958) leaves the product's c2 at level l: only c0 and c1 are expanded to Q.
+static void hps_overq_multiply(Context &c, HpsQ &h, const u64 *ct1, const u64 *ct2, u64 *dst, size_t batch, size_t chunk,
+                               const char *name, void *stream, bool keep_c2_low = false) {
     hipStream_t s = as_stream(stream);
-    const size_t C = bfv_batched_begin(c, "bfv_multiply_hps_overq_batched", ct1, ct2, dst, batch, chunk, s);
+    const size_t C = bfv_batched_begin(c, name, ct1, ct2, dst, batch, chunk, s);
     const uint32_t n = (uint32_t)c.n, sq = h.size_q, sr = h.size_r, sqr = sq + sr, sqf = h.size_q_full;
     const size_t qn = (size_t)sq * n, rn = (size_t)sr * n, qrn = (size_t)sqr * n, qfn = (size_t)sqf * n;
     const bool square = ct1 == ct2;
@@ -777,21 +618,16 @@ extern "C" int pha_bfv_multiply_hps_overq_batched(pha_context_t ctx, size_t size
         // scale by t / Rl and round straight into base Ql (:790-792), expand to Q (:794-795)
         u64 *out = dst + b0 * 3 * qfn;
         launch_scale_round_q(c, out, xp, h.frac.p, h.div_mod_q.p, sq, sr, s, 3 * B, qfn, qrn);
-        if (h.drop) launch_expand(c, h, out, out, s, 3 * B, qfn);
+        if (h.drop) launch_expand(c, h, out, out, s, keep_c2_low ? 2u : 3 * B, qfn);
     }
-    PHA_API_END
 }
 
-extern "C" int pha_bfv_multiply_behz_batched(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst,
-                                             size_t batch, size_t chunk, void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
-    if (batch == 0) return 0;
-    Context &c = ctx->c;
-    Behz &b = c.behz();
+// bfv_multiply_behz (src/evaluate.cu:447-548)
+static void behz_multiply(Context &c, Behz &b, const u64 *ct1, const u64 *ct2, u64 *dst, size_t batch, size_t chunk, const char *name,
+                          void *stream) {
     hipStream_t s = as_stream(stream);
-    const size_t C = bfv_batched_begin(c, "bfv_multiply_behz_batched", ct1, ct2, dst, batch, chunk, s);
-    const uint32_t n = (uint32_t)c.n, sq = b.size_q, sk = b.size_bsk, sb = b.size_b, sqk = sq + sk;
+    const size_t C = bfv_batched_begin(c, name, ct1, ct2, dst, batch, chunk, s);
+    const uint32_t n = (uint32_t)c.n, sq = b.size_q, sk = b.size_bsk, sqk = sq + sk;
     const size_t qn = (size_t)sq * n, bn = (size_t)sk * n, qbn = (size_t)sqk * n;
     const bool square = ct1 == ct2;
     // scratch: xa [C][2][Q+Bsk] | xb [C][2][Q+Bsk] | xp [C][3][Q+Bsk] | tmp (lift [C][2][Bsk+1], later conv / floor / m_sk)
@@ -800,16 +636,14 @@ extern "C" int pha_bfv_multiply_behz_batched(pha_context_t ctx, const uint64_t *
     u64 *xb = xa + C * 2 * qbn, *xp = xb + C * 2 * qbn, *tmp = xp + C * 3 * qbn;
     for (size_t b0 = 0; b0 < batch; b0 += C) {
         const uint32_t B = (uint32_t)std::min(C, batch - b0);
-        // BEHZ_mul_1 (evaluate.cu:404-441) for the 2 B polynomials of each operand, as behz_lift
+        // BEHZ_mul_1 (evaluate.cu:404-441) for the 2 B polynomials of each operand: q -> Bsk u {m_tilde}, then the small Montgomery
+        // reduction modulo q switches to base Bsk
         for (int w = 0; w < (square ? 1 : 2); w++) {
             const u64 *ct = (w ? ct2 : ct1) + b0 * 2 * qn;
             u64 *x = w ? xb : xa;
             lift_q_ntt(c, ct, qn, x, qbn, sq, 2 * B, s);
-            launch_bconv(c, b.d_q_to_bskmt.p, 0, 2 * B, sq, sk + 1, b.q_to_bskmt.split_kind, tmp, (size_t)(sk + 1) * n, ct, qn, nullptr,
-                         true, s);
-            MrqArgs ma{x + qn, tmp, c.d_mod.p, b.prod_q_mod_bsk.p, b.inv_mt_mod_bsk.p, b.neg_inv_prod_q_mod_mt, b.aux0, sk, n, qbn};
-            hipLaunchKernelGGL(sm_mrq_kernel, dim3(n / 256, sk, 2 * B), dim3(256), 0, s, ma);
-            check_launch();
+            launch_fastbconv_m_tilde(c, b, tmp, ct, qn, 2 * B, s);
+            launch_sm_mrq(c, b, x + qn, qbn, tmp, 2 * B, s);
             NttExtra xk;
             xk.batch = 2 * B;
             xk.poly_stride = qbn;
@@ -824,19 +658,91 @@ extern "C" int pha_bfv_multiply_behz_batched(pha_context_t ctx, const uint64_t *
         xi.scale_shoup = b.t_qb_shoup.p;
         ntt_inverse(c, xp, xp, xp, qr_sel(sq, sk, b.aux0), EPI_INV_SCALE, xi, s);
         u64 *conv = tmp, *fl = tmp + (size_t)B * 3 * bn, *msk = fl + (size_t)B * 3 * bn;  // conv, fl [3B][Bsk][N], msk [3B][N]
-        u64 *out = dst + b0 * 3 * qn;
-        // step 7 fast_floor (rns.cu:1394-1419)
-        launch_bconv(c, b.d_q_to_bsk.p, 0, 3 * B, sq, sk, b.q_to_bsk.split_kind, conv, bn, xp, qbn, nullptr, true, s);
-        FloorArgs fa{fl, xp + qn, conv, c.d_mod.p, b.inv_prod_q_mod_bsk.p, b.aux0, n, bn, qbn, bn};
-        hipLaunchKernelGGL(fast_floor_kernel, dim3(n / 256, sk, 3 * B), dim3(256), 0, s, fa);
-        check_launch();
-        // step 8 fastbconv_sk (rns.cu:1470-1510)
-        launch_bconv(c, b.d_b_to_msk.p, 0, 3 * B, sb, 1, b.b_to_msk.split_kind, msk, n, fl, bn, nullptr, true, s);   // B -> m_sk
-        launch_bconv(c, b.d_b_to_q.p, 0, 3 * B, sb, sq, b.b_to_q.split_kind, out, qn, fl, bn, nullptr, true, s);
-        SkArgs ka{out, msk, fl + (size_t)sb * n, c.d_mod.p, b.prod_b_mod_q.p, b.inv_prod_b_mod_msk, b.m_sk, n, qn, n, bn};
-        hipLaunchKernelGGL(sk_fix_kernel, dim3(n / 256, sq, 3 * B), dim3(256), 0, s, ka);
-        check_launch();
+        launch_fast_floor(c, b, fl, xp, qbn, xp + qn, qbn, conv, 3 * B, s);   // step 7
+        launch_fastbconv_sk(c, b, dst + b0 * 3 * qn, fl, msk, 3 * B, s);      // step 8
     }
+}
+
+// Every entry: its own argument checks, then one call of its variant's pipeline (which refuses a dst overlapping an input and, in
+// strict mode, checks both operands under the entry's name).
+
+extern "C" int pha_bfv_multiply_behz(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
+    behz_multiply(ctx->c, ctx->c.behz(), ct1, ct2, dst, 1, 1, "bfv_multiply_behz", stream);
+    PHA_API_END
+}
+
+extern "C" int pha_bfv_multiply_behz_batched(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst,
+                                             size_t batch, size_t chunk, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
+    if (batch == 0) return 0;
+    behz_multiply(ctx->c, ctx->c.behz(), ct1, ct2, dst, batch, chunk, "bfv_multiply_behz_batched", stream);
+    PHA_API_END
+}
+
+extern "C" int pha_bfv_multiply_hps(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
+    hps_multiply(ctx->c, ctx->c.hps(), ct1, ct2, dst, 1, 1, "bfv_multiply_hps", stream);
+    PHA_API_END
+}
+
+extern "C" int pha_bfv_multiply_hps_batched(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst,
+                                            size_t batch, size_t chunk, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
+    if (batch == 0) return 0;
+    hps_multiply(ctx->c, ctx->c.hps(), ct1, ct2, dst, batch, chunk, "bfv_multiply_hps_batched", stream);
+    PHA_API_END
+}
+
+extern "C" int pha_bfv_multiply_hps_overq(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst,
+                                          void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
+    hps_overq_multiply(ctx->c, ctx->c.hps_overq(), ct1, ct2, dst, 1, 1, "bfv_multiply_hps_overq", stream);
+    PHA_API_END
+}
+
+extern "C" int pha_bfv_multiply_hps_overq_leveled(pha_context_t ctx, size_t size_Ql, const uint64_t *ct1, const uint64_t *ct2,
+                                                  uint64_t *dst, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
+    if (size_Ql < 1 || size_Ql > ctx->c.size_q) throw std::invalid_argument("RNSBase is invalid");
+    hps_overq_multiply(ctx->c, ctx->c.hps_overq((uint32_t)size_Ql), ct1, ct2, dst, 1, 1, "bfv_multiply_hps_overq_leveled", stream);
+    PHA_API_END
+}
+
+extern "C" int pha_bfv_multiply_hps_overq_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct1, const uint64_t *ct2,
+                                                  uint64_t *dst, size_t batch, size_t chunk, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !dst) throw std::invalid_argument("null pointer");
+    if (size_Ql < 1 || size_Ql > ctx->c.size_q) throw std::invalid_argument("RNSBase is invalid");
+    if (batch == 0) return 0;
+    hps_overq_multiply(ctx->c, ctx->c.hps_overq((uint32_t)size_Ql), ct1, ct2, dst, batch, chunk, "bfv_multiply_hps_overq_batched", stream);
+    PHA_API_END
+}
+
+// bfv_mul_relin_hps under hps_overq_leveled with levels dropped (src/evaluate.cu:822-1027): the product's c2 is left at
+// level l, key-switched there, and the results go onto the Ql limbs of (c0, c1).  dst [2][Q][N].
+extern "C" int pha_bfv_mul_relin_hps_overq_leveled(pha_context_t ctx, size_t size_Ql, const uint64_t *ct1, const uint64_t *ct2,
+                                                   const uint64_t *const *rlk, uint64_t *dst, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    if (!ct1 || !ct2 || !rlk || !dst) throw std::invalid_argument("null pointer");
+    Context &c = ctx->c;
+    if (size_Ql < 1 || size_Ql >= c.size_q) throw std::invalid_argument("at least one level has to be dropped");
+    HpsQ &h = c.hps_overq((uint32_t)size_Ql);
+    hipStream_t s = as_stream(stream);
+    const size_t n = c.n, qln = size_Ql * n, qfn = (size_t)c.size_q * n;
+    u64 *d3 = c.scratch_outer(stream, 3 * qfn + 2 * qln), *res = d3 + 3 * qfn;   // the inner calls use the stream's own arena
+    hps_overq_multiply(c, h, ct1, ct2, d3, 1, 1, "bfv_mul_relin_hps_overq_leveled", stream, true);
+    PHA_HIP(hipMemsetAsync(res, 0, 2 * qln * sizeof(u64), s));
+    const int rc = pha_keyswitch_inplace(ctx, size_Ql, res, d3 + 2 * qfn, rlk, /*scheme bfv*/ 1, stream);
+    if (rc != 0) throw std::runtime_error(pha_last_error());
+    PHA_HIP(hipMemcpyAsync(dst, d3, 2 * qfn * sizeof(u64), hipMemcpyDeviceToDevice, s));
+    launch_expand_add(c, h, dst, qfn, res, qln, 2, s);
     PHA_API_END
 }
 
@@ -1072,7 +978,7 @@ int pha_exact_convert_array(pha_base_converter_t conv, uint64_t *dst, const uint
 
 // ---- the DRNSTool steps of the BFV multiplies as entry points of their own (include/rns.cuh:167-200), ONE polynomial per call,
 //      so that a caller written like bfv_multiply_behz / bfv_multiply_hps (src/evaluate.cu:447-548, :674-818) links against
-//      this library step by step.  The whole multiplies above run the same kernels on two or three polynomials per launch. ----
+//      this library step by step.  The whole multiplies above call the same stage launchers with 2 B or 3 B polynomials. ----
 static void need_top(Context &c, size_t size_Ql, const char *what) {
     if (size_Ql != c.size_q) throw std::invalid_argument(std::string(what) + ": the auxiliary base exists at the top data level only");
 }
@@ -1093,9 +999,7 @@ int pha_fastbconv_m_tilde(pha_context_t ctx, size_t size_Ql, uint64_t *dst, cons
     if (!dst || !src) throw std::invalid_argument("null pointer");
     Context &c = ctx->c;
     need_top(c, size_Ql, "fastbconv_m_tilde");
-    Behz &b = c.behz();
-    launch_bconv(c, b.d_q_to_bskmt.p, 0, 1, b.size_q, b.size_bsk + 1, b.q_to_bskmt.split_kind, dst, 0, src, 0, nullptr, true,
-                 as_stream(stream));
+    launch_fastbconv_m_tilde(c, c.behz(), dst, src, 0, 1, as_stream(stream));
     PHA_API_END
 }
 
@@ -1105,10 +1009,7 @@ int pha_sm_mrq(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t 
     if (!dst || !src) throw std::invalid_argument("null pointer");
     Context &c = ctx->c;
     need_top(c, size_Ql, "sm_mrq");
-    Behz &b = c.behz();
-    MrqArgs ma{dst, src, c.d_mod.p, b.prod_q_mod_bsk.p, b.inv_mt_mod_bsk.p, b.neg_inv_prod_q_mod_mt, b.aux0, b.size_bsk, (uint32_t)c.n};
-    hipLaunchKernelGGL(sm_mrq_kernel, dim3((unsigned)(c.n / 256), b.size_bsk, 1), dim3(256), 0, as_stream(stream), ma);
-    check_launch();
+    launch_sm_mrq(c, c.behz(), dst, 0, src, 1, as_stream(stream));
     PHA_API_END
 }
 
@@ -1120,13 +1021,8 @@ int pha_fast_floor(pha_context_t ctx, size_t size_Ql, const uint64_t *input_base
     Context &c = ctx->c;
     need_top(c, size_Ql, "fast_floor");
     Behz &b = c.behz();
-    hipStream_t s = as_stream(stream);
-    const uint32_t n = (uint32_t)c.n;
-    u64 *conv = c.scratch(stream, (size_t)b.size_bsk * n);
-    launch_bconv(c, b.d_q_to_bsk.p, 0, 1, b.size_q, b.size_bsk, b.q_to_bsk.split_kind, conv, 0, input_base_q, 0, nullptr, true, s);
-    FloorArgs fa{out_base_Bsk, input_base_Bsk, conv, c.d_mod.p, b.inv_prod_q_mod_bsk.p, b.aux0, n, 0, 0, 0};
-    hipLaunchKernelGGL(fast_floor_kernel, dim3(n / 256, b.size_bsk, 1), dim3(256), 0, s, fa);
-    check_launch();
+    u64 *conv = c.scratch(stream, (size_t)b.size_bsk * c.n);
+    launch_fast_floor(c, b, out_base_Bsk, input_base_q, 0, input_base_Bsk, 0, conv, 1, as_stream(stream));
     PHA_API_END
 }
 
@@ -1137,14 +1033,8 @@ int pha_fastbconv_sk(pha_context_t ctx, size_t size_Ql, const uint64_t *input_ba
     Context &c = ctx->c;
     need_top(c, size_Ql, "fastbconv_sk");
     Behz &b = c.behz();
-    hipStream_t s = as_stream(stream);
-    const uint32_t n = (uint32_t)c.n;
-    u64 *msk = c.scratch(stream, n);
-    launch_bconv(c, b.d_b_to_msk.p, 0, 1, b.size_b, 1, b.b_to_msk.split_kind, msk, 0, input_base_Bsk, 0, nullptr, true, s);
-    launch_bconv(c, b.d_b_to_q.p, 0, 1, b.size_b, b.size_q, b.b_to_q.split_kind, out_base_q, 0, input_base_Bsk, 0, nullptr, true, s);
-    SkArgs ka{out_base_q, msk, input_base_Bsk + (size_t)b.size_b * n, c.d_mod.p, b.prod_b_mod_q.p, b.inv_prod_b_mod_msk, b.m_sk, n, 0, 0, 0};
-    hipLaunchKernelGGL(sk_fix_kernel, dim3(n / 256, b.size_q, 1), dim3(256), 0, s, ka);
-    check_launch();
+    u64 *msk = c.scratch(stream, c.n);
+    launch_fastbconv_sk(c, b, out_base_q, input_base_Bsk, msk, 1, as_stream(stream));
     PHA_API_END
 }
 
@@ -1177,10 +1067,7 @@ int pha_ExpandCRTBasis_Ql_Q_add_to_ct(pha_context_t ctx, size_t size_Ql, uint64_
     if (!dst || !src) throw std::invalid_argument("null pointer");
     Context &c = ctx->c;
     if (size_Ql < 1 || size_Ql >= c.size_q) throw std::invalid_argument("at least one level has to be dropped");
-    HpsQ &h = c.hps_overq((uint32_t)size_Ql);
-    ExpandArgs ka{dst, src, h.drop_mod_q.p, h.drop_mod_q_shoup.p, c.d_mod.p, h.size_q, (uint32_t)c.n};
-    hipLaunchKernelGGL(hps_expand_add_kernel, dim3((unsigned)(c.n / 256), h.size_q), dim3(256), 0, as_stream(stream), ka);
-    check_launch();
+    launch_expand_add(c, c.hps_overq((uint32_t)size_Ql), dst, 0, src, 0, 1, as_stream(stream));
     PHA_API_END
 }
 

@@ -5,9 +5,9 @@
 // (pha_arith.h: fp_from_canon is exact only for words below 2^52), so a word >= its modulus there can give a wrong residue with no
 // error.  Two remedies, neither on the hot path:
 //   * pha_check_canonical / pha_check_canonical_keys count the words of a buffer that are >= their limb's modulus;
-//   * strict mode (PHA_STRICT=1 in the environment when the library is loaded, or pha_set_strict(1)): every entry point that
-//     takes caller-supplied operands counts first and fails with status -1 (invalid_argument, naming the operand) instead of
-//     computing.  Strict mode synchronises the stream per checked operand: a debugging aid, not for capture or timing.
+//   * strict mode (PHA_STRICT=1 in the environment when the library is loaded, or pha_set_strict(1)): the entry points that
+//     include/phantom_amd.h lists at pha_set_strict (dyadic, tensor, mod-up / inner product / mod-down, key switch, hoisting, BFV
+//     multiply) count first and fail with status -1 (invalid_argument, naming the operand) instead of computing.  Strict mode synchronises the stream per checked operand: a debugging aid, not for capture or timing.
 #include <atomic>
 #include <cstdlib>
 

@@ -623,36 +623,26 @@ Behz &Context::behz() {
     }
     {
         std::vector<u64x2> ipq(b->size_bsk), imt(b->size_bsk);
-        std::vector<u64> pq(b->size_bsk), tb(b->size_bsk), tbs(b->size_bsk);
+        std::vector<u64> pq(b->size_bsk);
         for (uint32_t j = 0; j < b->size_bsk; j++) {
             const u64 p = primes[b->aux0 + j];
             pq[j] = prod_mod(0, size_q, p);                         // :548-553
             ipq[j] = pair(h_invmod(pq[j], p), p);                   // :508-518
             imt[j] = pair(h_invmod(m_tilde % p, p), p);             // :537-546
-            tb[j] = plain_t;                                        // :467-479
-            tbs[j] = h_shoup(plain_t, p);
         }
         b->inv_prod_q_mod_bsk.upload(ipq);
         b->inv_mt_mod_bsk.upload(imt);
         b->prod_q_mod_bsk.upload(pq);
-        b->t_bsk.upload(tb);
-        b->t_bsk_shoup.upload(tbs);
     }
     {
-        std::vector<u64> pb(size_q), tq(size_q), tqs(size_q);
-        for (uint32_t i = 0; i < size_q; i++) {
-            pb[i] = prod_mod(b->aux0, b->size_b, primes[i]);
-            tq[i] = plain_t;
-            tqs[i] = h_shoup(plain_t, primes[i]);
-        }
+        std::vector<u64> pb(size_q);
+        for (uint32_t i = 0; i < size_q; i++) pb[i] = prod_mod(b->aux0, b->size_b, primes[i]);
         b->prod_b_mod_q.upload(pb);
-        b->t_q.upload(tq);
-        b->t_q_shoup.upload(tqs);
-        // the same scales by limb of a [Q || Bsk] buffer (batched multiply: one inverse transform over both bases)
-        std::vector<u64> tqb(tq), tqbs(tqs);
-        for (uint32_t j = 0; j < b->size_bsk; j++) {
+        // t (:467-479) by limb of a [Q || Bsk] buffer: one inverse transform over both bases multiplies by it
+        std::vector<u64> tqb, tqbs;
+        for (uint32_t i = 0; i < size_q + b->size_bsk; i++) {
             tqb.push_back(plain_t);
-            tqbs.push_back(h_shoup(plain_t, primes[b->aux0 + j]));
+            tqbs.push_back(h_shoup(plain_t, primes[i < size_q ? i : b->aux0 + i - size_q]));
         }
         b->t_qb.upload(tqb);
         b->t_qb_shoup.upload(tqbs);

@@ -182,8 +182,7 @@ struct Behz {
     DevBuf<u64x2> inv_prod_q_mod_bsk, inv_mt_mod_bsk;    // [Bsk]
     DevBuf<u64> prod_q_mod_bsk;                          // [Bsk]
     DevBuf<u64> prod_b_mod_q;                            // [Q]
-    DevBuf<u64> t_q, t_q_shoup, t_bsk, t_bsk_shoup;      // t with its Shoup quotient per limb (iNTT scale)
-    DevBuf<u64> t_qb, t_qb_shoup;                        // the same over [Q || Bsk] (batched multiply)
+    DevBuf<u64> t_qb, t_qb_shoup;                        // [Q + Bsk] t with its Shoup quotient per limb (iNTT scale)
     u64x2 neg_inv_prod_q_mod_mt{}, inv_prod_b_mod_msk{};
 };
 

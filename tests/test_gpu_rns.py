@@ -1,6 +1,8 @@
 """GPU parity: dyadic kernels, fast base conversion, mod-up, key-switch inner product, mod-down,
 keyswitch_inplace, CKKS rescale and Galois permutations vs the CPU oracle, bit-exact, at the
 BASELINE.json configurations (full size for C3/C4)."""
+import functools
+
 import numpy as np
 import pytest
 
@@ -787,6 +789,116 @@ def test_bfv_hps_overq_leveled(name, plain_t, ql, gpu):
     # the top level through the leveled entry is plain hps_overq
     ctx.bfv_multiply_hps_overq_leveled(size_q, d1, d2, dst)
     assert np.array_equal(P.to_host(dst), O.HpsOverQ(oc, plain_t).multiply(ct1, ct2))
+
+
+def test_bfv_mul_relin_leveled_squares(gpu):
+    """bfv_mul_relin_hps_overq_leveled with ct1 is ct2 (the squaring shortcut, c2 left at level l) vs the oracle, on the smallest
+    set test_bfv_hps_overq_leveled uses with a level dropped."""
+    import phantom_fhe_amd as P
+    name, plain_t, ql = "hyb12_a2", 1032193, 4
+    log_n, primes, size_p = primes_of(name)
+    n = 1 << log_n
+    size_q = len(primes) - size_p
+    oc, ctx = oracle_ctx(name), _ctx(name, gpu)
+    ctx.set_plain_modulus(plain_t)
+    hq, tool = O.HpsOverQ(oc, plain_t, ql), O.Tool(oc, ql)
+    r = rng_for(156)
+    ct1 = np.stack([uniform_poly(r, primes[:size_q], n) for _ in range(2)])
+    ct1[:, :, :32] = np.array(primes[:size_q], dtype=np.uint64)[None, :, None] - 1
+    evk = _keys(oc, r, primes, n, size_q, size_p)
+    rlk = P.PhantomRelinKey.from_numpy(evk, gpu)
+    d1 = P.to_device(ct1, gpu)
+    fused = P.to_device(np.zeros((2, size_q, n), dtype=np.uint64), gpu)
+    ctx.bfv_mul_relin_hps_overq_leveled(ql, d1, d1, rlk.public_keys_ptr, fused)
+    assert np.array_equal(P.to_host(fused), hq.mul_relin_leveled(tool, ct1, ct1, [evk[i] for i in range(tool.beta)]))
+    assert np.array_equal(P.to_host(d1), ct1)
+
+
+BFV_SINGLE_ENTRIES = ["bfv_multiply_behz", "bfv_multiply_hps", "bfv_multiply_hps_overq", "bfv_multiply_hps_overq_leveled"]
+
+
+@functools.lru_cache(maxsize=None)
+def _c1_pair_and_products():
+    """c1_bfv4096 with t = 65537: one seeded pair and the oracle's product per single-pair entry (the leveled one with one level
+    dropped).  Shared by the tests below, which leave the arrays as they are."""
+    name, plain_t = "c1_bfv4096", 65537
+    log_n, primes, size_p = primes_of(name)
+    n = 1 << log_n
+    size_q = len(primes) - size_p
+    oc = oracle_ctx(name)
+    r = rng_for(157)
+    ct1 = np.stack([uniform_poly(r, primes[:size_q], n) for _ in range(2)])
+    ct2 = np.stack([uniform_poly(r, primes[:size_q], n) for _ in range(2)])
+    want = {"bfv_multiply_behz": O.Behz(oc, plain_t).multiply(ct1, ct2),
+            "bfv_multiply_hps": O.Hps(oc, plain_t).multiply(ct1, ct2),
+            "bfv_multiply_hps_overq": O.HpsOverQ(oc, plain_t).multiply(ct1, ct2),
+            "bfv_multiply_hps_overq_leveled": O.HpsOverQ(oc, plain_t, size_q - 1).multiply(ct1, ct2)}
+    return name, plain_t, primes, size_q, n, ct1, ct2, want
+
+
+def _bfv_single(ctx, entry, size_q, a, b, dst):
+    if entry.endswith("_leveled"):
+        getattr(ctx, entry)(size_q - 1, a, b, dst)
+    else:
+        getattr(ctx, entry)(a, b, dst)
+
+
+@pytest.mark.parametrize("entry", BFV_SINGLE_ENTRIES)
+def test_bfv_multiply_refuses_dst_overlapping_an_input(entry, gpu):
+    """A dst that starts inside ct1's buffer is refused and nothing is written; the same call with a dst of its own matches the
+    oracle."""
+    import torch
+    import phantom_fhe_amd as P
+    name, plain_t, primes, size_q, n, ct1, ct2, want = _c1_pair_and_products()
+    ctx = _ctx(name, gpu)
+    ctx.set_plain_modulus(plain_t)
+    qn = size_q * n
+    buf = torch.zeros(qn + 3 * qn, dtype=torch.int64, device=gpu)      # [ct1 | ...]: dst starts at ct1's second polynomial
+    inp = buf[:2 * qn].view(2, size_q, n)
+    inp.copy_(P.to_device(ct1, gpu))
+    over = buf[qn:].view(3, size_q, n)
+    d2 = P.to_device(ct2, gpu)
+    with pytest.raises(ValueError) as e:
+        _bfv_single(ctx, entry, size_q, inp, d2, over)
+    assert "overlap" in str(e.value), str(e.value)
+    torch.cuda.synchronize()
+    assert np.array_equal(P.to_host(inp), ct1) and np.array_equal(P.to_host(d2), ct2), "a refused call wrote to an input"
+    assert not buf[2 * qn:].any(), "a refused call wrote to dst"
+    dst = P.to_device(np.zeros((3, size_q, n), dtype=np.uint64), gpu)
+    _bfv_single(ctx, entry, size_q, inp, d2, dst)
+    assert np.array_equal(P.to_host(dst), want[entry])
+
+
+@pytest.mark.parametrize("entry", BFV_SINGLE_ENTRIES)
+def test_bfv_multiply_strict_mode_names_the_operand(entry, gpu):
+    """Strict mode: a ct2 holding one word equal to its prime is refused under the entry's own name; with strict off the call
+    computes."""
+    import torch
+    import phantom_fhe_amd as P
+    name, plain_t, primes, size_q, n, ct1, ct2, want = _c1_pair_and_products()
+    ctx = _ctx(name, gpu)
+    ctx.set_plain_modulus(plain_t)
+    bad2 = ct2.copy()
+    bad2[1, 0, 5] = np.uint64(primes[0])
+    d1, d2, db2 = (P.to_device(x, gpu) for x in (ct1, ct2, bad2))
+    poison = torch.full((3, size_q, n), 7, dtype=torch.int64, device=gpu)
+    dst = poison.clone()
+    prev = P.set_strict(True)
+    try:
+        with pytest.raises(ValueError) as e:
+            _bfv_single(ctx, entry, size_q, d1, db2, dst)
+        assert "PHA_STRICT" in str(e.value) and f"{entry} ct2" in str(e.value) and "1 word" in str(e.value), str(e.value)
+        torch.cuda.synchronize()
+        assert torch.equal(dst, poison), "a refused call wrote something"
+        _bfv_single(ctx, entry, size_q, d1, d2, dst)                      # canonical operands pass
+        assert np.array_equal(P.to_host(dst), want[entry])
+        P.set_strict(False)
+        dst.copy_(poison)
+        _bfv_single(ctx, entry, size_q, d1, db2, dst)                     # strict off: the call computes
+        torch.cuda.synchronize()
+        assert not torch.equal(dst, poison)
+    finally:
+        P.set_strict(prev)
 
 
 @pytest.mark.parametrize("bits,m,n,k,batch", [(50, 256, 256, 256, 3), (50, 96, 40, 72, 2), (60, 128, 64, 100, 2), (36, 64, 32, 16, 1),
