@@ -27,10 +27,6 @@ __global__ __launch_bounds__(256) void stream_kernel(u32x4 *__restrict__ dst, co
     else dst[i] = v;
 }
 
-void need(const void *p) {
-    if (!p) throw std::invalid_argument("null device pointer");
-}
-
 }  // namespace
 
 extern "C" {

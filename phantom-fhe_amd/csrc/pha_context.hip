@@ -1037,7 +1037,7 @@ const uint32_t *Context::galois_table(uint32_t elt) {
     std::lock_guard<std::mutex> lk(mu);
     auto it = galois_tables.find(elt);
     if (it != galois_tables.end()) return it->second.p;
-    if (!(elt & 1) || elt >= 2 * n) throw std::invalid_argument("Galois element is not valid");
+    check_galois_elt(*this, elt);
     std::vector<uint32_t> tab(n);
     for (uint32_t i = (uint32_t)n; i < 2 * n; i++) {
         const uint32_t rev = h_brev(i, (int)log_n + 1);

@@ -410,10 +410,6 @@ static void launch_hoist_inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_m
 
 using namespace pha;
 
-static void need(const void *p) {
-    if (!p) throw std::invalid_argument("null device pointer");
-}
-
 // Core of the baby-step / giant-step entries: `blocks` row blocks that share the input ciphertext and every Galois key.  Block r
 // with weights w[r][i][j] gives out[r] = sum_i rot_{G_i}(sum_j w[r][i][j] (.) rot_{B_j}(ct)).  The fused baby-step kernel treats
 // the (block, giant step) pairs as one list of accumulators, so the baby keys, the gathered digits and the per-baby reductions are

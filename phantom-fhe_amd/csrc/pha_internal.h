@@ -410,10 +410,39 @@ struct ModupConvArgs {
 };
 bool modup_conv_strided(Context &c, u64 *digits, const LimbSel &sel, const NttExtra &x, const ModupConvArgs &m, hipStream_t s);
 
-// ---- key-switch building blocks of pha_rns.hip that pha_hoist.hip calls too ----------------------------------------------
+// ---- the hybrid key switch (pha_rns.hip) --------------------------------------------------------------------------------
+// ONE host driver, keyswitch(), stands behind the single, the batched and the composed entries (pha_keyswitch_inplace(_batched), the
+// unfused arm of pha_keyswitch_rescale(_batched), both key switches of pha_relinearize_rotate_batched): cx = mod-up + inner product of
+// c2 with the keys (modup_inner_prod()), then moddown_from_ntt over the 2 B polynomials into dst.  modup_inner_prod() is the one place
+// that chooses between the forms of the first half: ONE ciphertext takes the fused mod-up + inner product where the shape has one
+// (fusable_ip(); under ckks with the contiguous pass of the mod-down's inverse transform folded in), a batch takes the batched kernels,
+// whose inner product reads the digits' own limbs from c2 where own_in_place_ok() says so.  The fused key switch + rescale
+// (keyswitch_rescale()) calls modup_inner_prod() for its first half and has a second half of its own.  The building blocks below
+// are what pha_hoist.hip calls too.
+//
+// Scratch of a key switch of B ciphertexts at one level (eval_key_switch.cu:151,155), in words:
+//     tmp [B][2][Ql][N] | t_mod_up [B][beta][QlP][N] | cx [B][2][QlP][N]
+// tmp: the mod-up's coefficient-form c2 (one polynomial per ciphertext), then the mod-down's delta (two).  A caller that needs more
+// (the ct copy of the unfused key switch + rescale, ks | g1 of relinearize-rotate) appends it after words().
+struct KsScratch {
+    u64 *tmp, *t_mod_up, *cx;
+    static size_t words(size_t ql, size_t qlp, size_t beta, size_t n, size_t B) { return B * (2 * ql * n + beta * qlp * n + 2 * qlp * n); }
+    static size_t words(const Context &c, const Tool &t, size_t B) { return words(t.size_ql, t.size_qlp, t.beta, c.n, B); }
+    KsScratch(u64 *base, size_t ql, size_t qlp, size_t beta, size_t n, size_t B)
+        : tmp(base), t_mod_up(tmp + B * 2 * ql * n), cx(t_mod_up + B * beta * qlp * n) {}
+    KsScratch(u64 *base, const Context &c, const Tool &t, size_t B) : KsScratch(base, t.size_ql, t.size_qlp, t.beta, c.n, B) {}
+};
+
 bool ntt_domain_scheme(int scheme);   // ckks / bgv: true, bfv: false; throws on anything else
 void check_level(Context &c, size_t size_Ql, bool need_p);
 bool overlaps(const u64 *a, size_t na, const u64 *b, size_t nb);
+// argument checks shared by the entry points
+inline void need(const void *p) {
+    if (!p) throw std::invalid_argument("null device pointer");
+}
+inline void check_galois_elt(const Context &c, uint32_t elt) {
+    if (!(elt & 1) || elt >= 2 * c.n) throw std::invalid_argument("Galois element is not valid");
+}
 // DRNSTool::modup rns_bconv.cu:530-627.  All beta digits go through ONE base-conversion launch and ONE
 // forward-NTT launch pair (blockIdx.z = digit; digit z skips its own limbs, ntt_modup.cu:422).
 // `batch` ciphertexts at once: cks / t_cks are [batch][Ql][N], dst is [batch][beta][QlP][N].

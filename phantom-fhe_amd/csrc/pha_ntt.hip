@@ -1520,10 +1520,6 @@ bool modup_conv_strided(Context &c, u64 *digits, const LimbSel &sel, const NttEx
 
 using namespace pha;
 
-static void need(const void *p) {
-    if (!p) throw std::invalid_argument("null device pointer");
-}
-
 extern "C" {
 
 int pha_nwt_2d_radix8_forward_inplace(pha_context_t ctx, uint64_t *inout, size_t cms, size_t start, void *stream) {

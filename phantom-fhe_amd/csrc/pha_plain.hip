@@ -8,9 +8,6 @@
 
 using namespace pha;
 
-static void need(const void *p) {
-    if (!p) throw std::invalid_argument("null device pointer");
-}
 static void rc(int status) {   // an inner ABI call failed: re-raise with its own category
     if (status == 0) return;
     const std::string what = pha_last_error();

@@ -433,10 +433,6 @@ void launch_add(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, si
 
 using namespace pha;
 
-static void need(const void *p) {
-    if (!p) throw std::invalid_argument("null device pointer");
-}
-
 // ---- summed tensor product and the inner-product entries (extension) ------------------------------------------------------------
 static bool ranges_overlap(const u64 *a, size_t na, const u64 *b, size_t nb) { return a < b + nb && b < a + na; }
 

@@ -104,10 +104,6 @@ static void launch_x(Context &c, XArgs k, size_t limbs, size_t mod_start, hipStr
 
 using namespace pha;
 
-static void need(const void *p) {
-    if (!p) throw std::invalid_argument("null device pointer");
-}
-
 extern "C" {
 
 int pha_add_std_cipher(pha_context_t ctx, const uint64_t *cipher1, const uint64_t *cipher2, uint64_t *result, size_t cms,

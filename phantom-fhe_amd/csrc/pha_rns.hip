@@ -884,36 +884,10 @@ static void set_last_limb_fix(Context &c, Tool &t, const u64 *fix_ct, Args &k) {
     k.fix_ct_stride = (size_t)t.size_ql * c.n;
 }
 
-// mod-up + inner product of ONE ciphertext: the fused form where the shape has one, else the two steps.  fix_ct as in inner_prod.
-static void inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const u64 *const *rlk, hipStream_t s, uint32_t batch = 1,
-                       const u64 *fix_ct = nullptr, const u64 *own = nullptr, size_t own_stride = 0);
-// fold_inverse (ckks forms): the fused kernel also runs the contiguous pass of the mod-down's inverse transform on the special limbs
-// (and on the last data limb when fix_ct is given, the fused rescale); returns true when it did -- the caller then launches that
-// inverse with NttExtra::second_pass_only.
-static bool modup_inner_prod(Context &c, Tool &t, u64 *cx, u64 *t_mod_up, const u64 *c2, const u64 *const *rlk, int scheme, u64 *tmp,
-                             hipStream_t s, const u64 *fix_ct = nullptr, bool fold_inverse = false) {
-    if (!fusable_ip(c, t)) {
-        modup(c, t, t_mod_up, c2, scheme, tmp, s);
-        inner_prod(c, t, cx, t_mod_up, rlk, s, 1, fix_ct);
-        return false;
-    }
-    ModupIpArgs ip{};
-    ip.cx = cx; ip.evks = rlk; ip.qlp_n = (size_t)t.size_qlp * c.n; ip.qp_n = (size_t)c.size_qp * c.n;
-    set_last_limb_fix(c, t, fix_ct, ip);
-    if (fold_inverse) {
-        ip.inv_from = t.size_ql;
-        ip.inv_lead = fix_ct ? t.size_ql - 1 : 0xffffffffu;
-        ip.itw = c.d_itw.p;
-        ip.itwf = c.d_itwf.p;
-    }
-    modup(c, t, t_mod_up, c2, scheme, tmp, s, 1, 0, &ip);
-    return ip.inv_from != 0xffffffffu;
-}
-
 // phantom::key_switch_inner_prod eval_key_switch.cu:71-92
 // fix_ct != null (pha_keyswitch_rescale): cx's last data limb receives ct_last + cx_last * P^-1 (see InnerArgs)
-static void inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const u64 *const *rlk, hipStream_t s,
-                       uint32_t batch, const u64 *fix_ct, const u64 *own, size_t own_stride) {
+static void inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const u64 *const *rlk, hipStream_t s, uint32_t batch = 1,
+                       const u64 *fix_ct = nullptr, const u64 *own = nullptr, size_t own_stride = 0) {
     InnerArgs k{};
     k.cx = cx; k.t_mod_up = t_mod_up; k.evks = rlk; k.mod = c.d_mod.p; k.qlp_prime = t.d_qlp_prime.p;
     k.n = (uint32_t)c.n; k.beta = t.beta; k.qlp_n = (size_t)t.size_qlp * c.n; k.qp_n = (size_t)c.size_qp * c.n;
@@ -934,6 +908,34 @@ static void inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const 
         k.cx += 2 * k.qlp_n;
         if (k.fix_ct) k.fix_ct += 2 * k.fix_ct_stride;
     }
+}
+
+// mod-up + inner product of B ciphertexts, c2 at c2 + b * c2_stride: k.cx from c2 (pha_internal.h: the hybrid key switch).  ONE
+// ciphertext takes the fused form where the shape has one, everything else the two steps; a batch of an NTT-form scheme leaves the
+// digits' own limbs where they are (modup's own_in_place) and its inner product reads them from c2 (InnerArgs::own).  fix_ct as in
+// inner_prod.
+// fold_inverse (ckks forms): the fused kernel also runs the contiguous pass of the mod-down's inverse transform on the special limbs
+// (and on the last data limb when fix_ct is given, the fused rescale); returns true when it did -- the caller then launches that
+// inverse with NttExtra::second_pass_only.
+static bool modup_inner_prod(Context &c, Tool &t, const KsScratch &k, const u64 *c2, size_t c2_stride, const u64 *const *keys, int scheme,
+                             uint32_t B, hipStream_t s, const u64 *fix_ct = nullptr, bool fold_inverse = false) {
+    if (B == 1 && fusable_ip(c, t)) {
+        ModupIpArgs ip{};
+        ip.cx = k.cx; ip.evks = keys; ip.qlp_n = (size_t)t.size_qlp * c.n; ip.qp_n = (size_t)c.size_qp * c.n;
+        set_last_limb_fix(c, t, fix_ct, ip);
+        if (fold_inverse) {
+            ip.inv_from = t.size_ql;
+            ip.inv_lead = fix_ct ? t.size_ql - 1 : 0xffffffffu;
+            ip.itw = c.d_itw.p;
+            ip.itwf = c.d_itwf.p;
+        }
+        modup(c, t, k.t_mod_up, c2, scheme, k.tmp, s, 1, 0, &ip);
+        return ip.inv_from != 0xffffffffu;
+    }
+    const bool in_place = own_in_place_ok(t, scheme, B);
+    modup(c, t, k.t_mod_up, c2, scheme, k.tmp, s, B, c2_stride, nullptr, in_place);
+    inner_prod(c, t, k.cx, k.t_mod_up, keys, s, B, fix_ct, in_place ? c2 : nullptr, c2_stride);
+    return false;
 }
 
 // (described with its declaration in pha_internal.h)
@@ -1039,6 +1041,14 @@ void moddown_from_ntt(Context &c, Tool &t, u64 *ct, size_t ct_stride, u64 *cx, s
     }
 }
 
+// keyswitch_inplace eval_key_switch.cu:95-182 on B ciphertexts: dst [B][2][Ql][N] (+)= keyswitch(c2 + b * c2_stride); accumulate adds
+// to what dst holds (ct += ..., the add fused into the mod-down's epilogue).  dst and k.cx are uniformly strided over the 2 B polynomials.
+static void keyswitch(Context &c, Tool &t, const KsScratch &k, u64 *dst, bool accumulate, const u64 *c2, size_t c2_stride,
+                      const u64 *const *keys, int scheme, uint32_t B, hipStream_t s) {
+    const bool folded = modup_inner_prod(c, t, k, c2, c2_stride, keys, scheme, B, s, nullptr, scheme == PHA_SCHEME_CKKS && B == 1);
+    moddown_from_ntt(c, t, dst, (size_t)t.size_ql * c.n, k.cx, (size_t)t.size_qlp * c.n, 2 * B, scheme, accumulate, k.tmp, s, folded);
+}
+
 // DRNSTool::divide_and_round_q_last_ntt rns.cu:1160-1184 on `polys` polynomials src [polys][Ql][N] -> dst [polys][Ql-1][N]
 static void rescale_ntt(Context &c, Tool &t, u64 *src, uint32_t polys, u64 *dst, hipStream_t s) {
     const size_t n = c.n, size_Ql = t.size_ql, nl = size_Ql - 1;
@@ -1067,24 +1077,18 @@ static void rescale_ntt(Context &c, Tool &t, u64 *src, uint32_t polys, u64 *dst,
 // divide_and_round_q_last_ntt rns.cu:1160-1184 bit for bit): dst [B][2][Ql-1][N] = rescale(ct + keyswitch(c2)).
 // Against the two calls it drops the mod-down's forward transform over 2 x Ql limbs and the rescale's separate last-limb inverse
 // (their work rides on one inverse over the P limbs + the last data limb and ONE forward over 2 x (Ql - 1) limbs), and ct is
-// never written.  scratch `base` as laid out by the callers.
+// never written.
 static bool keyswitch_rescale_fusable(const Tool &t) {
     // bconv_rescale_kernel hard-codes the 16-row padding and the 30 / 30 cuts of converter kind 1 (Montgomery entries)
     return t.alpha > 1 && t.alpha <= (uint32_t)kBcRowPad && t.split_ok && t.p_to_ql_pinv.split_kind == 1 && t.p_to_ql_pinv.mont &&
            t.p_to_ql_pinv.row_pad == (uint32_t)kBcRowPad && t.size_ql >= 2;
 }
 static void keyswitch_rescale(Context &c, Tool &t, const u64 *ct, const u64 *c2, const u64 *const *rlk, u64 *dst, uint32_t B,
-                              u64 *base, hipStream_t s) {
+                              const KsScratch &k, hipStream_t s) {
     const size_t n = c.n, ql = t.size_ql, ql_n = ql * n, qlp_n = (size_t)t.size_qlp * n, nl = ql - 1;
-    u64 *tmp = base, *t_mod_up = base + B * 2 * ql_n, *cx = t_mod_up + B * (size_t)t.beta * qlp_n;
-    bool folded = false;   // the inverse transform's contiguous pass already ran inside the fused mod-up
-    if (B == 1) {
-        folded = modup_inner_prod(c, t, cx, t_mod_up, c2, rlk, PHA_SCHEME_CKKS, tmp, s, ct, true);   // cx_last <- ct_last + cx_last * P^-1
-    } else {
-        const bool in_place = own_in_place_ok(t, PHA_SCHEME_CKKS, B);   // the batched inner product reads the digits' own limbs from c2
-        modup(c, t, t_mod_up, c2, PHA_SCHEME_CKKS, tmp, s, B, 0, nullptr, in_place);
-        inner_prod(c, t, cx, t_mod_up, rlk, s, B, ct, in_place ? c2 : nullptr, ql_n);
-    }
+    u64 *tmp = k.tmp, *cx = k.cx;
+    // cx_last <- ct_last + cx_last * P^-1; folded: the inverse transform's contiguous pass already ran inside the fused mod-up
+    const bool folded = modup_inner_prod(c, t, k, c2, ql_n, rlk, PHA_SCHEME_CKKS, B, s, ct, B == 1);
     {   // coefficient form of the P limbs (x phat_i^-1, bconv phase 1) and of the last data limb, both polynomials, one launch pair
         NttExtra xb;
         xb.batch = 2 * B;
@@ -1139,10 +1143,6 @@ bool overlaps(const u64 *a, size_t na, const u64 *b, size_t nb) { return a < b +
 }  // namespace pha
 
 using namespace pha;
-
-static void need(const void *p) {
-    if (!p) throw std::invalid_argument("null device pointer");
-}
 
 extern "C" {
 
@@ -1215,25 +1215,16 @@ int pha_moddown(pha_context_t ctx, size_t size_Ql, uint64_t *ct_i, uint64_t *cx_
     PHA_API_END
 }
 
-int pha_keyswitch_inplace(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const uint64_t *c2,
-                          const uint64_t *const *rlk, int scheme, void *stream) {
-    PHA_CTX_BEGIN(ctx)
-    need(ct); need(c2); need(rlk);
-    Context &c = ctx->c;
-    check_level(c, size_Ql, true);
-    Tool &t = c.tool((uint32_t)size_Ql);
-    hipStream_t s = as_stream(stream);
-    strict_operand(c, "keyswitch ct", ct, rows_plain(0, size_Ql), 2, size_Ql * c.n, s);
-    strict_operand(c, "keyswitch c2", c2, rows_plain(0, size_Ql), 1, 0, s);
-    strict_keys(c, "keyswitch key", rlk, t.beta, (uint32_t)size_Ql, s);
-    const size_t n = c.n, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n;
-    // scratch: t_cks / delta [2][Ql][N] | t_mod_up [beta][QlP][N] | cx [2][QlP][N]  (eval_key_switch.cu:151,155)
-    u64 *base = c.scratch(stream, 2 * ql_n + (size_t)t.beta * qlp_n + 2 * qlp_n);
-    u64 *tmp = base, *t_mod_up = base + 2 * ql_n, *cx = t_mod_up + (size_t)t.beta * qlp_n;
-    const bool folded = modup_inner_prod(c, t, cx, t_mod_up, c2, rlk, scheme, tmp, s, nullptr, scheme == PHA_SCHEME_CKKS);
-    // both polynomials at once; ct += moddown(cx) with the add fused into the NTT epilogue
-    moddown_from_ntt(c, t, ct, ql_n, cx, qlp_n, 2, scheme, true, tmp, s, folded);
-    PHA_API_END
+// the batch limits of the batched key-switch entries: blockIdx.z carries beta * batch digit polynomials and 2 * batch polynomials
+static void check_ks_batch(const Tool &t, size_t batch) {
+    if (batch > 1024 || (size_t)t.beta * batch > 65535 || 2 * batch > 65535) throw std::invalid_argument("batch out of range");
+}
+// strict mode: the operands of a key switch of B ciphertexts, ct [B][2][Ql][N], c2 [B][Ql][N] and the keys
+static void strict_ks_operands(Context &c, Tool &t, const u64 *ct, const u64 *c2, const u64 *const *keys, uint32_t B, hipStream_t s) {
+    const size_t ql_n = (size_t)t.size_ql * c.n;
+    strict_operand(c, "keyswitch ct", ct, rows_plain(0, t.size_ql), 2 * B, ql_n, s);
+    strict_operand(c, "keyswitch c2", c2, rows_plain(0, t.size_ql), B, ql_n, s);
+    strict_keys(c, "keyswitch key", keys, t.beta, t.size_ql, s);
 }
 
 int pha_keyswitch_inplace_batched(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const uint64_t *c2, size_t batch,
@@ -1241,27 +1232,21 @@ int pha_keyswitch_inplace_batched(pha_context_t ctx, size_t size_Ql, uint64_t *c
     PHA_CTX_BEGIN(ctx)
     need(ct); need(c2); need(rlk);
     if (batch == 0) return 0;
-    if (batch > 1024) throw std::invalid_argument("batch out of range");
     Context &c = ctx->c;
     check_level(c, size_Ql, true);
     Tool &t = c.tool((uint32_t)size_Ql);
-    if ((size_t)t.beta * batch > 65535 || 2 * batch > 65535) throw std::invalid_argument("batch out of range");
+    check_ks_batch(t, batch);
     hipStream_t s = as_stream(stream);
     const uint32_t B = (uint32_t)batch;
-    strict_operand(c, "keyswitch ct", ct, rows_plain(0, size_Ql), 2 * B, size_Ql * c.n, s);
-    strict_operand(c, "keyswitch c2", c2, rows_plain(0, size_Ql), B, size_Ql * c.n, s);
-    strict_keys(c, "keyswitch key", rlk, t.beta, (uint32_t)size_Ql, s);
-    const size_t n = c.n, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n;
-    // scratch: t_cks / delta [B][2][Ql][N] | t_mod_up [B][beta][QlP][N] | cx [B][2][QlP][N]
-    u64 *base = c.scratch(stream, B * (2 * ql_n + (size_t)t.beta * qlp_n + 2 * qlp_n));
-    u64 *tmp = base, *t_mod_up = base + B * 2 * ql_n, *cx = t_mod_up + B * (size_t)t.beta * qlp_n;
-    // (NTT-form schemes, B > 1: the batched inner product reads the digits' own limbs from c2, the mod-up does not copy them)
-    const bool in_place = own_in_place_ok(t, scheme, B);
-    modup(c, t, t_mod_up, c2, scheme, tmp, s, B, 0, nullptr, in_place);
-    inner_prod(c, t, cx, t_mod_up, rlk, s, B, nullptr, in_place ? c2 : nullptr, ql_n);
-    // 2B polynomials: ct [B][2][Ql][N] and cx [B][2][QlP][N] are uniformly strided
-    moddown_from_ntt(c, t, ct, ql_n, cx, qlp_n, 2 * B, scheme, true, tmp, s);
+    strict_ks_operands(c, t, ct, c2, rlk, B, s);
+    const KsScratch k(c.scratch(stream, KsScratch::words(c, t, B)), c, t, B);
+    keyswitch(c, t, k, ct, true, c2, size_Ql * c.n, rlk, scheme, B, s);
     PHA_API_END
+}
+
+int pha_keyswitch_inplace(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const uint64_t *c2,
+                          const uint64_t *const *rlk, int scheme, void *stream) {
+    return pha_keyswitch_inplace_batched(ctx, size_Ql, ct, c2, 1, rlk, scheme, stream);
 }
 
 int pha_keyswitch_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, const uint64_t *c2, size_t batch,
@@ -1269,32 +1254,24 @@ int pha_keyswitch_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint6
     PHA_CTX_BEGIN(ctx)
     need(ct); need(c2); need(rlk); need(dst);
     if (batch == 0) return 0;
-    if (batch > 1024) throw std::invalid_argument("batch out of range");
     Context &c = ctx->c;
     check_level(c, size_Ql, true);
     if (size_Ql < 2) throw std::invalid_argument("cannot rescale the last remaining modulus");
     Tool &t = c.tool((uint32_t)size_Ql);
-    if ((size_t)t.beta * batch > 65535 || 2 * batch > 65535) throw std::invalid_argument("batch out of range");
+    check_ks_batch(t, batch);
     hipStream_t s = as_stream(stream);
     const uint32_t B = (uint32_t)batch;
-    strict_operand(c, "keyswitch ct", ct, rows_plain(0, size_Ql), 2 * B, size_Ql * c.n, s);
-    strict_operand(c, "keyswitch c2", c2, rows_plain(0, size_Ql), B, size_Ql * c.n, s);
-    strict_keys(c, "keyswitch key", rlk, t.beta, (uint32_t)size_Ql, s);
-    const size_t n = c.n, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n;
+    strict_ks_operands(c, t, ct, c2, rlk, B, s);
+    const size_t n = c.n, ql_n = size_Ql * n;
     if (overlaps(dst, B * 2 * (size_Ql - 1) * n, ct, B * 2 * ql_n) || overlaps(dst, B * 2 * (size_Ql - 1) * n, c2, B * ql_n))
         throw std::invalid_argument("dst must not overlap ct or c2");
-    // scratch: t_cks / v [B][2][Ql][N] | t_mod_up [B][beta][QlP][N] | cx [B][2][QlP][N] (| ct copy [B][2][Ql][N] for the fallback)
-    const size_t words = B * (2 * ql_n + (size_t)t.beta * qlp_n + 2 * qlp_n);
+    const size_t words = KsScratch::words(c, t, B);
     if (keyswitch_rescale_fusable(t)) {
-        keyswitch_rescale(c, t, ct, c2, rlk, dst, B, c.scratch(stream, words), s);
-    } else {   // alpha = 1, wide primes, wide P: the two reference steps on a copy of ct
-        u64 *base = c.scratch(stream, words + B * 2 * ql_n);
-        u64 *tmp = base, *t_mod_up = base + B * 2 * ql_n, *cx = t_mod_up + B * (size_t)t.beta * qlp_n, *work = base + words;
+        keyswitch_rescale(c, t, ct, c2, rlk, dst, B, KsScratch(c.scratch(stream, words), c, t, B), s);
+    } else {   // alpha = 1, wide primes, wide P: the two reference steps on a copy of ct [B][2][Ql][N], kept after the key switch's scratch
+        u64 *base = c.scratch(stream, words + B * 2 * ql_n), *work = base + words;
         PHA_HIP(hipMemcpyAsync(work, ct, B * 2 * ql_n * sizeof(u64), hipMemcpyDeviceToDevice, s));
-        const bool in_place = own_in_place_ok(t, PHA_SCHEME_CKKS, B);
-        modup(c, t, t_mod_up, c2, PHA_SCHEME_CKKS, tmp, s, B, 0, nullptr, in_place);
-        inner_prod(c, t, cx, t_mod_up, rlk, s, B, nullptr, in_place ? c2 : nullptr, ql_n);
-        moddown_from_ntt(c, t, work, ql_n, cx, qlp_n, 2 * B, PHA_SCHEME_CKKS, true, tmp, s);
+        keyswitch(c, t, KsScratch(base, c, t, B), work, true, c2, ql_n, rlk, PHA_SCHEME_CKKS, B, s);
         rescale_ntt(c, t, work, 2 * B, dst, s);
     }
     PHA_API_END
@@ -1318,7 +1295,7 @@ int pha_relinearize_rotate_batched(pha_context_t ctx, size_t size_Ql, const uint
     if (batch == 0) return 0;
     Context &c = ctx->c;
     check_level(c, size_Ql, true);
-    if (!(galois_elt & 1) || galois_elt >= 2 * c.n) throw std::invalid_argument("Galois element is not valid");
+    check_galois_elt(c, galois_elt);
     Tool &t = c.tool((uint32_t)size_Ql);
     const bool ntt_dom = ntt_domain_scheme(scheme);
     if (scheme == PHA_SCHEME_BGV && !t.bgv_ready) throw std::invalid_argument("bgv needs a plain modulus (pha_context_set_plain_modulus)");
@@ -1337,27 +1314,21 @@ int pha_relinearize_rotate_batched(pha_context_t ctx, size_t size_Ql, const uint
     if (two_lanes) chunk /= 2;
     const uint32_t *tab = ntt_dom ? c.galois_table(galois_elt) : nullptr;
     const size_t C = chunk;
-    const size_t words = C * (2 * ql_n + (size_t)t.beta * qlp_n + 2 * qlp_n + 3 * ql_n);
-    // one set of B ciphertexts from b0 on stream ls, scratch base: tmp [C][2][Ql][N] | t_mod_up [C][beta][QlP][N] | cx [C][2][QlP][N] |
-    // ks [C][2][Ql][N] | g1 [C][Ql][N]
+    const size_t ks_words = KsScratch::words(c, t, C), words = ks_words + C * 3 * ql_n;
+    // one set of B <= C ciphertexts from b0 on stream ls, scratch base: the key switches' scratch for C | ks [C][2][Ql][N] | g1 [C][Ql][N]
     auto one_set = [&](hipStream_t ls, u64 *base, size_t b0) {
-        u64 *tmp = base, *t_mod_up = base + C * 2 * ql_n, *cx = t_mod_up + C * (size_t)t.beta * qlp_n, *ks = cx + C * 2 * qlp_n,
-            *g1 = ks + C * 2 * ql_n;
+        const KsScratch k(base, c, t, C);
+        u64 *ks = base + ks_words, *g1 = ks + C * 2 * ql_n;
         const uint32_t B = (uint32_t)std::min(C, batch - b0);
         const u64 *in = ct3 + b0 * 3 * ql_n;
         u64 *o = out + b0 * 2 * ql_n;
         // relinearize: ks = keyswitch(c2), c2 read where it lies (every third polynomial)
-        const bool in_place = own_in_place_ok(t, scheme, B);   // (CKKS / BGV; the BFV mod-up transforms its own limbs in the digit buffers)
-        modup(c, t, t_mod_up, in + 2 * ql_n, scheme, tmp, ls, B, 3 * ql_n, nullptr, in_place);
-        inner_prod(c, t, cx, t_mod_up, rlk, ls, B, nullptr, in_place ? in + 2 * ql_n : nullptr, 3 * ql_n);
-        moddown_from_ntt(c, t, ks, ql_n, cx, qlp_n, 2 * B, scheme, false, tmp, ls);
+        keyswitch(c, t, k, ks, false, in + 2 * ql_n, 3 * ql_n, rlk, scheme, B, ls);
         // rotate: (galois(c0 + ks0), 0) and galois(c1 + ks1) in the layout of the second key switch (apply_galois_inplace)
         hipLaunchKernelGGL(galois_split_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql, 2 * B), dim3(256), 0, ls, o, g1, ks, tab,
                            c.d_mod.p, tab ? galois_elt : inv_mod_2n(galois_elt, n), (uint32_t)n, (uint32_t)size_Ql, in, 3u);
         check_launch();
-        modup(c, t, t_mod_up, g1, scheme, tmp, ls, B, 0, nullptr, in_place);
-        inner_prod(c, t, cx, t_mod_up, glk, ls, B, nullptr, in_place ? g1 : nullptr, ql_n);
-        moddown_from_ntt(c, t, o, ql_n, cx, qlp_n, 2 * B, scheme, true, tmp, ls);
+        keyswitch(c, t, k, o, true, g1, ql_n, glk, scheme, B, ls);
     };
     if (!two_lanes) {
         u64 *base = c.scratch(stream, words);
@@ -1499,7 +1470,7 @@ int pha_apply_galois_batched(pha_context_t ctx, const uint64_t *src, uint64_t *d
     need(src); need(dst);
     if (src == dst) throw std::invalid_argument("apply_galois cannot run in place");
     Context &c = ctx->c;
-    if (!(galois_elt & 1) || galois_elt >= 2 * c.n) throw std::invalid_argument("Galois element is not valid");
+    check_galois_elt(c, galois_elt);
     if (cms > c.size_qp) throw std::invalid_argument("modulus index out of range");
     if (polys == 0 || cms == 0) return 0;
     if (polys > 65535) throw std::invalid_argument("batch out of range");
@@ -1523,7 +1494,7 @@ int pha_apply_galois_for_keyswitch(pha_context_t ctx, const uint64_t *src, uint6
     need(src); need(dst_ct); need(dst_c2);
     if (src == dst_ct || src == dst_c2) throw std::invalid_argument("apply_galois cannot run in place");
     Context &c = ctx->c;
-    if (!(galois_elt & 1) || galois_elt >= 2 * c.n) throw std::invalid_argument("Galois element is not valid");
+    check_galois_elt(c, galois_elt);
     if (size_Ql == 0 || size_Ql > c.size_q) throw std::invalid_argument("size_Ql out of range");
     if (batch == 0) return 0;
     if (2 * batch > 65535) throw std::invalid_argument("batch out of range");
@@ -1541,7 +1512,7 @@ int pha_apply_galois(pha_context_t ctx, const uint64_t *src, uint64_t *dst, uint
     need(src); need(dst);
     if (src == dst) throw std::invalid_argument("apply_galois cannot run in place");
     Context &c = ctx->c;
-    if (!(galois_elt & 1) || galois_elt >= 2 * c.n) throw std::invalid_argument("Galois element is not valid");
+    check_galois_elt(c, galois_elt);
     if (mod_start + cms > c.size_qp) throw std::invalid_argument("modulus index out of range");
     launch_galois_coeff(c, dst, src, galois_elt, cms, mod_start, 1, as_stream(stream));
     PHA_API_END

@@ -387,6 +387,34 @@ def test_relinearize_rotate_a12_sets(batch, chunk, gpu):
     _release()
 
 
+# a last set of ONE ciphertext (3 = 2 + 1): both of its key switches take what the single entry takes at N = 2^14, the fused mod-up +
+# inner product -- under ckks with the folded inverse pass (the first one stores, the second accumulates), under bfv from
+# coefficient-form input; c2 of the first one is read where it lies in ct3
+@pytest.mark.parametrize("name,scheme", [("hyb14_a4", "ckks"), ("hyb14_a2", "bfv")])
+def test_relinearize_rotate_last_set_of_one(name, scheme, gpu):
+    from phantom_fhe_amd import workloads as W
+    scheme, ql, batch, elt = SCHEMES[scheme], 8, 3, 5
+    P, oc, ctx, log_n, primes, size_p, size_q = _setup(name, scheme, gpu)
+    n = 1 << log_n
+    r = rng_for(8800 + size_p)
+    dnum = size_q // size_p
+    evk, gk = _keys(r, primes, n, dnum), _keys(r, primes, n, dnum)
+    rlk, d_gk = P.PhantomRelinKey.from_numpy(evk, gpu), P.PhantomRelinKey.from_numpy(gk, gpu)
+    tool = _tool(oc, ql, scheme)
+    assert tool.beta == dnum <= 4
+    ct3 = np.stack([np.stack([uniform_poly(r, primes[:ql], n) for _ in range(3)]) for _ in range(batch)])
+    ref = _relin_rotate_reference(oc, tool, log_n, ct3, [evk[i] for i in range(tool.beta)], [gk[i] for i in range(tool.beta)], elt, scheme)
+    d3 = P.to_device(ct3, gpu)
+    got = P.to_host(W.relinearize_rotate_batch(ctx, ql, d3, rlk, d_gk, elt, scheme, chunk=2))
+    for b in range(batch):
+        _check(got[b], ref[b], f"relinearize_rotate_batch {name} B={batch} chunk=2", ql, size_p, lead=(b,))
+    whole = P.to_host(W.relinearize_rotate_batch(ctx, ql, d3, rlk, d_gk, elt, scheme, chunk=batch))
+    _check(got, whole, f"relinearize_rotate_batch {name} B={batch} chunk=2 vs chunk={batch}", ql, size_p)
+    assert np.array_equal(P.to_host(d3), ct3), "relinearize_rotate_batch wrote to ct3"
+    del ctx, rlk, d_gk, d3
+    _release()
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # D: the shapes bench.py times
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -326,7 +326,10 @@ KSR_CASES = [("hyb12_a2", 6, 1), ("hyb12_a2", 5, 2), ("hyb12_a2", 2, 1), ("hyb13
              # final transform's strided pass too (the kernel's FORM 1 / 2), and the inner product reads the digits' own limbs from c2:
              # the top level runs the 15-input instantiations of all three forms in the PRODUCT library
              ("c3_ckks16", 45, 8), ("c3_ckks16", 31, 8),
-             ("hyb16_a12", 24, 8)]    # alpha = 12: the 16-input instantiation, 8 x 2 digits = 1024 workgroups in the product library
+             ("hyb16_a12", 24, 8),    # alpha = 12: the 16-input instantiation, 8 x 2 digits = 1024 workgroups in the product library
+             # 61-bit special primes at N = 2^14: the two reference steps on a copy of ct (no fused rescale), whose key switch of ONE
+             # ciphertext is the fused mod-up + inner product with the folded inverse pass; (hyb14_a4, 8, 1) above is the fused rescale's
+             ("p61_14_a2", 6, 1)]
 
 
 @pytest.mark.parametrize("name,ql,batch", KSR_CASES)
@@ -543,7 +546,12 @@ def test_extreme_residues_and_empty_calls(gpu):
                                                   ("c3_ckks16", O.CKKS, 45, 5),    # 10 polynomials at N = 2^16: the r04 batched contiguous pass, mod-down epilogue
                                                   # r05: alpha = 12 at N = 2^16 -- in the experiments library (tests/test_gpu_ntt_variants.py) these take
                                                   # modup_conv_s1_kernel<., 16>: full digits, a one-limb last digit, the BGV branch
-                                                  ("hyb16_a12", O.CKKS, 24, 2), ("hyb16_a12", O.CKKS, 13, 2), ("hyb16_a12", O.BGV, 24, 2)])
+                                                  ("hyb16_a12", O.CKKS, 24, 2), ("hyb16_a12", O.CKKS, 13, 2), ("hyb16_a12", O.BGV, 24, 2),
+                                                  # a batch of ONE takes what the single entry takes: the fused mod-up + inner product
+                                                  # with the folded inverse pass (ckks), from coefficient-form input (bfv), without the
+                                                  # fold (bgv); the two steps at beta 6 and at N = 2^12, which have no fused form
+                                                  ("hyb14_a4", O.CKKS, 8, 1), ("hyb14_a2", O.BFV, 8, 1), ("hyb14_a4", O.BGV, 8, 1),
+                                                  ("hyb14_b6", O.CKKS, 12, 1), ("hyb12_a2", O.CKKS, 6, 1)])
 def test_batched_keyswitch_and_tensor(name, scheme, ql, batch, gpu):
     """pha_keyswitch_inplace_batched / pha_tensor_prod_2x2_batched: every ciphertext of the batch must equal the
     single-ciphertext result (oracle), including short last digits and the alpha = 1 path."""

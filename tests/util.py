@@ -24,6 +24,7 @@ CONFIGS = {
     "wide_p33": (12, [36] * 6 + [37] * 33, 33),            # special base wider than the register-resident converters (alpha > 32)
     "wide_p20": (12, [45] * 24 + [46] * 20, 20),           # 17..32 special primes: the 30 / 31-bit split converter (two digits: 20 + 4 limbs)
     "p61_a2": (12, [50] * 6 + [61, 61], 2),               # 61-bit special primes: 30 / 31 cuts in mod-up, 31 / 30 in mod-down
+    "p61_14_a2": (14, [50] * 6 + [61, 61], 2),            # the same at N = 2^14 (beta 3): no fused key switch + rescale (wide primes), but ONE ciphertext has the fused mod-up + inner product
     "bfv13_50": (13, [50] * 4 + [60, 60], 2),             # uniform data primes: what the HPS variant of BFV multiply needs
     # more than four key-switch digits with alpha > 1 (tests/test_gpu_batched_dispatch.py): the unfused mod-up + inner product of one
     # ciphertext, the per-ciphertext inner product loop of a batch, the mod-up that copies the digits' own limbs
