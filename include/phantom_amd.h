@@ -56,7 +56,8 @@ const char *pha_last_error(void);
  * pha_set_strict(on): strict mode on / off for the process, returns the previous state.  Default: on iff PHA_STRICT=1 was in the
  *   environment when the library was first used.  In strict mode the dyadic, tensor, mod-up / inner-product / mod-down, key-switch,
  *   hoisting and BFV multiply entries check ct / c2 / t_mod_up / keys / weights / ct1 and ct2 before they compute (one
- *   synchronising pass per operand) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
+ *   synchronising pass per operand; among them pha_keyswitch_mod_switch, pha_keyswitch_mod_switch_batched and
+ *   pha_inner_product_relin_mod_switch_batched) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
 int pha_check_canonical(pha_context_t ctx, const uint64_t *data, size_t coeff_modulus_size, size_t start_modulus_idx,
                         size_t size_P_tail, size_t polys, size_t poly_stride, uint64_t *bad_words, void *stream);
 int pha_check_canonical_keys(pha_context_t ctx, size_t size_Ql, const uint64_t *const *keys, size_t n_keys, uint64_t *bad_words,
@@ -320,6 +321,20 @@ int pha_keyswitch_rescale(pha_context_t ctx, size_t size_Ql, const uint64_t *ct,
 /* the same for `batch` ciphertexts ct [batch][2][Ql][N], c2 [batch][Ql][N] -> dst [batch][2][Ql-1][N] against one key */
 int pha_keyswitch_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, const uint64_t *c2, size_t batch,
                                   const uint64_t *const *rlk, uint64_t *dst, void *stream);
+/* Build-defined fusion (no reference launcher), the bgv counterpart: key switch followed by mod_switch_to_next, i.e. the
+ * relinearize -> mod_switch_to_next pair of src/evaluate.cu:1028-1077,1376-1427 (keyswitch_inplace eval_key_switch.cu:95-182 then
+ * mod_t_and_divide_q_last_ntt rns.cu:1186-1236) as ONE call: dst [2][Ql-1][N] = mod_switch(ct + keyswitch(c2)), bit-identical to
+ * pha_keyswitch_inplace(..., PHA_SCHEME_BGV) followed by pha_mod_t_and_divide_q_last_ntt(..., 2, ...) for every tool shape.  ct
+ * [2][Ql][N] (NTT form) and c2 [Ql][N] are only read; dst must not overlap them.  Both steps divide in coefficient form, so the
+ * forward transform of 2 x Ql limbs, the add to ct and the inverse transform of the same limbs between them cancel: 4 Ql + 2 alpha - 2
+ * limb transforms after the key inner product instead of 8 Ql + 2 alpha - 2, and no copy of ct.  Needs
+ * pha_context_set_plain_modulus and size_Ql >= 2.  The caller multiplies the correction factor by q_last^-1 mod t, as after
+ * mod_switch_to_next. */
+int pha_keyswitch_mod_switch(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, const uint64_t *c2,
+                             const uint64_t *const *rlk, uint64_t *dst, void *stream);
+/* the same for `batch` ciphertexts ct [batch][2][Ql][N], c2 [batch][Ql][N] -> dst [batch][2][Ql-1][N] against one key */
+int pha_keyswitch_mod_switch_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, const uint64_t *c2, size_t batch,
+                                     const uint64_t *const *rlk, uint64_t *dst, void *stream);
 /* tensor_prod_2x2_rns_poly for `batch` ciphertext pairs in the layout above: operands [batch][2][L][N],
  * res01 [batch][2][L][N] receives (c0, c1), res2 [batch][L][N] receives c2; res01 may alias operand1 */
 int pha_tensor_prod_2x2_batched(pha_context_t ctx, const uint64_t *operand1, const uint64_t *operand2, uint64_t *res01,
@@ -381,6 +396,14 @@ int pha_plain_inner_product_rescale_batched(pha_context_t ctx, size_t size_Ql, c
                                             size_t plain_term_stride, size_t plain_batch_stride,
                                             size_t ct_term_stride, size_t ct_batch_stride, size_t acc_batch_stride,
                                             int scheme, uint64_t *dst, size_t chunk, void *stream);
+/* bgv with the level drop: dst [batch][2][Ql-1][N] = mod_switch( S01[g] + keyswitch(S2[g]) ); bit-identical to
+ * pha_tensor_prod_2x2_sum_batched followed by pha_keyswitch_mod_switch_batched, operands, strides and `chunk` as
+ * pha_inner_product_relin_rescale_batched, its ckks counterpart (declared after the plaintext sums: existing declarations keep
+ * their neighbours). */
+int pha_inner_product_relin_mod_switch_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *op1, const uint64_t *op2,
+                                               size_t terms, size_t batch, size_t op1_term_stride, size_t op1_batch_stride,
+                                               size_t op2_term_stride, size_t op2_batch_stride, const uint64_t *const *rlk,
+                                               uint64_t *dst, size_t chunk, void *stream);
 /* phantom::hoisting_inplace (include/evaluate.cuh:233-241, src/evaluate.cu:1670-1866) on raw buffers:
  * ct [2][Ql][N] <- sum over the n_elts Galois elements of rotate(ct).  galois_elts is a HOST array;
  * glk is a HOST array of n_elts DEVICE pointer tables (PhantomRelinKey::public_keys_ptr() of each

@@ -727,6 +727,38 @@ int pha_inner_product_relin_batched(pha_context_t ctx, size_t size_Ql, const uin
     }
     PHA_API_END
 }
+// bgv: the sums of a chunk, then ONE fused key switch + mod_switch_to_next for the chunk (pha_keyswitch_mod_switch_batched)
+int pha_inner_product_relin_mod_switch_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *op1, const uint64_t *op2, size_t terms,
+                                               size_t batch, size_t op1_term_stride, size_t op1_batch_stride, size_t op2_term_stride,
+                                               size_t op2_batch_stride, const uint64_t *const *rlk, uint64_t *dst, size_t chunk,
+                                               void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    need(op1); need(op2); need(rlk); need(dst);
+    Context &c = ctx->c;
+    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("size_Ql out of range");
+    if (c.size_p == 0) throw std::invalid_argument("context has no special modulus");
+    if (size_Ql < 2) throw std::invalid_argument("cannot switch down the last remaining modulus");
+    if (!c.tool((uint32_t)size_Ql).bgv_ready) throw std::invalid_argument("bgv needs a plain modulus (pha_context_set_plain_modulus)");
+    sum_check(c, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride);
+    const size_t ql_n = size_Ql * c.n, out_n = (size_Ql - 1) * c.n;
+    sum_check_output(c, "dst", dst, batch * 2 * out_n, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride,
+                     op2_batch_stride);
+    if (batch == 0) return 0;
+    hipStream_t s = as_stream(stream);
+    sum_strict(c, "tensor_prod_2x2_sum operand1", op1, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, s);
+    sum_strict(c, "tensor_prod_2x2_sum operand2", op2, size_Ql, terms, batch, op2_term_stride, op2_batch_stride, s);
+    const size_t C = inner_product_chunk(c, size_Ql, chunk, batch);
+    u64 *s01 = c.scratch_outer(stream, C * 3 * ql_n), *s2 = s01 + C * 2 * ql_n;   // the sums of a chunk: [C][2][Ql][N] | [C][Ql][N]
+    for (size_t b0 = 0; b0 < batch; b0 += C) {
+        const size_t B = std::min(C, batch - b0);
+        launch_tensor_sum(c, op1 + b0 * op1_batch_stride, op2 + b0 * op2_batch_stride, s01, s2, size_Ql, terms, B, op1_term_stride,
+                          op1_batch_stride, op2_term_stride, op2_batch_stride, s);
+        const int rc = pha_keyswitch_mod_switch_batched(ctx, size_Ql, s01, s2, B, rlk, dst + b0 * 2 * out_n, stream);
+        if (rc != 0) return rc;   // (its message is the last error)
+    }
+    PHA_API_END
+}
+
 int pha_multiply_plain_sum_batched(pha_context_t ctx, const uint64_t *plain, const uint64_t *ct, const uint64_t *acc, uint64_t *res,
                                    size_t cms, size_t terms, size_t batch, size_t plain_term_stride, size_t plain_batch_stride,
                                    size_t ct_term_stride, size_t ct_batch_stride, size_t acc_batch_stride, void *stream) {

@@ -668,6 +668,92 @@ __global__ __launch_bounds__(256) void bgv_switch_kernel(const BgvSwitchArgs k) 
     k.dst[(size_t)blockIdx.z * k.dst_stride + (size_t)limb * k.n + coeff] = shoup(d, k.inv_q_last[limb], m.value);
 }
 
+// ---- pha_keyswitch_mod_switch: BGV key switch + mod_switch_to_next in one.  The mod-down's forward transform, the add to ct and
+//      the switch's inverse transform cancel (iNTT(ct + NTT(w)) = iNTT(ct) + w, word for word: every stored word is the canonical
+//      residue), so ct is folded into the extended-base sums in NTT form and ONE kernel does the work of p_to_t_kernel,
+//      bgv_moddown_kernel and bgv_switch_kernel in coefficient form. ------------------------------------------------------------
+struct BgvFoldArgs {
+    u64 *cx;                   // [polys][QlP][N], NTT form: limbs j < Ql receive cx_j + (P mod q_j) * ct_j
+    const u64 *ct;             // [polys][Ql][N], only read
+    const u64x2 *p_mod_q;
+    const DModulus *mod;
+    uint32_t n;
+    size_t cx_stride, ct_stride;
+};
+// two coefficients per thread (16-byte loads and stores); limb = blockIdx.y, polynomial = blockIdx.z
+__global__ __launch_bounds__(256) void bgv_fold_ct_kernel(const BgvFoldArgs k) {
+    const uint32_t limb = blockIdx.y;
+    const u64 q = k.mod[limb].value;
+    const u64x2 p = k.p_mod_q[limb];
+    const size_t id = (size_t)limb * k.n + ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
+    u64x2 *cx = reinterpret_cast<u64x2 *>(k.cx + (size_t)blockIdx.z * k.cx_stride + id);
+    const u64x2 a = *reinterpret_cast<const u64x2 *>(k.ct + (size_t)blockIdx.z * k.ct_stride + id);
+    u64x2 v = *cx;
+    v.x = add_mod(v.x, shoup(a.x, p, q), q);
+    v.y = add_mod(v.y, shoup(a.y, p, q), q);
+    *cx = v;
+}
+
+struct BgvDownSwitchArgs {
+    u64 *dst;                  // [polys][Ql-1][N], coefficient form
+    const u64 *cx;             // [polys][QlP][N], coefficient form (ct folded in)
+    const u64 *delta;          // [polys][Ql][N]: the P -> Ql conversion of cx's P limbs
+    size_t dst_stride, cx_stride, delta_stride;
+    const u64x2 *hat_inv;      // the constants of p_to_t_kernel, bgv_moddown_kernel and bgv_switch_kernel
+    const uint32_t *iprime;
+    const u64 *hat_mod_t;
+    const u64x2 *p_mod_q, *pinv, *q_last_mod_q, *inv_q_last;
+    const DModulus *mod;
+    DModulus t;
+    u64x2 pinv_t, inv_q_last_t;
+    uint32_t n, ql, alpha, per_group;   // output limbs [blockIdx.y * per_group, +per_group) of [0, ql - 1)
+};
+// bgv_moddown_kernel's word of one limb: (cx - delta + u (P mod q)) P^-1 mod q
+__device__ __forceinline__ u64 bgv_down_word(const BgvDownSwitchArgs &k, uint32_t limb, u64 q, u64 cx, u64 delta, u64 u) {
+    const u64 corr = shoup(u, k.p_mod_q[limb], q);
+    return shoup(add_mod(sub_mod(cx, delta, q), corr, q), k.pinv[limb], q);
+}
+// two coefficients per thread, polynomial = blockIdx.z; a thread walks the output limbs of its group, so the alpha + 2 reads
+// behind u, v_last and u' are made once per group
+__global__ __launch_bounds__(256) void bgv_down_switch_kernel(const BgvDownSwitchArgs k) {
+    const size_t coeff = ((size_t)blockIdx.x * 256 + threadIdx.x) * 2;
+    const u64 *cx = k.cx + (size_t)blockIdx.z * k.cx_stride + coeff;
+    const u64 *delta = k.delta + (size_t)blockIdx.z * k.delta_stride + coeff;
+    u64 *dst = k.dst + (size_t)blockIdx.z * k.dst_stride + coeff;
+    const uint32_t nl = k.ql - 1;
+    // [cx_P]_t (base_P_to_t_conv) and u = [cx_P]_t P^-1 mod t
+    u64 lo0 = 0, hi0 = 0, lo1 = 0, hi1 = 0;
+    for (uint32_t i = 0; i < k.alpha; i++) {
+        const u64 p = k.mod[k.iprime[i]].value;
+        const u64x2 h = k.hat_inv[i];
+        const u64x2 x = *reinterpret_cast<const u64x2 *>(cx + (size_t)(k.ql + i) * k.n);
+        mac128(shoup(x.x, h, p), k.hat_mod_t[i], lo0, hi0);
+        mac128(shoup(x.y, h, p), k.hat_mod_t[i], lo1, hi1);
+    }
+    const u64 tv = k.t.value;
+    const u64 u0 = shoup(barrett128(lo0, hi0, k.t), k.pinv_t, tv), u1 = shoup(barrett128(lo1, hi1, k.t), k.pinv_t, tv);
+    // the last limb of ct + keyswitch(c2) in coefficient form, and u' = (v_last mod t) q_last^-1 mod t
+    const u64 q_last = k.mod[nl].value;
+    const u64x2 cl = *reinterpret_cast<const u64x2 *>(cx + (size_t)nl * k.n);
+    const u64x2 dl = *reinterpret_cast<const u64x2 *>(delta + (size_t)nl * k.n);
+    const u64 last0 = bgv_down_word(k, nl, q_last, cl.x, dl.x, u0), last1 = bgv_down_word(k, nl, q_last, cl.y, dl.y, u1);
+    const u64 s0 = shoup(barrett64(last0, tv, k.t.ratio1), k.inv_q_last_t, tv);
+    const u64 s1 = shoup(barrett64(last1, tv, k.t.ratio1), k.inv_q_last_t, tv);
+    const uint32_t j0 = blockIdx.y * k.per_group, j1 = min(j0 + k.per_group, nl);
+    for (uint32_t j = j0; j < j1; j++) {
+        const DModulus m = k.mod[j];
+        const u64 q = m.value;
+        const u64x2 c = *reinterpret_cast<const u64x2 *>(cx + (size_t)j * k.n);
+        const u64x2 d = *reinterpret_cast<const u64x2 *>(delta + (size_t)j * k.n);
+        const u64x2 qlm = k.q_last_mod_q[j], iql = k.inv_q_last[j];
+        const u64 w0 = bgv_down_word(k, j, q, c.x, d.x, u0), w1 = bgv_down_word(k, j, q, c.y, d.y, u1);
+        u64x2 r;
+        r.x = shoup(add_mod(sub_mod(w0, barrett64(last0, q, m.ratio1), q), shoup(s0, qlm, q), q), iql, q);
+        r.y = shoup(add_mod(sub_mod(w1, barrett64(last1, q, m.ratio1), q), shoup(s1, qlm, q), q), iql, q);
+        *reinterpret_cast<u64x2 *>(dst + (size_t)j * k.n) = r;
+    }
+}
+
 // ---- key-switching key generation, arithmetic part (src/secretkey.cu:232-341): per digit d and limb j of QP
 //      b = -(a*s + u) [multiply_and_add_negate_rns_poly polymath.cu:234-251], and on the digit's own limbs
 //      b += P * new_key [multiply_temp_mod_and_add_rns_poly polymath.cu:318-338]; the key is (b, a). ----
@@ -1133,6 +1219,58 @@ static void keyswitch_rescale(Context &c, Tool &t, const u64 *ct, const u64 *c2,
     ntt_forward(c, tmp, tmp, dst, plain_sel(0, nl), EPI_FWD_KSRESCALE, x, s);
 }
 
+// Key switch + BGV mod_switch_to_next in one (build-defined fusion; equals keyswitch_inplace eval_key_switch.cu:95-182 under bgv
+// followed by mod_t_and_divide_q_last_ntt rns.cu:1186-1236 bit for bit): dst [B][2][Ql-1][N] = mod_switch(ct + keyswitch(c2)).
+// A sibling of moddown_from_ntt's bgv branch, not a mode of it.  Both the t-corrected mod-down and the switch work in coefficient
+// form, so the forward transform of 2 x Ql limbs, the add to ct and the inverse transform of the same limbs between them cancel:
+// ct rides into the one inverse transform as cx_j + (P mod q_j) ct_j (the division by P that follows gives it back), which leaves
+// 4 Ql + 2 alpha - 2 limb transforms per ciphertext after the inner product where the two calls run 8 Ql + 2 alpha - 2, two
+// element-wise passes for five, and no copy of ct.  Only generic pieces: every tool shape takes this path.
+static void keyswitch_mod_switch(Context &c, Tool &t, const u64 *ct, const u64 *c2, const u64 *const *rlk, u64 *dst, uint32_t B,
+                                 const KsScratch &k, hipStream_t s) {
+    const size_t n = c.n, ql = t.size_ql, ql_n = ql * n, qlp_n = (size_t)t.size_qlp * n, nl = ql - 1;
+    const uint32_t polys = 2 * B;
+    u64 *cx = k.cx, *delta = k.tmp;
+    modup_inner_prod(c, t, k, c2, ql_n, rlk, PHA_SCHEME_BGV, B, s);
+    {
+        const BgvFoldArgs f{cx, ct, t.p_mod_q2.p, c.d_mod.p, (uint32_t)n, qlp_n, ql_n};
+        hipLaunchKernelGGL(bgv_fold_ct_kernel, dim3((unsigned)(n / 512), (unsigned)ql, polys), dim3(256), 0, s, f);
+        check_launch();
+    }
+    NttExtra xb;
+    xb.batch = polys;
+    xb.poly_stride = qlp_n;
+    ntt_inverse(c, cx, cx, cx, special_sel(0, t.size_qlp, c.size_qp, c.size_p), EPI_INV_CANON, xb, s);
+    if (t.alpha == 1) {   // the branches of the bgv mod-down
+        for (uint32_t z = 0; z < polys; z++) {
+            SinglePArgs sp{delta + z * ql_n, nullptr, cx + z * qlp_n + ql_n, c.d_mod.p, t.d_qlp_prime.p, (uint32_t)ql, (uint32_t)n};
+            hipLaunchKernelGGL(single_p_kernel, dim3((unsigned)(n / 256), (unsigned)ql), dim3(256), 0, s, sp);
+            check_launch();
+        }
+    } else {
+        launch_bconv(c, t.d_p_to_ql_conv.p, 0, polys, t.alpha, (uint32_t)ql, t.moddown_split, delta, ql_n, cx, qlp_n, nullptr, true, s, 0, 0,
+                     nullptr);
+    }
+    BgvDownSwitchArgs a{};
+    a.dst = dst; a.cx = cx; a.delta = delta; a.dst_stride = nl * n; a.cx_stride = qlp_n; a.delta_stride = ql_n;
+    a.hat_inv = t.p_to_ql.hat_inv.p; a.iprime = t.p_to_ql.d_iprime.p; a.hat_mod_t = t.p_hat_mod_t.p;
+    a.p_mod_q = t.p_mod_q2.p; a.pinv = t.pinv2.p; a.q_last_mod_q = t.q_last_mod_q2.p; a.inv_q_last = t.inv_q_last2.p;
+    a.mod = c.d_mod.p; a.t = t.t_mod; a.pinv_t = t.pinv_mod_t; a.inv_q_last_t = t.inv_q_last_mod_t;
+    a.n = (uint32_t)n; a.ql = (uint32_t)ql; a.alpha = t.alpha;
+    // a group re-reads alpha + 2 shared limbs for its outputs' 2 each: at least 8 outputs per group, and more than that only
+    // while two workgroups per CU remain
+    const size_t col_blocks = (n / 512) * polys;
+    size_t groups = std::max<size_t>(1, std::min<size_t>((nl + 7) / 8, (2 * (size_t)c.num_cus + col_blocks - 1) / col_blocks));
+    a.per_group = (uint32_t)((nl + groups - 1) / groups);
+    groups = (nl + a.per_group - 1) / a.per_group;
+    hipLaunchKernelGGL(bgv_down_switch_kernel, dim3((unsigned)(n / 512), (unsigned)groups, polys), dim3(256), 0, s, a);
+    check_launch();
+    NttExtra xo;
+    xo.batch = polys;
+    xo.poly_stride = nl * n;
+    ntt_forward(c, dst, dst, dst, plain_sel(0, nl), EPI_FWD_CANON, xo, s);
+}
+
 void check_level(Context &c, size_t size_Ql, bool need_p) {
     if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("size_Ql out of range");
     if (need_p && c.size_p == 0) throw std::invalid_argument("context has no special modulus");
@@ -1280,6 +1418,32 @@ int pha_keyswitch_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint6
 int pha_keyswitch_rescale(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, const uint64_t *c2,
                           const uint64_t *const *rlk, uint64_t *dst, void *stream) {
     return pha_keyswitch_rescale_batched(ctx, size_Ql, ct, c2, 1, rlk, dst, stream);
+}
+
+int pha_keyswitch_mod_switch_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, const uint64_t *c2, size_t batch,
+                                     const uint64_t *const *rlk, uint64_t *dst, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    need(ct); need(c2); need(rlk); need(dst);
+    if (batch == 0) return 0;
+    Context &c = ctx->c;
+    check_level(c, size_Ql, true);
+    if (size_Ql < 2) throw std::invalid_argument("cannot switch down the last remaining modulus");
+    Tool &t = c.tool((uint32_t)size_Ql);
+    if (!t.bgv_ready) throw std::invalid_argument("bgv needs a plain modulus (pha_context_set_plain_modulus)");
+    check_ks_batch(t, batch);
+    hipStream_t s = as_stream(stream);
+    const uint32_t B = (uint32_t)batch;
+    const size_t n = c.n, ql_n = size_Ql * n;
+    if (overlaps(dst, B * 2 * (size_Ql - 1) * n, ct, B * 2 * ql_n) || overlaps(dst, B * 2 * (size_Ql - 1) * n, c2, B * ql_n))
+        throw std::invalid_argument("dst must not overlap ct or c2");
+    strict_ks_operands(c, t, ct, c2, rlk, B, s);
+    keyswitch_mod_switch(c, t, ct, c2, rlk, dst, B, KsScratch(c.scratch(stream, KsScratch::words(c, t, B)), c, t, B), s);
+    PHA_API_END
+}
+
+int pha_keyswitch_mod_switch(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, const uint64_t *c2,
+                             const uint64_t *const *rlk, uint64_t *dst, void *stream) {
+    return pha_keyswitch_mod_switch_batched(ctx, size_Ql, ct, c2, 1, rlk, dst, stream);
 }
 
 // BASELINE config 4 as one call (build-defined composition of relinearize_inplace src/evaluate.cu:1028-1077 and

@@ -1149,6 +1149,21 @@ inline void rescale_to_next_inplace(const PhantomContext &context, PhantomCipher
     return destination;
 }
 
+namespace detail {
+// correction_factor * q_last^-1 mod t (src/evaluate.cu:1421-1425): what a bgv mod_switch_to_next leaves as the correction factor
+inline uint64_t bgv_switched_correction_factor(const EncryptionParameters &parms, uint64_t correction_factor) {
+    const uint64_t t = parms.plain_modulus().value();
+    const uint64_t q_last_t = parms.coeff_modulus().back().value() % t;
+    __int128 r0 = t, r1 = q_last_t, s0 = 0, s1 = 1;
+    while (r1 != 0) {
+        const __int128 k = r0 / r1, r2 = r0 - k * r1, s2 = s0 - k * s1;
+        r0 = r1; r1 = r2; s0 = s1; s1 = s2;
+    }
+    const uint64_t inv = static_cast<uint64_t>(((s0 % static_cast<__int128>(t)) + t) % t);
+    return static_cast<uint64_t>((static_cast<unsigned __int128>(correction_factor) * inv) % t);
+}
+}  // namespace detail
+
 // mod_switch_to_next (src/evaluate.cu:1506-1543): CKKS drops the last limb (mod_switch_drop_to_next
 // :1429-1470); BFV / BGV divide by q_last (mod_switch_scale_to_next :1376-1427)
 [[nodiscard]] inline PhantomCiphertext mod_switch_to_next(const PhantomContext &context, const PhantomCiphertext &encrypted) {
@@ -1181,17 +1196,30 @@ inline void rescale_to_next_inplace(const PhantomContext &context, PhantomCipher
     auto copy = util::make_cuda_auto_ptr<uint64_t>(size * L * n, s);  // the switch works on a copy (:1392-1395)
     util::check_hip(hipMemcpyAsync(copy.get(), encrypted.data(), size * L * n * 8, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
     util::check_pha(pha_mod_t_and_divide_q_last_ntt(context.amd(), L, copy.get(), size, destination.data(), s));
-    // correction factor *= q_last^-1 mod t (:1421-1425)
-    const uint64_t t = parms.plain_modulus().value();
-    const uint64_t q_last_t = parms.coeff_modulus().back().value() % t;
-    __int128 r0 = t, r1 = q_last_t, s0 = 0, s1 = 1;
-    while (r1 != 0) {
-        const __int128 k = r0 / r1, r2 = r0 - k * r1, s2 = s0 - k * s1;
-        r0 = r1; r1 = r2; s0 = s1; s1 = s2;
-    }
-    const uint64_t inv = static_cast<uint64_t>(((s0 % static_cast<__int128>(t)) + t) % t);
-    destination.set_correction_factor(
-        static_cast<uint64_t>((static_cast<unsigned __int128>(encrypted.correction_factor()) * inv) % t));
+    destination.set_correction_factor(detail::bgv_switched_correction_factor(parms, encrypted.correction_factor()));
+    return destination;
+}
+
+// Extension (no reference function): relinearize_inplace (src/evaluate.cu:1028-1077) followed by mod_switch_to_next
+// (:1376-1427) as ONE call -- the same ciphertext bit for bit (pha_keyswitch_mod_switch: both divisions happen in coefficient
+// form, so the transforms between them cancel).  bgv, size-3 input.
+[[nodiscard]] inline PhantomCiphertext relinearize_mod_switch(const PhantomContext &context, const PhantomCiphertext &encrypted,
+                                                              const PhantomRelinKey &relin_keys) {
+    const auto &parms = context.get_context_data(encrypted.chain_index()).parms();
+    if (parms.scheme() != scheme_type::bgv) throw std::invalid_argument("unsupported operation for scheme type");
+    if (encrypted.size() != 3) throw std::invalid_argument("destination_size must be 3");
+    if (!encrypted.is_ntt_form()) throw std::invalid_argument("BGV encrypted must be in NTT form");
+    if (!relin_keys.generated()) throw std::invalid_argument("PhantomRelinKey has not been generated");
+    const auto &s = cudaStreamPerThread;
+    const size_t L = parms.coeff_modulus().size(), n = parms.poly_modulus_degree();
+    const size_t next = context.get_next_index(encrypted.chain_index());
+    PhantomCiphertext destination;
+    destination.resize(context, next, 2, s);
+    util::check_pha(pha_keyswitch_mod_switch(context.amd(), detail::level_size_Ql(context, encrypted), encrypted.data(),
+                                             encrypted.data() + 2 * L * n, relin_keys.public_keys_ptr(), destination.data(), s));
+    destination.set_ntt_form(true);
+    destination.set_scale(encrypted.scale());
+    destination.set_correction_factor(detail::bgv_switched_correction_factor(parms, encrypted.correction_factor()));
     return destination;
 }
 inline void mod_switch_to_next_inplace(const PhantomContext &context, PhantomCiphertext &encrypted) {
@@ -1399,6 +1427,11 @@ inline PhantomCiphertext multiply(const PhantomContext &c, const PhantomCipherte
 [[nodiscard]] inline PhantomCiphertext multiply_relin_rescale(const PhantomContext &context, const PhantomCiphertext &encrypted1,
                                                               const PhantomCiphertext &encrypted2, const PhantomRelinKey &relin_keys) {
     return relinearize_rescale(context, multiply(context, encrypted1, encrypted2), relin_keys);
+}
+// multiply + relinearize + mod_switch_to_next (bgv) with the fused second half
+[[nodiscard]] inline PhantomCiphertext multiply_relin_mod_switch(const PhantomContext &context, const PhantomCiphertext &encrypted1,
+                                                                 const PhantomCiphertext &encrypted2, const PhantomRelinKey &relin_keys) {
+    return relinearize_mod_switch(context, multiply(context, encrypted1, encrypted2), relin_keys);
 }
 inline PhantomCiphertext relinearize(const PhantomContext &c, const PhantomCiphertext &e, const PhantomRelinKey &k) { PhantomCiphertext d = e; relinearize_inplace(c, d, k); return d; }
 inline PhantomCiphertext multiply_and_relin(const PhantomContext &c, const PhantomCiphertext &a, const PhantomCiphertext &b, const PhantomRelinKey &k) { PhantomCiphertext d = a; multiply_and_relin_inplace(c, d, b, k); return d; }

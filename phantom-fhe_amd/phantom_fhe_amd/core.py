@@ -335,6 +335,15 @@ class PhantomContext:
         _lib.check(self._L.pha_keyswitch_rescale_batched(self._h, size_Ql, _ptr(ct), _ptr(c2), batch, _ptr(rlk_ptrs), _ptr(dst),
                                                          _stream()))
 
+    def keyswitch_mod_switch(self, size_Ql, ct, c2, rlk_ptrs, dst):
+        """dst [2][Ql-1][N] = mod_switch(ct + keyswitch(c2)) in one call (bgv): bit-identical to keyswitch_inplace followed by
+        mod_t_and_divide_q_last_ntt, without the forward / inverse transform pair between them; ct and c2 are only read."""
+        _lib.check(self._L.pha_keyswitch_mod_switch(self._h, size_Ql, _ptr(ct), _ptr(c2), _ptr(rlk_ptrs), _ptr(dst), _stream()))
+
+    def keyswitch_mod_switch_batched(self, size_Ql, ct, c2, batch, rlk_ptrs, dst):
+        _lib.check(self._L.pha_keyswitch_mod_switch_batched(self._h, size_Ql, _ptr(ct), _ptr(c2), batch, _ptr(rlk_ptrs), _ptr(dst),
+                                                            _stream()))
+
     def tensor_prod_2x2_batched(self, op1, op2, res01, res2, cms, batch):
         _lib.check(self._L.pha_tensor_prod_2x2_batched(self._h, _ptr(op1), _ptr(op2), _ptr(res01), _ptr(res2), cms,
                                                        batch, _stream()))
@@ -378,6 +387,13 @@ class PhantomContext:
         t1, b1, t2, b2 = self._sum_strides(op1, op2, size_Ql, terms, batch, strides)
         _lib.check(self._L.pha_inner_product_relin_batched(self._h, size_Ql, _ptr(op1), _ptr(op2), terms, batch, t1, b1, t2, b2,
                                                            _ptr(rlk_ptrs), int(scheme), _ptr(dst), chunk, _stream()))
+
+    def inner_product_relin_mod_switch_batched(self, size_Ql, op1, op2, terms, batch, rlk_ptrs, dst, strides=None, chunk=0):
+        """Extension (bgv): dst [batch][2][Ql-1][N] = mod_switch(relinearize(sum over k of op1[g][k] * op2[g][k])) with ONE key switch
+        per sum; bit-identical to tensor_prod_2x2_sum_batched followed by keyswitch_mod_switch_batched."""
+        t1, b1, t2, b2 = self._sum_strides(op1, op2, size_Ql, terms, batch, strides)
+        _lib.check(self._L.pha_inner_product_relin_mod_switch_batched(self._h, size_Ql, _ptr(op1), _ptr(op2), terms, batch, t1, b1, t2,
+                                                                      b2, _ptr(rlk_ptrs), _ptr(dst), chunk, _stream()))
 
     def _plain_sum_strides(self, plain, ct, cms, terms, batch, strides):
         """(plain term, plain batch, ct term, ct batch, acc batch) strides in 64-bit words.  None: the dense layout, plain

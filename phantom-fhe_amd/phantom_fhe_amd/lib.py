@@ -54,10 +54,13 @@ _SIGS = {
     "pha_keyswitch_inplace_batched": [vp, sz, vp, vp, sz, vp, C.c_int, vp],
     "pha_keyswitch_rescale": [vp, sz, vp, vp, vp, vp, vp],
     "pha_keyswitch_rescale_batched": [vp, sz, vp, vp, sz, vp, vp, vp],
+    "pha_keyswitch_mod_switch": [vp, sz, vp, vp, vp, vp, vp],
+    "pha_keyswitch_mod_switch_batched": [vp, sz, vp, vp, sz, vp, vp, vp],
     "pha_tensor_prod_2x2_batched": [vp, vp, vp, vp, vp, sz, sz, vp],
     "pha_tensor_prod_2x2_sum_batched": [vp, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, sz, vp],
     "pha_inner_product_relin_rescale_batched": [vp, sz, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, sz, vp],
     "pha_inner_product_relin_batched": [vp, sz, vp, vp, sz, sz, sz, sz, sz, sz, vp, C.c_int, vp, sz, vp],
+    "pha_inner_product_relin_mod_switch_batched": [vp, sz, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, sz, vp],
     "pha_multiply_plain_sum_batched": [vp, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, sz, sz, vp],
     "pha_plain_inner_product_rescale_batched": [vp, sz, vp, vp, vp, sz, sz, sz, sz, sz, sz, sz, C.c_int, vp, sz, vp],
     "pha_bfv_multiply_behz": [vp, vp, vp, vp, vp],

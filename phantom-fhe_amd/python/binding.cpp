@@ -174,6 +174,9 @@ PYBIND11_MODULE(pyPhantom, m) {
     // extensions (no reference name): relinearize + rescale_to_next as one call, same ciphertext (pha_keyswitch_rescale)
     m.def("relinearize_rescale", &relinearize_rescale);
     m.def("multiply_relin_rescale", &multiply_relin_rescale);
+    // the bgv counterpart: relinearize + mod_switch_to_next as one call, same ciphertext (pha_keyswitch_mod_switch)
+    m.def("relinearize_mod_switch", &relinearize_mod_switch);
+    m.def("multiply_relin_mod_switch", &multiply_relin_mod_switch);
     m.def("mod_switch_to_next", py::overload_cast<const PhantomContext &, const PhantomCiphertext &>(&mod_switch_to_next));
     m.def("apply_galois", &apply_galois);
     m.def("rotate", &rotate);
