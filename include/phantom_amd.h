@@ -559,6 +559,44 @@ int pha_bfv_multiply_plain(pha_context_t ctx, size_t size_Ql, uint64_t *ct, size
  * src/evaluate.cu:1150-1154, 1208-1212, 1319-1323 as one launch; the caller then applies
  * multiply_scalar_and_add/sub (correction factor) or multiply_rns_poly */
 int pha_bgv_lift_plain(pha_context_t ctx, size_t size_Ql, const uint64_t *plain, uint64_t *out, void *stream);
+/* Extension (no reference launcher; the reference runs multiply_plain_normal, src/evaluate.cu:1256-1300, once per product and
+ * add_inplace per term): BFV plaintext-weighted sums of ciphertexts with ONE forward transform per term and ONE inverse per sum
+ * (DESIGN.md section 4.8d).  All buffers are device memory, strides are 64-bit words, L = size_Ql.  Shared by the three entries:
+ * refused (status -1, nothing launched) are a null required pointer, size_Ql outside 1..|Q|, a context without a plain modulus,
+ * a plain modulus t that is not below every q_i of the level, an odd stride and buffers that are not 16-byte aligned.
+ *
+ * The lift: out (i) [L][N] at out + i * out_stride = NTT form of the centred lift of plain (i) ([N] words below t at plain +
+ * i * plain_stride; w >= (t + 1) / 2 becomes w + q_j - t in limb j) -- word for word pha_abs_plain_rns_poly followed by
+ * pha_nwt_2d_radix8_forward_inplace, but the lift is the load prologue of the transform's first pass: `count` plaintexts x L limbs
+ * go through one pair of launches and the lifted coefficient form never reaches memory.  Also refused: out_stride below L * N
+ * with count > 1, out overlapping plain.  count == 0 does nothing; counts beyond a launch's grid are cut into pieces. */
+int pha_bfv_lift_plain_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *plain, size_t count, size_t plain_stride,
+                               uint64_t *out, size_t out_stride, void *stream);
+/* For every g < batch, in the ring: res[g] = acc[g] + sum over k < terms of plain[g][k] * ct[g][k]   (acc == NULL: no addend).
+ * ct (g, k) at ct + g * ct_batch_stride + k * ct_term_stride, acc (g) and res (g) are [2][L][N] in COEFFICIENT form (bfv's
+ * form), canonical; plain (g, k) at plain_ntt + g * plain_batch_stride + k * plain_term_stride is [L][N] as
+ * pha_bfv_lift_plain_batched writes it; res is dense [batch][2][L][N].  A batch stride of 0 shares that operand between the
+ * groups.  Per `slab` terms (0: the default, 4) the slab's ciphertexts are transformed forward out of place into a work buffer
+ * ([chunk][slab][2][L][N] words; [slab][2][L][N], transformed once for all groups, when ct is shared), the one-launch sum of
+ * pha_multiply_plain_sum_batched adds the slab to the NTT-form partial sums kept in res, and after the last slab ONE inverse
+ * transform per `chunk` groups (0: the default, 8) runs in place in res and adds acc in its final store.  The operands are only
+ * read, nothing is copied, every chunk and slab size gives the same bits, and the call can be captured into a graph once the
+ * work buffer has its size (first call).  Word for word the loop of pha_bfv_multiply_plain (cipher_size 2, on copies) and
+ * pha_add_rns_poly in any order; terms == 1 without acc gives the words of pha_bfv_multiply_plain.  Also refused: terms == 0, a
+ * plain term stride below L * N or a ct term stride below 2 * L * N with terms > 1, res overlapping any operand (acc included).
+ * batch == 0 does nothing. */
+int pha_bfv_multiply_plain_sum_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *plain_ntt, const uint64_t *ct,
+                                       const uint64_t *acc, uint64_t *res, size_t terms, size_t batch,
+                                       size_t plain_term_stride, size_t plain_batch_stride, size_t ct_term_stride,
+                                       size_t ct_batch_stride, size_t acc_batch_stride, size_t chunk, size_t slab, void *stream);
+/* The same with RAW plaintexts: plain (g, k) is [N] words below t (what a bfv PhantomPlaintext holds; plain term stride at least N
+ * with terms > 1).  Each slab's plaintexts are lifted and transformed into the work buffer (another [chunk][slab][L][N] words;
+ * [slab][L][N], lifted once for all groups, when plain is shared).  Bit-identical to pha_bfv_lift_plain_batched followed by
+ * pha_bfv_multiply_plain_sum_batched. */
+int pha_bfv_plain_inner_product_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *plain, const uint64_t *ct,
+                                        const uint64_t *acc, uint64_t *res, size_t terms, size_t batch,
+                                        size_t plain_term_stride, size_t plain_batch_stride, size_t ct_term_stride,
+                                        size_t ct_batch_stride, size_t acc_batch_stride, size_t chunk, size_t slab, void *stream);
 
 /* ---- Galois (include/galois.cuh:98-130, src/galois.cu:11-39,67-102) ---- */
 int pha_apply_galois_ntt(pha_context_t ctx, const uint64_t *src, uint64_t *dst, uint32_t galois_elt,

@@ -8,6 +8,7 @@
 //   * strict mode (PHA_STRICT=1 in the environment when the library is loaded, or pha_set_strict(1)): the entry points that
 //     include/phantom_amd.h lists at pha_set_strict (dyadic, tensor, mod-up / inner product / mod-down, key switch, hoisting, BFV
 //     multiply) count first and fail with status -1 (invalid_argument, naming the operand) instead of computing.  Strict mode synchronises the stream per checked operand: a debugging aid, not for capture or timing.
+#include <algorithm>
 #include <atomic>
 #include <cstdlib>
 
@@ -41,6 +42,21 @@ __global__ __launch_bounds__(256) void canon_count_kernel(const CanonArgs k) {
     }
     const u64 q = k.mod[row].value;
     const bool bad = base[(size_t)limb * k.n + coeff] >= q;
+    const unsigned long long m = __ballot(bad);
+    if ((threadIdx.x & 63) == 0 && m) atomicAdd(k.count, (unsigned long long)__popcll(m));
+}
+
+// words of `polys` raw plaintexts ([N] words each, plain_stride apart) that are not below t
+struct PlainCountArgs {
+    const u64 *data;
+    unsigned long long *count;
+    u64 t;
+    uint32_t n;
+    size_t stride;
+};
+__global__ __launch_bounds__(256) void plain_count_kernel(const PlainCountArgs k) {
+    const uint32_t coeff = blockIdx.x * 256 + threadIdx.x;
+    const bool bad = k.data[(size_t)blockIdx.y * k.stride + coeff] >= k.t;
     const unsigned long long m = __ballot(bad);
     if ((threadIdx.x & 63) == 0 && m) atomicAdd(k.count, (unsigned long long)__popcll(m));
 }
@@ -109,6 +125,24 @@ void strict_operand(Context &c, const char *what, const u64 *data, const RowMap 
     if (bad)
         throw std::invalid_argument(std::string("PHA_STRICT: ") + what + " holds " + std::to_string(bad) +
                                     " word(s) >= their limb's modulus (operands must be canonical; include/phantom_amd.h)");
+}
+void strict_plain(Context &c, const char *what, const u64 *data, u64 t, size_t polys, size_t stride, hipStream_t s) {
+    if (!strict_mode() || !data) return;
+    unsigned long long *d_count = nullptr, host = 0;
+    PHA_HIP(hipMalloc(&d_count, sizeof(unsigned long long)));   // (a debugging path, like run_count)
+    hipError_t e = hipMemsetAsync(d_count, 0, sizeof(unsigned long long), s);
+    for (size_t p0 = 0; p0 < polys && e == hipSuccess; p0 += 65535) {
+        const PlainCountArgs k{data + p0 * stride, d_count, t, (uint32_t)c.n, stride};
+        hipLaunchKernelGGL(plain_count_kernel, dim3((unsigned)(c.n / 256), (unsigned)std::min<size_t>(65535, polys - p0)), dim3(256), 0, s, k);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&host, d_count, sizeof(host), hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    (void)hipFree(d_count);
+    PHA_HIP(e);
+    if (host)
+        throw std::invalid_argument(std::string("PHA_STRICT: ") + what + " holds " + std::to_string(host) +
+                                    " word(s) >= the plain modulus (a bfv plaintext's words are below t; include/phantom_amd.h)");
 }
 void strict_keys(Context &c, const char *what, const u64 *const *keys, uint32_t n_keys, uint32_t size_Ql, hipStream_t s) {
     if (!strict_mode() || !keys) return;

@@ -336,6 +336,7 @@ u64 count_noncanonical(Context &c, const u64 *data, const RowMap &rows, uint32_t
 u64 count_noncanonical_keys(Context &c, const u64 *const *keys, uint32_t n_keys, uint32_t size_Ql, hipStream_t s);
 void strict_operand(Context &c, const char *what, const u64 *data, const RowMap &rows, uint32_t polys, size_t poly_stride, hipStream_t s);
 void strict_keys(Context &c, const char *what, const u64 *const *keys, uint32_t n_keys, uint32_t size_Ql, hipStream_t s);
+void strict_plain(Context &c, const char *what, const u64 *data, u64 t, size_t polys, size_t stride, hipStream_t s);   // raw bfv plaintexts: words below t
 
 // NTT drivers (pha_ntt.hip): pass 1 reads `in` and writes `mid`, pass 2 reads `mid` and writes `out`
 struct NttExtra {
@@ -353,6 +354,8 @@ struct NttExtra {
     bool first_pass_done = false;                        // forward: the strided pass already ran (r05: fused into the mod-up's base conversion, modup_conv_strided)
     const u64 *pro_src = nullptr;                        // forward only: every limb of polynomial z transforms
     size_t pro_stride = 0;                               //   (pro_src + z * pro_stride) mod its own prime; `in` unused
+    u64 pro_lift_t = 0;                                  //   != 0 (EPI_FWD_CANON only): the words are below this t and are LIFTED instead, centred (pha_bfv_lift.h)
+    size_t aux_pair_stride = 0;                          // EPI_INV_CANON_ADD: polynomials come in pairs; pair g adds aux + g * aux_pair_stride (+ aux_stride for its second)
     uint32_t excl_step = 0;                              // polynomial z skips [excl_start + z*step, min(+len, limit))
     uint32_t excl_limit = 0xffffffffu;
     uint32_t excl_mod = 0;                               // != 0: the skipped range follows z % excl_mod (batches of ciphertexts)
@@ -506,6 +509,13 @@ void launch_tensor(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs,
 void launch_tensor_batched(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, uint32_t remap_from, uint32_t remap_add,
                            bool square, size_t batch, hipStream_t s);
 void launch_add(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, size_t mod_start, hipStream_t s);
+// plain_sum_kernel (pha_poly.hip), launch only: res[g] = acc[g] + sum_k plain[g][k] (.) ct[g][k]; strides as pha_multiply_plain_sum_batched
+void launch_plain_sum(Context &c, const u64 *plain, const u64 *ct, const u64 *acc, u64 *res, size_t cms, size_t terms, size_t batch,
+                      size_t tp, size_t bp, size_t tc, size_t bc, size_t ba, hipStream_t s);
+// does out [out_words] touch any of the operand's buffers (op_words each at op + g * bs + k * ts)?
+bool touches_operand(const u64 *out, size_t out_words, const u64 *op, size_t terms, size_t batch, size_t ts, size_t bs, size_t op_words);
+// strict mode: every distinct [2][L][N] ciphertext of an operand (pha_poly.hip)
+void sum_strict(Context &c, const char *what, const u64 *op, size_t cms, size_t terms, size_t batch, size_t ts, size_t bs, hipStream_t s);
 
 void register_context(Context *c, bool alive);   // live-context list walked by the per-thread arena reaper
 

@@ -89,6 +89,8 @@ struct NttKArgs {
     // back on ONE XCD (block b -> XCD b % 8), so that the twiddle rows they share are fetched into that L2 once
     uint32_t zfast_tiles;    // 0 = plain 3-D grid (tile, limb, polynomial); else tiles per limb of the 1-D form
     uint32_t zfast_run;      // tiles of one polynomial that run back to back before the next polynomial's (a multiple of 8)
+    u64 pro_t;               // != 0: the prologue is the BFV plain lift instead (PRO_LIFT kernels): pro_src holds words below pro_t
+    size_t aux_pair_stride;  // EPI_INV_CANON_ADD: polynomial z adds aux + (z / 2) * aux_pair_stride + (z % 2) * aux_stride (acc of group z / 2)
     const u64 *h_primes;     // HOST copy of the context's primes (launchers only: which limbs run on the FP64 back end)
 };
 
@@ -128,7 +130,7 @@ __device__ __forceinline__ void tile_args(const NttKArgs &k, uint32_t twr, uint3
         a.scale.x = k.scale[twr];
         a.scale.y = k.scale_shoup[twr];
     }
-    a.aux = (EPI == EPI_FWD_MODDOWN || EPI == EPI_FWD_MODDOWN_ADD || EPI == EPI_FWD_KSRESCALE) ? k.aux + (size_t)twr * n : nullptr;
+    a.aux = (EPI == EPI_FWD_MODDOWN || EPI == EPI_FWD_MODDOWN_ADD || EPI == EPI_FWD_KSRESCALE || EPI == EPI_INV_CANON_ADD) ? k.aux + (size_t)twr * n : nullptr;
     if (EPI == EPI_FWD_KSRESCALE) {
         a.scale2.x = k.scale2[twr];
         a.scale2.y = k.scale2_shoup[twr];
@@ -166,11 +168,14 @@ __device__ __forceinline__ void full_tile_args(const NttKArgs &k, uint32_t twr, 
         if (EPI == EPI_FWD_MODDOWN || EPI == EPI_FWD_MODDOWN_ADD || EPI == EPI_FWD_KSRESCALE) a.aux += (size_t)z * k.aux_stride;
         if (EPI == EPI_FWD_KSRESCALE) a.aux2 += (size_t)z * k.aux2_stride;
     }
+    if (EPI == EPI_INV_CANON_ADD) a.aux += (size_t)(z >> 1) * k.aux_pair_stride + (size_t)(z & 1) * k.aux_stride;
     if (FWD && (C::STRIDED || C::WHOLE) && k.pro_src) {  // rescale prologue: transform (the last limb of polynomial z) mod this prime
         const uint32_t prime = twr >= k.sel.remap_from ? twr + k.sel.remap_add : twr;
         a.in = k.pro_src + (size_t)z * k.pro_stride;
         a.pro_reduce = true;
         a.pro_ratio1 = k.mod[prime].ratio1;
+        a.pro_half = bfv_lift_threshold(k.pro_t);   // (read by the PRO_LIFT kernels only)
+        a.pro_inc = bfv_lift_increment(a.q, k.pro_t);
     }
 }
 
@@ -179,11 +184,11 @@ __device__ __forceinline__ void full_tile_args(const NttKArgs &k, uint32_t twr, 
 // back end (sweep at 2^16, 60 / 240 / 1020 limbs: 36.3 / 118 / 505 us with one shared body, 32.8 / 107 / 458 us specialised).
 // COH: the pass reads what other workgroups of this launch wrote (one-launch transform).
 // ONLY: 0 = both back ends (a.fp decides), 2 = the caller knows the limb runs on the integer back end (one body: fewer registers).
-template <class C, bool FWD, int EPI, bool FOLD, int HOIST, bool COH, int ONLY = 0>
+template <class C, bool FWD, int EPI, bool FOLD, int HOIST, bool COH, int ONLY = 0, int PRO = PRO_NONE>
 __device__ __forceinline__ void exec_pass(const PassArgs &a, u64 *lds, int tid) {
     u64 reg[C::EPT];
     u64x2 twreg[C::TW_TOTAL];
-    using Prog = PassProgram<C, FWD, EPI, FOLD, HOIST, COH>;
+    using Prog = PassProgram<C, FWD, EPI, FOLD, HOIST, COH, PRO>;
     auto pass = [&](const PassArgs &pa) __attribute__((always_inline)) {
         Prog::load_twiddles(pa, tid, twreg);
         Prog::template run<0>(pa, lds, tid, reg, twreg);
@@ -318,7 +323,7 @@ template <class C> constexpr int x_occ() { return C::WHOLE ? 1 : C::STRIDED ? (C
 #else
 #define PHA_PASS_BOUNDS __launch_bounds__(C::THREADS)
 #endif
-template <class C, bool FWD, int EPI, bool FOLD, int HOIST>
+template <class C, bool FWD, int EPI, bool FOLD, int HOIST, int PRO = PRO_NONE>
 __global__ PHA_PASS_BOUNDS PHA_PASS_ATTR void ntt_pass_kernel(const NttKArgs k) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64 *lds = reinterpret_cast<u64 *>(smem);
@@ -343,7 +348,7 @@ __global__ PHA_PASS_BOUNDS PHA_PASS_ATTR void ntt_pass_kernel(const NttKArgs k) 
     const unsigned long long wg_t0 = wall_clock64();
 #endif
     PHA_STAMP(0);
-    exec_pass<C, FWD, EPI, FOLD, HOIST, false>(a, lds, threadIdx.x);
+    exec_pass<C, FWD, EPI, FOLD, HOIST, false, 0, PRO>(a, lds, threadIdx.x);
 #if defined(PHA_EXP_STAMPS)
     __builtin_amdgcn_s_waitcnt(0);
     PHA_STAMP(6);
@@ -499,7 +504,7 @@ __global__ __launch_bounds__(512, PHA_FUSED_MIN_WAVES) void ntt_fused_kernel(con
 
 #endif  // PHA_EXPERIMENTS
 
-template <class C, bool FWD, int EPI, bool FOLD>
+template <class C, bool FWD, int EPI, bool FOLD, int PRO = PRO_NONE>
 static void launch_pass(const NttKArgs &k, hipStream_t s) {
     const size_t n = (size_t)1 << k.log_n;
     const size_t lds_bytes = (size_t)C::LDS_WORDS * sizeof(u64);
@@ -526,7 +531,7 @@ static void launch_pass(const NttKArgs &k, hipStream_t s) {
         PHA_HIP(hipGetDevice(&dev));
         const uint64_t bit = 1ull << (dev & 63);
         if (!(raised.load(std::memory_order_acquire) & bit)) {
-            PHA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt_pass_kernel<C, FWD, EPI, FOLD, (C::WHOLE ? 0 : C::STRIDED ? PHA_X_HOIST_S : PHA_X_HOIST_C)>),
+            PHA_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&ntt_pass_kernel<C, FWD, EPI, FOLD, (C::WHOLE ? 0 : C::STRIDED ? PHA_X_HOIST_S : PHA_X_HOIST_C), PRO>),
                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
             raised.fetch_or(bit, std::memory_order_release);
         }
@@ -539,9 +544,9 @@ static void launch_pass(const NttKArgs &k, hipStream_t s) {
     static const size_t pad_s = std::getenv("PHA_X_LDS_S") ? (size_t)std::atol(std::getenv("PHA_X_LDS_S")) : 0;
     static const size_t pad_c = std::getenv("PHA_X_LDS_C") ? (size_t)std::atol(std::getenv("PHA_X_LDS_C")) : 0;
     const size_t lds_x = lds_bytes + (C::STRIDED ? pad_s : pad_c);
-    hipLaunchKernelGGL((ntt_pass_kernel<C, FWD, EPI, FOLD, HX>), grid, dim3(C::THREADS), lds_x, s, kk);
+    hipLaunchKernelGGL((ntt_pass_kernel<C, FWD, EPI, FOLD, HX, PRO>), grid, dim3(C::THREADS), lds_x, s, kk);
 #else
-    hipLaunchKernelGGL((ntt_pass_kernel<C, FWD, EPI, FOLD, HX>), grid, dim3(C::THREADS), lds_bytes, s, kk);
+    hipLaunchKernelGGL((ntt_pass_kernel<C, FWD, EPI, FOLD, HX, PRO>), grid, dim3(C::THREADS), lds_bytes, s, kk);
 #endif
     check_launch();
 }
@@ -585,6 +590,14 @@ static bool launch_fused(Context &c, const NttKArgs &kA_in, const NttKArgs &kB_i
 
 #endif  // PHA_EXPERIMENTS
 
+// the inverse transform's last pass (the strided one, or the whole transform) with the epilogue the caller asked for
+template <class P>
+static void launch_inverse_last(const NttKArgs &k, int epi, hipStream_t s) {
+    if (epi == EPI_INV_SCALE) launch_pass<P, false, EPI_INV_SCALE, true>(k, s);
+    else if (epi == EPI_INV_CANON_ADD) launch_pass<P, false, EPI_INV_CANON_ADD, true>(k, s);
+    else launch_pass<P, false, EPI_INV_CANON, true>(k, s);
+}
+
 // N = 4096 / 8192 as ONE pass (the transform fits a tile): T1 = 1, T2 = N
 template <class W>
 static void forward_whole(NttKArgs k, int epi, hipStream_t s) {
@@ -594,6 +607,7 @@ static void forward_whole(NttKArgs k, int epi, hipStream_t s) {
     if (epi == EPI_FWD_MODDOWN) launch_pass<W, true, EPI_FWD_MODDOWN, false>(k, s);
     else if (epi == EPI_FWD_MODDOWN_ADD) launch_pass<W, true, EPI_FWD_MODDOWN_ADD, false>(k, s);
     else if (epi == EPI_FWD_KSRESCALE) launch_pass<W, true, EPI_FWD_KSRESCALE, false>(k, s);
+    else if (k.pro_t) launch_pass<W, true, EPI_FWD_CANON, false, PRO_LIFT>(k, s);
     else launch_pass<W, true, EPI_FWD_CANON, false>(k, s);
 }
 template <class W>
@@ -601,8 +615,7 @@ static void inverse_whole(NttKArgs k, int epi, hipStream_t s) {
     k.t1 = 1;
     k.t2 = W::T;
     k.mid = k.out;
-    if (epi == EPI_INV_SCALE) launch_pass<W, false, EPI_INV_SCALE, true>(k, s);
-    else launch_pass<W, false, EPI_INV_CANON, true>(k, s);
+    launch_inverse_last<W>(k, epi, s);
 }
 
 // the batched, twiddle-resident passes (ntt_zloop_kernel): plain launches of >= 8 polynomials that fill the device
@@ -677,7 +690,7 @@ static void forward_impl(NttKArgs k, int epi, hipStream_t s, Context *fused = nu
     k.pro_src = nullptr;   // the rescale prologue belongs to the first pass
 #if defined(PHA_EXPERIMENTS)
     if constexpr (P1::THREADS == 512 && P1::LOGTILE == 12 && P2::THREADS == 64) {
-        if (fused && epi != EPI_FWD_KSRESCALE && !k.first_pass_done) {   // both passes in one launch
+        if (fused && epi != EPI_FWD_KSRESCALE && !k.first_pass_done && !k.pro_t) {   // both passes in one launch
             const bool done = epi == EPI_FWD_MODDOWN ? launch_fused<P1, P2, true, EPI_FWD_MODDOWN, false>(*fused, k1, k, s)
                               : epi == EPI_FWD_MODDOWN_ADD ? launch_fused<P1, P2, true, EPI_FWD_MODDOWN_ADD, false>(*fused, k1, k, s)
                                                            : launch_fused<P1, P2, true, EPI_FWD_CANON, false>(*fused, k1, k, s);
@@ -689,7 +702,9 @@ static void forward_impl(NttKArgs k, int epi, hipStream_t s, Context *fused = nu
 #endif
     // (the strided pass in the batched form measured SLOWER -- 720 limbs 282 -> 302 us: its twiddles are few and shared by a tile's columns,
     //  and a 512-thread workgroup that walks several polynomials keeps its barrier schedule for all of them)
-    if (!k.first_pass_done) launch_pass<P1, true, EPI_NONE, false>(k1, s);
+    if (k.first_pass_done) {
+    } else if (k1.pro_t) launch_pass<P1, true, EPI_NONE, false, PRO_LIFT>(k1, s);   // (a plaintext's words lifted as they are loaded)
+    else launch_pass<P1, true, EPI_NONE, false>(k1, s);
     if (k.first_pass_only) return;
     // pass 1 ran in -> mid with the input stride; pass 2 reads mid and writes out with the output stride
 #if !defined(PHA_NO_ZLOOP)
@@ -725,7 +740,7 @@ static void inverse_impl(NttKArgs k, int epi, hipStream_t s, Context *fused = nu
     k.out_stride = final_stride;
 #if defined(PHA_EXPERIMENTS)
     if constexpr (P1::THREADS == 512 && P1::LOGTILE == 12 && P2::THREADS == 64) {
-        if (fused) {
+        if (fused && epi != EPI_INV_CANON_ADD) {
             const bool done = epi == EPI_INV_SCALE ? launch_fused<P1, P2, false, EPI_INV_SCALE, true>(*fused, k1, k, s)
                                                    : launch_fused<P1, P2, false, EPI_INV_CANON, true>(*fused, k1, k, s);
             if (done) return;
@@ -739,22 +754,19 @@ static void inverse_impl(NttKArgs k, int epi, hipStream_t s, Context *fused = nu
         using IpPlan = NttPlan<LOGN, (LOGN >= 14 && LOGN <= 16) ? PHA_IP_PLAN : 3>;
         if (P1::LOGT + IpPlan::P2::LOGT != LOGN)
             throw std::logic_error("second_pass_only: the chosen plan's strided pass does not complete the fused mod-up's contiguous pass");
-        if (epi == EPI_INV_SCALE) launch_pass<P1, false, EPI_INV_SCALE, true>(k, s);
-        else launch_pass<P1, false, EPI_INV_CANON, true>(k, s);
+        launch_inverse_last<P1>(k, epi, s);
         return;
     }
 #if !defined(PHA_NO_ZLOOP)
     if constexpr (VARIANT == 10 || VARIANT == 3 || VARIANT == 4) {   // batched launches: the contiguous pass with the twiddles resident (ntt_zloop_kernel)
         using Z2 = typename NttPlan<LOGN, VARIANT == 4 ? 3 : VARIANT>::P2;
         if (!launch_zloop<Z2, false, EPI_NONE, false>(k1, s)) launch_pass<P2, false, EPI_NONE, false>(k1, s);
-        if (epi == EPI_INV_SCALE) launch_pass<P1, false, EPI_INV_SCALE, true>(k, s);
-        else launch_pass<P1, false, EPI_INV_CANON, true>(k, s);
+        launch_inverse_last<P1>(k, epi, s);
         return;
     }
 #endif
     launch_pass<P2, false, EPI_NONE, false>(k1, s);
-    if (epi == EPI_INV_SCALE) launch_pass<P1, false, EPI_INV_SCALE, true>(k, s);
-    else launch_pass<P1, false, EPI_INV_CANON, true>(k, s);
+    launch_inverse_last<P1>(k, epi, s);
 }
 
 static NttKArgs make_args(Context &c, const u64 *in, u64 *mid, u64 *out, const LimbSel &sel, const NttExtra &x,
@@ -795,6 +807,8 @@ static NttKArgs make_args(Context &c, const u64 *in, u64 *mid, u64 *out, const L
     k.excl_mod = x.excl_mod;
     k.pro_src = fwd ? x.pro_src : nullptr;
     k.pro_stride = x.pro_stride;
+    k.pro_t = fwd && x.pro_src ? x.pro_lift_t : 0;
+    k.aux_pair_stride = x.aux_pair_stride;
     uint32_t excl = 0;
     if (sel.excl_end > sel.excl_start) {
         const uint32_t lo = sel.excl_start > sel.start ? sel.excl_start : sel.start;
@@ -1154,6 +1168,7 @@ void ntt_forward(Context &c, const u64 *in, u64 *mid, u64 *out, const LimbSel &s
     if (sel.count == 0) return;
     check_sel(c, sel);
     NttKArgs k = make_args(c, in, mid, out, sel, x, true);
+    if (k.pro_t && (epi != EPI_FWD_CANON || x.first_pass_done)) throw std::logic_error("ntt_forward: the plain lift goes with the plain forward transform only");
     const NttChoice ch = choose_plan(c, sel, x);
     k.zfast_tiles = ch.zfast ? 1u : 0u;   // request: launch_pass turns it into the tile count of the contiguous pass
     if (ch.whole == 12) return forward_whole<WholePlan12>(k, epi, s);

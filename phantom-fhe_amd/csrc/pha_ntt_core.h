@@ -23,6 +23,7 @@
 // the exact thread program (indexing, LDS layout, twiddle addressing) on the CPU against the oracle.
 #pragma once
 #include "pha_arith.h"
+#include "pha_bfv_lift.h"
 
 namespace pha {
 
@@ -39,6 +40,14 @@ enum Epilogue {
     // forward: out = (ct + cx * PInv - NTT(v)) * q_last^-1 -- the mod-down epilogue (ntt_moddown.cu:203-208), add_to_ct
     // (rns_bconv.cu:763-769) and the rescale epilogue (rns.cu:1141-1158) of key switch + rescale in one (pha_keyswitch_rescale)
     EPI_FWD_KSRESCALE = 6,
+    EPI_INV_CANON_ADD = 7,    // inverse: out = acc + iNTT(.), canonical (the one inverse of a BFV plaintext-weighted sum, pha_plain.hip); aux = acc
+};
+
+// Load prologues of a transform's first pass that are chosen at compile time (PassProgram's PRO).  PRO_NONE keeps the run-time
+// rescale prologue (PassArgs::pro_reduce) and is what every instantiation from before the BFV plain lift is.
+enum Prologue {
+    PRO_NONE = 0,
+    PRO_LIFT = 1,   // forward: `in` holds words below t; each becomes its centred lift modulo this limb's prime (pha_bfv_lift.h)
 };
 
 // Round schedule of one pass: LOGT stages split into NR rounds of R0,R1,R2 stages (forward order).
@@ -130,6 +139,7 @@ struct PassArgs {
     // first reduced modulo this limb's prime (divide_and_round_reduce_q_last_kernel rns.cu:1128-1139)
     bool pro_reduce;
     u64 pro_ratio1;    // floor(2^64 / q)
+    u64 pro_half, pro_inc;   // PRO_LIFT: (t + 1) / 2 and q - t
 };
 
 template <class C>
@@ -368,6 +378,7 @@ PHA_HD u64 apply_epilogue_v(u64 x, const PassArgs &a, u64 aux, u64 acc) {
         return shoup(sub_mod(u, t, q), a.scale, q);
     }
     if (EPI == EPI_INV_CANON) return PHA_FPSEL(a) ? x : csub(csub(x, q << 1), q);
+    if (EPI == EPI_INV_CANON_ADD) return add_mod(aux, PHA_FPSEL(a) ? x : csub(csub(x, q << 1), q), q);   // aux carries acc's word
     if (EPI == EPI_INV_SCALE) return shoup(x, a.scale, q);
     return x;
 }
@@ -375,7 +386,7 @@ PHA_HD u64 apply_epilogue_v(u64 x, const PassArgs &a, u64 aux, u64 acc) {
 template <int EPI>
 PHA_HD u64 apply_epilogue(u64 x, const PassArgs &a, size_t gi) {
     u64 aux = 0, acc = 0;
-    if (EPI == EPI_FWD_MODDOWN || EPI == EPI_FWD_MODDOWN_ADD || EPI == EPI_FWD_KSRESCALE) aux = a.aux[gi];
+    if (EPI == EPI_FWD_MODDOWN || EPI == EPI_FWD_MODDOWN_ADD || EPI == EPI_FWD_KSRESCALE || EPI == EPI_INV_CANON_ADD) aux = a.aux[gi];
     if (EPI == EPI_FWD_MODDOWN_ADD) acc = a.out[gi];
     if (EPI == EPI_FWD_KSRESCALE) acc = a.aux2[gi];
     return apply_epilogue_v<EPI>(x, a, aux, acc);
@@ -636,7 +647,7 @@ PHA_HD void round_out(const PassArgs &a, u64 *lds, int tid, const u64 *reg) {
 #pragma unroll
                 for (int k = 0; k < K; k += 2) {
                     u64x2 aux{0, 0}, acc{0, 0};
-                    if (EPI == EPI_FWD_MODDOWN || EPI == EPI_FWD_MODDOWN_ADD || EPI == EPI_FWD_KSRESCALE)
+                    if (EPI == EPI_FWD_MODDOWN || EPI == EPI_FWD_MODDOWN_ADD || EPI == EPI_FWD_KSRESCALE || EPI == EPI_INV_CANON_ADD)
                         aux = reinterpret_cast<const u64x2 *>(a.aux + g0)[k >> 1];
                     if (EPI == EPI_FWD_MODDOWN_ADD) acc = p[k >> 1];
                     if (EPI == EPI_FWD_KSRESCALE) acc = reinterpret_cast<const u64x2 *>(a.aux2 + g0)[k >> 1];
@@ -680,7 +691,7 @@ PHA_HD void tile_sync() {
 #endif
 }
 
-template <class C, bool FWD, int EPI, bool FOLD, int HOIST = 1, bool COH = false>
+template <class C, bool FWD, int EPI, bool FOLD, int HOIST = 1, bool COH = false, int PRO = PRO_NONE>
 struct PassProgram {
     static constexpr int NSEG = C::NR;
     static constexpr int THREADS = C::THREADS;
@@ -807,7 +818,13 @@ struct PassProgram {
         // go out at once, the butterflies then run at normal priority (720 limbs -2 %, tools/build_variant.sh prioA)
         if (first) __builtin_amdgcn_s_setprio(0);
 #endif
-        if (first && FWD && FIRST_PASS && a.pro_reduce) {  // uniform per workgroup
+        if constexpr (PRO == PRO_LIFT) {   // BFV plain lift: the words just loaded are a plaintext's, below t
+            static_assert(FWD && FIRST_PASS, "the plain lift is the load prologue of a forward transform's first pass");
+            if (first) {
+#pragma unroll
+                for (int i = 0; i < C::EPT; i++) reg[i] = bfv_lift_word(reg[i], a.pro_half, a.pro_inc);
+            }
+        } else if (first && FWD && FIRST_PASS && a.pro_reduce) {  // uniform per workgroup
 #pragma unroll
             for (int i = 0; i < C::EPT; i++) reg[i] = barrett64(reg[i], a.q, a.pro_ratio1);
         }

@@ -407,7 +407,7 @@ __global__ __launch_bounds__(kEwThreads, 8) void plain_sum_kernel(const PlainSum
 }
 
 // launch only: the callers have validated (plain_sum_check below)
-static void launch_plain_sum(Context &c, const u64 *plain, const u64 *ct, const u64 *acc, u64 *res, size_t cms, size_t terms,
+void launch_plain_sum(Context &c, const u64 *plain, const u64 *ct, const u64 *acc, u64 *res, size_t cms, size_t terms,
                              size_t batch, size_t tp, size_t bp, size_t tc, size_t bc, size_t ba, hipStream_t s) {
     PlainSumArgs k{plain, ct, acc, res, c.d_mod.p, c.d_fpinfo.p, (uint32_t)c.n, (uint32_t)cms, (uint32_t)terms, tp, bp, tc, bc, ba};
     const dim3 grid((unsigned)(c.n / (kEwThreads * kEwPerThread)), (unsigned)cms, (unsigned)batch), block(kEwThreads);
@@ -438,7 +438,7 @@ static bool ranges_overlap(const u64 *a, size_t na, const u64 *b, size_t nb) { r
 
 // does out [out_words] touch any operand ciphertext (2 L N words at op + g * bs + k * ts)?  The span of all of them first: the
 // usual call is answered by one comparison
-static bool touches_operand(const u64 *out, size_t out_words, const u64 *op, size_t terms, size_t batch, size_t ts, size_t bs,
+bool pha::touches_operand(const u64 *out, size_t out_words, const u64 *op, size_t terms, size_t batch, size_t ts, size_t bs,
                             size_t ct_words) {
     const size_t groups = bs ? batch : 1;
     if (!ranges_overlap(out, out_words, op, (groups - 1) * bs + (terms - 1) * ts + ct_words)) return false;
@@ -472,7 +472,7 @@ static void sum_check_output(Context &c, const char *name, const u64 *out, size_
 }
 
 // strict mode: every distinct operand ciphertext, in runs of at most 65534 polynomials per count (grid z); never skipped
-static void sum_strict(Context &c, const char *what, const u64 *op, size_t cms, size_t terms, size_t batch, size_t ts, size_t bs,
+void pha::sum_strict(Context &c, const char *what, const u64 *op, size_t cms, size_t terms, size_t batch, size_t ts, size_t bs,
                        hipStream_t s) {
     if (!strict_mode()) return;
     const size_t ln = cms * c.n, groups = bs ? batch : 1;

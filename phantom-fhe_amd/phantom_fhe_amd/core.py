@@ -436,6 +436,58 @@ class PhantomContext:
         _lib.check(self._L.pha_plain_inner_product_rescale_batched(self._h, size_Ql, _ptr(plain), _ptr(ct), _ptr(acc), terms, batch,
                                                                    tp, bp, tc, bc, ba, int(scheme), _ptr(dst), chunk, _stream()))
 
+    def bfv_lift_plain_batched(self, size_Ql, plain, count, out, strides=None):
+        """Extension (bfv): out (i) [L][N] = NTT form of the centred lift of plain (i) ([N] words below t) for i < count, the lift
+        being the load of the forward transform; word for word abs_plain_rns_poly + nwt_2d_radix8_forward_inplace.  strides:
+        (plain, out) in 64-bit words; None: dense plain [count][N] and out [count][L][N]."""
+        ps, os_ = (int(v) for v in strides) if strides is not None else (self.n, size_Ql * self.n)
+        _lib.check(self._L.pha_bfv_lift_plain_batched(self._h, size_Ql, _ptr(plain), count, ps, _ptr(out), os_, _stream()))
+
+    def _bfv_plain_sum_strides(self, plain, ct, size_Ql, terms, batch, strides, raw):
+        """As _plain_sum_strides; raw: plain (g, k) is [N] (a bfv plaintext), so dense [batch][terms][N] or, shared by all
+        groups, [terms][N]."""
+        if strides is not None:
+            tp, bp, tc, bc, ba = (int(v) for v in strides)
+            return tp, bp, tc, bc, ba
+        ln = size_Ql * self.n
+        one = (self.n,) if raw else (size_Ql, self.n)
+        pn = self.n if raw else ln
+        if plain is None or ct is None:         # the library refuses the null pointer
+            return pn, terms * pn, 2 * ln, terms * 2 * ln, 2 * ln
+        dense_c = (batch, terms, 2, size_Ql, self.n)
+        if tuple(plain.shape) == (batch, terms) + one:
+            bp = terms * pn
+        elif tuple(plain.shape) == (terms,) + one:
+            bp = 0
+        else:
+            raise ValueError("plain must be [batch][terms]%s or, shared by all groups, [terms]%s (or pass strides)"
+                             % (("[N]", "[N]") if raw else ("[L][N]", "[L][N]")))
+        if tuple(ct.shape) == dense_c:
+            bc = terms * 2 * ln
+        elif tuple(ct.shape) == dense_c[1:]:
+            bc = 0
+        else:
+            raise ValueError("ct must be [batch][terms][2][L][N] or, shared by all groups, [terms][2][L][N] (or pass strides)")
+        return pn, bp, 2 * ln, bc, 2 * ln
+
+    def bfv_multiply_plain_sum_batched(self, size_Ql, plain_ntt, ct, acc, res, terms, batch, strides=None, chunk=0, slab=0):
+        """Extension (bfv): for every group g < batch, res[g] = acc[g] + sum over k < terms of plain[g][k] * ct[g][k] in the ring; ct,
+        acc (may be None) and res [batch][2][L][N] in coefficient form, plain (g, k) [L][N] as bfv_lift_plain_batched writes it.
+        One forward transform per term, one inverse per sum; word for word the loop of bfv_multiply_plain and add_rns_poly.
+        strides: see _plain_sum_strides; `chunk` groups per inverse transform and `slab` terms per sum launch (0: the library's
+        defaults) size the work buffer and change no bit."""
+        tp, bp, tc, bc, ba = self._bfv_plain_sum_strides(plain_ntt, ct, size_Ql, terms, batch, strides, False)
+        _lib.check(self._L.pha_bfv_multiply_plain_sum_batched(self._h, size_Ql, _ptr(plain_ntt), _ptr(ct), _ptr(acc), _ptr(res), terms,
+                                                              batch, tp, bp, tc, bc, ba, chunk, slab, _stream()))
+
+    def bfv_plain_inner_product_batched(self, size_Ql, plain, ct, acc, res, terms, batch, strides=None, chunk=0, slab=0):
+        """Extension (bfv): bfv_multiply_plain_sum_batched on RAW plaintexts, plain (g, k) = [N] words below t (what a bfv
+        PhantomPlaintext holds), lifted and transformed per slab; bit-identical to bfv_lift_plain_batched followed by
+        bfv_multiply_plain_sum_batched."""
+        tp, bp, tc, bc, ba = self._bfv_plain_sum_strides(plain, ct, size_Ql, terms, batch, strides, True)
+        _lib.check(self._L.pha_bfv_plain_inner_product_batched(self._h, size_Ql, _ptr(plain), _ptr(ct), _ptr(acc), _ptr(res), terms,
+                                                               batch, tp, bp, tc, bc, ba, chunk, slab, _stream()))
+
     def bfv_multiply_behz(self, ct1, ct2, dst):
         """bfv_multiply_behz (src/evaluate.cu:447-548): [2][Q][N] x [2][Q][N] -> [3][Q][N], coefficient form."""
         _lib.check(self._L.pha_bfv_multiply_behz(self._h, _ptr(ct1), _ptr(ct2), _ptr(dst), _stream()))

@@ -63,6 +63,9 @@ _SIGS = {
     "pha_inner_product_relin_mod_switch_batched": [vp, sz, vp, vp, sz, sz, sz, sz, sz, sz, vp, vp, sz, vp],
     "pha_multiply_plain_sum_batched": [vp, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, sz, sz, vp],
     "pha_plain_inner_product_rescale_batched": [vp, sz, vp, vp, vp, sz, sz, sz, sz, sz, sz, sz, C.c_int, vp, sz, vp],
+    "pha_bfv_lift_plain_batched": [vp, sz, vp, sz, sz, vp, sz, vp],
+    "pha_bfv_multiply_plain_sum_batched": [vp, sz, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, sz, sz, sz, vp],
+    "pha_bfv_plain_inner_product_batched": [vp, sz, vp, vp, vp, vp, sz, sz, sz, sz, sz, sz, sz, sz, sz, vp],
     "pha_bfv_multiply_behz": [vp, vp, vp, vp, vp],
     "pha_bfv_multiply_hps": [vp, vp, vp, vp, vp],
     "pha_bfv_multiply_hps_overq": [vp, vp, vp, vp, vp],
