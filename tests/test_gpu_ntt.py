@@ -366,7 +366,11 @@ def test_batched_forward_with_resident_twiddles_at_2_16(batch, gpu):
     """r04: plain forward launches of >= 8 polynomials at N = 2^16 take the twiddle-resident contiguous pass (ntt_cpass_zloop_kernel:
     the FP64 limbs walk `zper` polynomials per workgroup, the integer limbs run one (tile, polynomial) per workgroup at the head of
     the same grid).  The C3 chain mixes both back ends (limb 0 is a 60-bit prime, limbs 1..44 are 50-bit); every polynomial against
-    the oracle, odd batch sizes included, plus a limb range that starts inside the chain."""
+    the oracle, odd batch sizes included.  The seven-limb sub-case at the end is NOT that kernel: 64 tiles x 7 limbs x
+    2 wavefronts = 896 wavefronts per polynomial, times at most four groups of polynomials (B = 16) = 3584, stays below the kernel's
+    minimum of 4096, so limbs [0, 7) run the plain pass of the 64 x 1024 plan with the batched strides at all three batch sizes
+    (kernel trace: profiles/ntt_plan_switch_kernels.md).  The resident-twiddle kernel on limb ranges that start inside a chain, guard
+    limbs and other chains: tests/test_gpu_ntt_plans.py."""
     import phantom_fhe_amd as P
     name = "c3_ckks16"
     log_n, primes, size_p = primes_of(name)
@@ -381,7 +385,7 @@ def test_batched_forward_with_resident_twiddles_at_2_16(batch, gpu):
         assert np.array_equal(got[z], oc.nwt_forward(x[z], L, 0)), z
     ctx.nwt_2d_radix8_backward_inplace_batched(d, L, 0, batch, L * n)
     assert np.array_equal(P.to_host(d), x)
-    # limbs [0, 7) only (one integer limb + six FP64 limbs), the other limbs must stay untouched
+    # limbs [0, 7) only (one integer limb + six FP64 limbs; the plain pass, see above), the other limbs must stay untouched
     d = P.to_device(x, gpu)
     ctx.nwt_2d_radix8_forward_inplace_batched(d, 7, 0, batch, L * n)
     got = P.to_host(d)

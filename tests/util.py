@@ -41,6 +41,23 @@ BETA_GT4_LEVELS = {
 }
 
 
+# NTT plan-switch chains (tests/test_gpu_ntt_plans.py).  Both back ends side by side: primes of 51 bits and more run the integer
+# butterflies, smaller ones the FP64 ones -- the plain ones at 48..50 bits, the light forward ones below 2^47, the light inverse
+# ones below 2^42.  The order puts the integer limbs in the middle and at the end of every 12 limbs, never at the start.
+MIXED_BITS = [50, 48, 47, 60, 46, 43, 42, 41, 40, 36, 30, 55]
+
+
+def chain_bits(count, pattern=MIXED_BITS):
+    """The first `count` prime sizes of `pattern` repeated."""
+    return [pattern[i % len(pattern)] for i in range(count)]
+
+
+@functools.lru_cache(maxsize=None)
+def chain_primes(log_n, bits):
+    """Distinct NTT primes of the sizes `bits` (a tuple) at N = 2^log_n, in that order."""
+    return tuple(int(x) for x in O.coeff_modulus_create(1 << log_n, list(bits)))
+
+
 @functools.lru_cache(maxsize=None)
 def primes_of(name):
     log_n, bits, size_p = CONFIGS[name]
