@@ -56,8 +56,8 @@ const char *pha_last_error(void);
  * pha_set_strict(on): strict mode on / off for the process, returns the previous state.  Default: on iff PHA_STRICT=1 was in the
  *   environment when the library was first used.  In strict mode the dyadic, tensor, mod-up / inner-product / mod-down, key-switch,
  *   hoisting and BFV multiply entries check ct / c2 / t_mod_up / keys / weights / ct1 and ct2 before they compute (one
- *   synchronising pass per operand; among them pha_keyswitch_mod_switch, pha_keyswitch_mod_switch_batched and
- *   pha_inner_product_relin_mod_switch_batched) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
+ *   synchronising pass per operand; among them pha_keyswitch_mod_switch, pha_keyswitch_mod_switch_batched,
+ *   pha_inner_product_relin_mod_switch_batched, pha_hoisting_batched and pha_hoisting_weighted_batched) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
 int pha_check_canonical(pha_context_t ctx, const uint64_t *data, size_t coeff_modulus_size, size_t start_modulus_idx,
                         size_t size_P_tail, size_t polys, size_t poly_stride, uint64_t *bad_words, void *stream);
 int pha_check_canonical_keys(pha_context_t ctx, size_t size_Ql, const uint64_t *const *keys, size_t n_keys, uint64_t *bad_words,
@@ -439,6 +439,21 @@ int pha_hoisting_weighted_bsgs_blocks(pha_context_t ctx, size_t size_Ql, const u
                                       size_t n_baby, const uint64_t *const *const *baby_glk, const uint32_t *giant_elts, size_t n_giant,
                                       const uint64_t *const *const *giant_glk, const uint64_t *const *weights, uint64_t *out, int scheme,
                                       void *stream);
+/* Hoisted rotations of a BATCH of ciphertexts that share the Galois keys (and, in the weighted form, the plaintext weights): one
+ * encrypted layer or matrix block applied to `batch` encrypted inputs.  ct and out are [batch][2][Ql][N]; galois_elts, glk and
+ * weights are what pha_hoisting / pha_hoisting_weighted take (HOST arrays of device tables and buffers) and serve every ciphertext.
+ * out[b] is word for word what the single entry writes into a copy of ct[b]: sum_e rotate_e(ct[b]), resp.
+ * sum_e w_e (.) rotate_e(ct[b]).  Schemes as the single entries (plain: ckks / bgv / bfv; weighted: ckks / bgv).
+ * ct is only read; out may be exactly ct (in place), any other overlap is refused.  `chunk` ciphertexts go through one set of
+ * launches -- one mod-up of beta * chunk digits, the gather + inner-product launches, which read each key limb (permutation entry,
+ * weight) once per group of up to 4 ciphertexts, one mod-down of 2 * chunk polynomials -- and size the scratch; 0 = 8; capped by
+ * batch and by the grid limits (beta * chunk, 2 * chunk <= 65535).  Every chunk size gives the same words; a chunk of one
+ * ciphertext runs the launches of the single entry.  batch = 0 does nothing. */
+int pha_hoisting_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t batch, const uint32_t *galois_elts, size_t n_elts,
+                         const uint64_t *const *const *glk, int scheme, uint64_t *out, size_t chunk, void *stream);
+int pha_hoisting_weighted_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t batch, const uint32_t *galois_elts,
+                                  size_t n_elts, const uint64_t *const *const *glk, const uint64_t *const *weights, int scheme,
+                                  uint64_t *out, size_t chunk, void *stream);
 /* PhantomSecretKey::generate_one_kswitch_key (src/secretkey.cu:297-341 with encrypt_zero_symmetric :232-295),
  * arithmetic part; the randomness comes from the caller because the PRNG (sample_uniform_poly /
  * sample_error_poly, src/prng.cu) is outside the accelerated path.  All buffers on the device:

@@ -1,10 +1,12 @@
 // pha_hoist.hip -- hoisted rotations on gfx950: one mod-up shared by many Galois elements (pha_hoisting), the plaintext-weighted
-// form (pha_hoisting_weighted) and its baby-step / giant-step forms (pha_hoisting_weighted_bsgs, ..._blocks).
+// form (pha_hoisting_weighted), its baby-step / giant-step forms (pha_hoisting_weighted_bsgs, ..._blocks), and both hoisted forms for
+// a batch of ciphertexts that share the keys (pha_hoisting_batched, pha_hoisting_weighted_batched).
 //
 // Reference: src/evaluate.cu:1670-1866.  The mod-up, the mod-down and the Galois launchers these entries call live in pha_rns.hip
 // (declared in pha_internal.h).
 #include "../../include/phantom_amd.h"
 #include "pha_internal.h"
+#include "pha_hoist_batched.h"
 #include <algorithm>
 
 namespace pha {
@@ -406,6 +408,217 @@ static void launch_hoist_inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_m
     }
 }
 
+// ---- hoisted rotations of a batch of ciphertexts that share keys, tables and weights (pha_hoisting_batched,
+//      pha_hoisting_weighted_batched).  The thread program is pha_hoist_batched.h (replayed on the CPU by tests/emu): one thread
+//      owns two adjacent coefficients of one limb for up to CB ciphertexts, blockIdx.z = group of CB ciphertexts of the chunk. ----
+template <int BETA, int CB, bool WEIGHTED>
+__global__ __launch_bounds__(256) void hoist_inner_prod_batched_kernel(const HoistBArgs k) {
+    hoist_batched_thread<BETA, CB, WEIGHTED>(k, blockIdx.x * 256 + threadIdx.x, blockIdx.y, blockIdx.z);
+}
+
+// The c0 / (c0, c1) kernels' batched twins: a thread owns one coefficient of one limb for up to kHoistCGroup ciphertexts (blockIdx.z
+// carries the group), so a permutation entry and a weight are read once per group.  Ciphertext b's polynomials are at src + b *
+// src_stride and dst + b * dst_stride (+ poly_stride for c1).
+constexpr uint32_t kHoistCGroup = 4;
+
+// dst[b][0][limb][k] = sum_e src[b][limb][perm_e[k]] mod q, dst[b][1] = 0
+__global__ __launch_bounds__(256) void hoist_c0_batched_kernel(u64 *dst, size_t dst_stride, const u64 *src, size_t src_stride,
+                                                               const uint32_t *const *tables, uint32_t n_elts, const DModulus *mod,
+                                                               uint32_t n, uint32_t n_ct, size_t poly_stride) {
+    const uint32_t limb = blockIdx.y, first = blockIdx.z * kHoistCGroup;
+    const uint32_t cnt = n_ct - first < kHoistCGroup ? n_ct - first : kHoistCGroup;   // (uniform)
+    const u64 q = mod[limb].value;
+    const uint32_t coeff = blockIdx.x * 256 + threadIdx.x;
+    const u64 *row = src + (size_t)first * src_stride + (size_t)limb * n;
+    u64 acc[kHoistCGroup] = {};
+    for (uint32_t e = 0; e < n_elts; e++) {
+        const uint32_t from = tables[e][coeff];
+#pragma unroll
+        for (uint32_t j = 0; j < kHoistCGroup; j++)
+            if (j < cnt) acc[j] = add_mod(acc[j], row[(size_t)j * src_stride + from], q);
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kHoistCGroup; j++)
+        if (j < cnt) {
+            u64 *d = dst + (size_t)(first + j) * dst_stride + (size_t)limb * n + coeff;
+            d[0] = acc[j];
+            d[poly_stride] = 0;
+        }
+}
+
+// dst[b][p][limb][k] = sum_e w_e[limb][k] * src[b][p][limb][perm_e[k]] mod q.  blockIdx.z = 2 * group + p; elements and fold as
+// hoist_weighted_c_kernel.
+__global__ __launch_bounds__(256) void hoist_weighted_c_batched_kernel(u64 *dst, size_t dst_stride, const u64 *src, size_t src_stride,
+                                                                       const uint32_t *const *tables, const u64 *const *weights,
+                                                                       uint32_t n_elts, uint32_t first_c1, const DModulus *mod,
+                                                                       uint32_t n, uint32_t n_ct, size_t poly_stride) {
+    const uint32_t limb = blockIdx.y, p = blockIdx.z & 1, first = (blockIdx.z >> 1) * kHoistCGroup;
+    const uint32_t cnt = n_ct - first < kHoistCGroup ? n_ct - first : kHoistCGroup;   // (uniform)
+    const DModulus m = mod[limb];
+    const uint32_t coeff = blockIdx.x * 256 + threadIdx.x;
+    const size_t id = (size_t)limb * n + coeff;
+    const u64 *row = src + (size_t)first * src_stride + p * poly_stride + (size_t)limb * n;
+    u64 lo[kHoistCGroup] = {}, hi[kHoistCGroup] = {};
+    uint32_t terms = 0;
+    for (uint32_t e = p ? first_c1 : 0; e < n_elts; e++) {
+        const uint32_t from = tables[e][coeff];
+        const u64 w = weights[e][id];
+#pragma unroll
+        for (uint32_t j = 0; j < kHoistCGroup; j++)
+            if (j < cnt) mac128(row[(size_t)j * src_stride + from], w, lo[j], hi[j]);
+        if (++terms == 48) {           // products of two 61-bit residues: 48 * 2^122 stays below 2^128
+#pragma unroll
+            for (uint32_t j = 0; j < kHoistCGroup; j++) {
+                lo[j] = barrett128(lo[j], hi[j], m);
+                hi[j] = 0;
+            }
+            terms = 1;
+        }
+    }
+#pragma unroll
+    for (uint32_t j = 0; j < kHoistCGroup; j++)
+        if (j < cnt) dst[(size_t)(first + j) * dst_stride + p * poly_stride + id] = barrett128(lo[j], hi[j], m);
+}
+
+// The gather + inner products of `n_ct` >= 2 ciphertexts (t_mod_up [n_ct][beta][QlP][N] -> cx [n_ct][2][QlP][N]), `per_call` Galois
+// elements per launch as launch_hoist_inner_prod.
+static void launch_hoist_inner_prod_batched(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const u64 *const *const *d_keys,
+                                            const uint32_t *const *d_tabs, const u64 *const *d_w, size_t n_elts, size_t per_call,
+                                            size_t n_ct, hipStream_t s) {
+    for (size_t e0 = 0; e0 < n_elts; e0 += per_call) {
+        HoistBArgs k{};
+        k.cx = cx; k.t_mod_up = t_mod_up; k.keys = d_keys + e0; k.tables = d_tabs + e0; k.weights = d_w ? d_w + e0 : nullptr;
+        k.mod = c.d_mod.p; k.qlp_prime = t.d_qlp_prime.p; k.n = (uint32_t)c.n; k.beta = t.beta;
+        k.n_elts = (uint32_t)std::min(per_call, n_elts - e0); k.accumulate = e0 ? 1 : 0; k.n_ct = (uint32_t)n_ct;
+        k.qlp_n = (size_t)t.size_qlp * c.n; k.qp_n = (size_t)c.size_qp * c.n;
+        with_beta<0>(t.beta, [&](auto B) {
+            constexpr int BETA = decltype(B)::value;
+            constexpr int CBP = hoist_batched_cb(BETA, false), CBW = hoist_batched_cb(BETA, true);
+            const unsigned cb = d_w ? CBW : CBP;
+            const dim3 grid((unsigned)(c.n / 512), t.size_qlp, (unsigned)((n_ct + cb - 1) / cb)), block(256);
+            if (d_w) hipLaunchKernelGGL((hoist_inner_prod_batched_kernel<BETA, CBW, true>), grid, block, 0, s, k);
+            else hipLaunchKernelGGL((hoist_inner_prod_batched_kernel<BETA, CBP, false>), grid, block, 0, s, k);
+        });
+        check_launch();
+    }
+}
+
+// Driver of both batched entries (weights == null: the plain form).  Per chunk of cb ciphertexts: one mod-up of beta * cb digits (the
+// digits' own limbs copied into t_mod_up -- the gather reads them through the permutation, so modup's own_in_place is off here whatever
+// the key switch's own_in_place_ok() says), the inner-product launches, the c0 / (c0, c1) sums into out, one mod-down of 2 * cb
+// polynomials added to them.  A chunk of one ciphertext runs the single entries' launches.
+// Scratch: KsScratch of `chunk` ciphertexts | copy of the chunk's c0 [chunk][Ql][N] (plain; in place or bfv) resp. (c0, c1)
+// [chunk][2][Ql][N] (weighted, in place) | pointer tables.
+static void hoist_batched_core(Context &c, size_t size_Ql, const u64 *ct, size_t batch, const uint32_t *galois_elts, size_t n_elts,
+                               const uint64_t *const *const *glk, const uint64_t *const *weights, int scheme, u64 *out, size_t chunk,
+                               void *stream) {
+    const bool weighted = weights != nullptr;
+    const bool ntt_dom = ntt_domain_scheme(scheme);
+    check_level(c, size_Ql, true);
+    Tool &t = c.tool((uint32_t)size_Ql);
+    hipStream_t s = as_stream(stream);
+    const size_t n = c.n, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n, ct_words = 2 * ql_n;
+    const bool in_place = out == ct;
+    if (!in_place && overlaps(out, batch * ct_words, ct, batch * ct_words))
+        throw std::invalid_argument("out must be ct itself (in place) or must not overlap it");
+    // every refusal before the first launch
+    for (size_t e = 0; e < n_elts; e++) {
+        check_galois_elt(c, galois_elts[e]);
+        if (weighted && !weights[e]) throw std::invalid_argument("null weight");
+    }
+    for (size_t e = 0; e < n_elts; e++)
+        if (!glk[e] && !(weighted && galois_elts[e] == 1)) throw std::logic_error("Galois key not present in hoisting");
+    if (strict_mode()) {
+        strict_operand(c, "hoisting ct", ct, rows_plain(0, size_Ql), (uint32_t)(2 * batch), ql_n, s);
+        for (size_t e = 0; e < n_elts; e++) {
+            if (glk[e]) strict_keys(c, "hoisting Galois key", glk[e], t.beta, (uint32_t)size_Ql, s);
+            if (weighted) strict_operand(c, "hoisting weight", weights[e], rows_qlp(t.size_ql, c.size_q, c.size_p), 1, 0, s);
+        }
+    }
+    if (!chunk) chunk = 8;
+    chunk = std::min(std::min(chunk, batch), (size_t)65535 / std::max<size_t>(2, t.beta));
+    // the elements in launch order: as given (plain); key-switched ones first, main-diagonal ones (element 1, no key) last (weighted)
+    std::vector<const void *> tabs, keys, w_all;
+    size_t n_ks = 0;
+    for (int pass = 0; pass < (weighted ? 2 : 1); pass++)
+        for (size_t e = 0; e < n_elts; e++) {
+            const bool keyed = !weighted || galois_elts[e] != 1;
+            if (weighted && keyed == (pass == 1)) continue;
+            tabs.push_back(c.galois_table(galois_elts[e]));
+            if (weighted) w_all.push_back(weights[e]);
+            if (keyed) {
+                keys.push_back(glk[e]);
+                n_ks++;
+            }
+        }
+    const size_t copy_polys = weighted ? (in_place ? 2 : 0) : ((in_place || !ntt_dom) ? 1 : 0);
+    const size_t ks_words = KsScratch::words(c, t, chunk), ptr_words = 3 * n_elts;
+    u64 *base = c.scratch(stream, ks_words + chunk * copy_polys * ql_n + ptr_words);
+    const KsScratch k(base, c, t, chunk);
+    u64 *cc = base + ks_words, *d_ptrs = cc + chunk * copy_polys * ql_n;
+    PHA_HIP(hipMemcpyAsync(d_ptrs, tabs.data(), n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
+    if (weighted) PHA_HIP(hipMemcpyAsync(d_ptrs + n_elts, w_all.data(), n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
+    if (n_ks) PHA_HIP(hipMemcpyAsync(d_ptrs + 2 * n_elts, keys.data(), n_ks * sizeof(void *), hipMemcpyHostToDevice, s));
+    const uint32_t *const *d_tabs = reinterpret_cast<const uint32_t *const *>(d_ptrs);
+    const u64 *const *d_w = weighted ? reinterpret_cast<const u64 *const *>(d_ptrs + n_elts) : nullptr;
+    const u64 *const *const *d_keys = reinterpret_cast<const u64 *const *const *>(d_ptrs + 2 * n_elts);
+    // plain: acc_capacity / beta elements per launch; weighted: 63, whatever the primes (pha_hoisting_weighted)
+    const size_t per_call = weighted ? 63 : std::max<size_t>(1, acc_capacity(c) / t.beta);
+
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t cb = std::min(chunk, batch - b0);
+        const u64 *in = ct + b0 * ct_words;
+        u64 *o = out + b0 * ct_words;
+        // what the sums over c0 (and c1) read once `o` is being written: the chunk itself, or its copy
+        const u64 *src = in;
+        size_t src_stride = ct_words;
+        if (copy_polys == 2) {
+            PHA_HIP(hipMemcpyAsync(cc, in, cb * ct_words * sizeof(u64), hipMemcpyDeviceToDevice, s));
+            src = cc;
+        } else if (copy_polys == 1) {
+            PHA_HIP(hipMemcpy2DAsync(cc, ql_n * sizeof(u64), in, ct_words * sizeof(u64), ql_n * sizeof(u64), cb, hipMemcpyDeviceToDevice, s));
+            src = cc;
+            src_stride = ql_n;
+        }
+        if (n_ks) {
+            modup(c, t, k.t_mod_up, in + ql_n, scheme, k.tmp, s, (uint32_t)cb, ct_words, nullptr, false);
+            if (cb == 1) launch_hoist_inner_prod(c, t, k.cx, k.t_mod_up, d_keys, d_tabs, d_w, n_ks, per_call, s);
+            else launch_hoist_inner_prod_batched(c, t, k.cx, k.t_mod_up, d_keys, d_tabs, d_w, n_ks, per_call, cb, s);
+        }
+        if (weighted) {
+            if (cb == 1)
+                hipLaunchKernelGGL(hoist_weighted_c_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql, 2), dim3(256), 0, s, o, src, d_tabs,
+                                   d_w, (uint32_t)n_elts, (uint32_t)n_ks, c.d_mod.p, (uint32_t)n, ql_n);
+            else
+                hipLaunchKernelGGL(hoist_weighted_c_batched_kernel,
+                                   dim3((unsigned)(n / 256), (unsigned)size_Ql, (unsigned)(2 * ((cb + kHoistCGroup - 1) / kHoistCGroup))),
+                                   dim3(256), 0, s, o, ct_words, src, src_stride, d_tabs, d_w, (uint32_t)n_elts, (uint32_t)n_ks, c.d_mod.p,
+                                   (uint32_t)n, (uint32_t)cb, ql_n);
+            check_launch();
+        } else if (ntt_dom) {
+            if (cb == 1) {
+                hipLaunchKernelGGL(hoist_c0_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql), dim3(256), 0, s, o, src, d_tabs,
+                                   (uint32_t)n_elts, c.d_mod.p, (uint32_t)n);
+                check_launch();
+                PHA_HIP(hipMemsetAsync(o + ql_n, 0, ql_n * sizeof(u64), s));
+            } else {
+                hipLaunchKernelGGL(hoist_c0_batched_kernel,
+                                   dim3((unsigned)(n / 256), (unsigned)size_Ql, (unsigned)((cb + kHoistCGroup - 1) / kHoistCGroup)), dim3(256),
+                                   0, s, o, ct_words, src, src_stride, d_tabs, (uint32_t)n_elts, c.d_mod.p, (uint32_t)n, (uint32_t)cb, ql_n);
+                check_launch();
+            }
+        } else {
+            // coefficient-domain automorphism (src/galois.cu:20-39) of the chunk's dense c0 copy, one launch per element, and the adds
+            PHA_HIP(hipMemsetAsync(o, 0, cb * ct_words * sizeof(u64), s));
+            for (size_t e = 0; e < n_elts; e++) {
+                launch_galois_coeff(c, k.tmp, cc, galois_elts[e], size_Ql, 0, cb, s);
+                for (size_t b = 0; b < cb; b++) launch_add(c, o + b * ct_words, k.tmp + b * ql_n, o + b * ct_words, size_Ql, 0, s);
+            }
+        }
+        if (n_ks) moddown_from_ntt(c, t, o, ql_n, k.cx, qlp_n, (uint32_t)(2 * cb), scheme, true, k.tmp, s);
+    }
+}
+
 }  // namespace pha
 
 using namespace pha;
@@ -675,6 +888,28 @@ int pha_hoisting_weighted_bsgs_blocks(pha_context_t ctx, size_t size_Ql, const u
     if (overlaps(out, n_blocks * 2 * ql_n, ct, 2 * ql_n)) throw std::invalid_argument("out must not overlap ct");
     bsgs_core(c, c.tool((uint32_t)size_Ql), ct, n_blocks, baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights, out, scheme,
               stream);
+    PHA_API_END
+}
+
+int pha_hoisting_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t batch, const uint32_t *galois_elts, size_t n_elts,
+                         const uint64_t *const *const *glk, int scheme, uint64_t *out, size_t chunk, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    need(ct); need(galois_elts); need(glk); need(out);
+    if (n_elts == 0) throw std::invalid_argument("steps must not be empty");
+    if (batch == 0) return 0;
+    hoist_batched_core(ctx->c, size_Ql, ct, batch, galois_elts, n_elts, glk, nullptr, scheme, out, chunk, stream);
+    PHA_API_END
+}
+
+int pha_hoisting_weighted_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t batch, const uint32_t *galois_elts,
+                                  size_t n_elts, const uint64_t *const *const *glk, const uint64_t *const *weights, int scheme,
+                                  uint64_t *out, size_t chunk, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    need(ct); need(galois_elts); need(glk); need(weights); need(out);
+    if (n_elts == 0) throw std::invalid_argument("steps must not be empty");
+    if (!ntt_domain_scheme(scheme)) throw std::invalid_argument("weighted hoisting takes NTT-form ciphertexts (ckks / bgv)");
+    if (batch == 0) return 0;
+    hoist_batched_core(ctx->c, size_Ql, ct, batch, galois_elts, n_elts, glk, weights, scheme, out, chunk, stream);
     PHA_API_END
 }
 

@@ -635,6 +635,34 @@ class PhantomContext:
         _lib.check(self._L.pha_hoisting_weighted_bsgs_blocks(self._h, size_Ql, _ptr(ct), len(weights), be, len(baby_elts), bk, ge,
                                                              len(giant_elts), gk, ws, _ptr(out), int(scheme), _stream()))
 
+    def hoisting_batched(self, size_Ql, ct, galois_elts, galois_keys, scheme, out=None, chunk=0):
+        """pha_hoisting_batched: out[b] = sum_e rotate_e(ct[b]) for a batch ct [B][2][Ql][N] that shares the Galois keys; every
+        out[b] is word for word what hoisting() makes of ct[b].  out=None allocates, out=ct works in place; `chunk` ciphertexts go
+        through one set of launches (0: the library's default).  Returns out."""
+        if out is None:
+            out = torch.empty_like(ct)
+        if ct.shape[0] == 0:             # (an empty tensor has no device pointer to hand over)
+            return out
+        elts = (C.c_uint32 * len(galois_elts))(*[int(e) for e in galois_elts])
+        tabs = (C.c_void_p * len(galois_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in galois_keys])
+        _lib.check(self._L.pha_hoisting_batched(self._h, size_Ql, _ptr(ct), ct.shape[0], elts, len(galois_elts), tabs, int(scheme),
+                                                _ptr(out), chunk, _stream()))
+        return out
+
+    def hoisting_weighted_batched(self, size_Ql, ct, galois_elts, galois_keys, weights, scheme, out=None, chunk=0):
+        """pha_hoisting_weighted_batched: out[b] = sum_e weights[e] (.) rotate_e(ct[b]) for a batch ct [B][2][Ql][N] that shares the
+        Galois keys and the weights (as hoisting_weighted takes them); out, chunk and the result as hoisting_batched."""
+        if out is None:
+            out = torch.empty_like(ct)
+        if ct.shape[0] == 0:             # (an empty tensor has no device pointer to hand over)
+            return out
+        elts = (C.c_uint32 * len(galois_elts))(*[int(e) for e in galois_elts])
+        tabs = (C.c_void_p * len(galois_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in galois_keys])
+        ws = (C.c_void_p * len(weights))(*[_ptr(w) for w in weights])
+        _lib.check(self._L.pha_hoisting_weighted_batched(self._h, size_Ql, _ptr(ct), ct.shape[0], elts, len(galois_elts), tabs, ws,
+                                                         int(scheme), _ptr(out), chunk, _stream()))
+        return out
+
     def divide_and_round_q_last_ntt(self, size_Ql, src, cipher_size, dst):
         _lib.check(self._L.pha_divide_and_round_q_last_ntt(self._h, size_Ql, _ptr(src), cipher_size, _ptr(dst),
                                                            _stream()))

@@ -75,6 +75,13 @@ def diag_matvec(ctx, size_Ql, ct, galois_elts, galois_keys, diagonals, scheme):
     return out
 
 
+def diag_matvec_batch(ctx, size_Ql, cts, galois_elts, galois_keys, diagonals, scheme, chunk=0):
+    """The same block applied to a batch of encrypted vectors cts [B][2][Ql][N] (pha_hoisting_weighted_batched): the Galois keys and
+    the diagonals are read once per group of ciphertexts instead of once per vector.  `chunk` vectors go through one set of
+    launches (0: the library's default).  Returns [B][2][Ql][N]; every result equals diag_matvec of that vector."""
+    return ctx.hoisting_weighted_batched(size_Ql, cts, galois_elts, galois_keys, diagonals, scheme, chunk=chunk)
+
+
 def diag_matvec_bsgs(ctx, size_Ql, ct, baby_elts, baby_keys, giant_elts, giant_keys, diagonals, scheme):
     """The same block in baby-step / giant-step form (pha_hoisting_weighted_bsgs): with d = n_giant * n_baby diagonals,
     out = sum_i rot_{giant_elts[i]}(sum_j diagonals[i][j] (.) rot_{baby_elts[j]}(ct)) from n_baby + n_giant - 2 Galois keys instead of
