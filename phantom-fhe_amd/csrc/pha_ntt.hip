@@ -38,6 +38,16 @@ namespace pha {
 #ifndef PHA_X_VARIANT
 #define PHA_X_VARIANT (1 | 32 | 64 | 2048 | 4096)
 #endif
+// Block order of the strided pass of a launch pair whose contiguous pass is ntt_zloop_kernel (PassOrder, pha_ntt_core.h; measured in
+// profiles/ntt_pass_order.md).  A compile-time choice, no run-time knob: 0 = the plain grid (tile, limb, polynomial), poly-major;
+// 1 = the reverse of the contiguous pass's order; 2 = 1, and a launch whose buffer is larger than the last-level cache goes as two
+// launch pairs, one per half of its limbs.
+#ifndef PHA_NTT_PASS_ORDER
+#define PHA_NTT_PASS_ORDER 1
+#endif
+#ifndef PHA_NTT_ORDER_INT_HEAD
+#define PHA_NTT_ORDER_INT_HEAD 1   // 1: the integer limbs stay at the head of the strided launch (pass_order_reverse); 0: the exact reverse, integer limbs last
+#endif
 constexpr int kDefaultVariant = PHA_X_VARIANT;   // 8 coefficients per thread, one-wavefront contiguous pass, on-the-fly twiddles for >= 1024 tiles of fewer than 8 polynomials, polynomial-fastest block order in large batched contiguous passes, 2^16 = 64 x 1024   // 8 coefficients per thread, one-wavefront contiguous pass, on-the-fly twiddles for >= 1024 tiles of fewer than 8 polynomials, polynomial-fastest block order in large batched contiguous passes
 #if defined(PHA_EXPERIMENTS)
 std::atomic<int> g_ntt_variant{kDefaultVariant};
@@ -227,15 +237,8 @@ __device__ __forceinline__ void exec_pass(const PassArgs &a, u64 *lds, int tid) 
 // polynomials -- 26 loads, their address arithmetic and their waits leave the loop, which is what an issue-bound pass is short of
 // (720 limbs at N = 2^16: 300 -> 274 us per step with 4 polynomials per workgroup).  Integer-back-end limbs (60-bit primes: 16-byte twiddle pairs would need 100+ registers) take the plain pass, one
 // (tile, polynomial) per workgroup, at the head of the same grid.
-// Work map of one launch: a 1-D grid, the integer-back-end limbs FIRST (their tiles are the longest: one polynomial per workgroup, so that
-// they run side by side from the start), then the FP64 limbs with zper polynomials per workgroup.
-struct ZloopMap {
-    uint32_t n_int, n_fp;      // limbs of each kind in the selection
-    uint32_t zper;             // polynomials per FP64 workgroup
-    uint32_t tiles;            // tiles per limb
-    uint32_t int_blocks;       // n_int * tiles * batch
-    uint8_t limb[128];         // selection-relative limb indices: the n_int integer limbs, then the n_fp FP64 limbs
-};
+// Work map of one launch: ZloopMap (pha_ntt_core.h): a 1-D grid, the integer-back-end limbs FIRST (their tiles are the longest: one
+// polynomial per workgroup, so that they run side by side from the start), then the FP64 limbs with zper polynomials per workgroup.
 template <class C, bool FWD, int EPI, bool FOLD>
 __global__ __launch_bounds__(C::THREADS) void ntt_zloop_kernel(const NttKArgs k, const ZloopMap m) {
     static_assert(!C::WHOLE, "the batched form exists for the passes of the two-pass plans");
@@ -324,7 +327,7 @@ template <class C> constexpr int x_occ() { return C::WHOLE ? 1 : C::STRIDED ? (C
 #define PHA_PASS_BOUNDS __launch_bounds__(C::THREADS)
 #endif
 template <class C, bool FWD, int EPI, bool FOLD, int HOIST, int PRO = PRO_NONE>
-__global__ PHA_PASS_BOUNDS PHA_PASS_ATTR void ntt_pass_kernel(const NttKArgs k) {
+__global__ PHA_PASS_BOUNDS PHA_PASS_ATTR void ntt_pass_kernel(const NttKArgs k, const PassOrder o) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     u64 *lds = reinterpret_cast<u64 *>(smem);
 
@@ -340,6 +343,11 @@ __global__ PHA_PASS_BOUNDS PHA_PASS_ATTR void ntt_pass_kernel(const NttKArgs k) 
         tile = group % k.zfast_tiles;
         y = group / k.zfast_tiles;
     }
+#if PHA_NTT_PASS_ORDER
+    else if (o.tiles) {   // (uniform) the strided pass of a pair whose contiguous pass is ntt_zloop_kernel: the reverse of that kernel's order
+        if (!pass_order_decode(o, k.batch, blockIdx.x, blockIdx.y, blockIdx.z, y, z, tile)) return;
+    }
+#endif
     const uint32_t twr = k.sel.start + y;  // limb in the buffer (uniform)
     if (limb_excluded(k, twr, z)) return;
     PassArgs a;
@@ -505,7 +513,7 @@ __global__ __launch_bounds__(512, PHA_FUSED_MIN_WAVES) void ntt_fused_kernel(con
 #endif  // PHA_EXPERIMENTS
 
 template <class C, bool FWD, int EPI, bool FOLD, int PRO = PRO_NONE>
-static void launch_pass(const NttKArgs &k, hipStream_t s) {
+static void launch_pass(const NttKArgs &k, hipStream_t s, const PassOrder *order = nullptr) {
     const size_t n = (size_t)1 << k.log_n;
     const size_t lds_bytes = (size_t)C::LDS_WORDS * sizeof(u64);
     const unsigned tiles_per_limb = (unsigned)(n >> C::LOGTILE);
@@ -522,6 +530,11 @@ static void launch_pass(const NttKArgs &k, hipStream_t s) {
 #endif
         const unsigned groups = tiles_per_limb * k.sel.count;
         grid = dim3(((groups + kk.zfast_run - 1) / kk.zfast_run) * kk.zfast_run * k.batch, 1, 1);
+    }
+    PassOrder o{};
+    if (order && !kk.zfast_tiles) {   // the caller's block order (the strided pass of a pair with ntt_zloop_kernel)
+        o = *order;
+        pass_order_grid(o, k.batch, grid.x, grid.y, grid.z);
     }
     // (requesting all rounds' twiddles up front, HOIST 1, was measured again in r02 for the small launches of mod-down and
     //  rescale: no gain at any size)
@@ -544,9 +557,9 @@ static void launch_pass(const NttKArgs &k, hipStream_t s) {
     static const size_t pad_s = std::getenv("PHA_X_LDS_S") ? (size_t)std::atol(std::getenv("PHA_X_LDS_S")) : 0;
     static const size_t pad_c = std::getenv("PHA_X_LDS_C") ? (size_t)std::atol(std::getenv("PHA_X_LDS_C")) : 0;
     const size_t lds_x = lds_bytes + (C::STRIDED ? pad_s : pad_c);
-    hipLaunchKernelGGL((ntt_pass_kernel<C, FWD, EPI, FOLD, HX, PRO>), grid, dim3(C::THREADS), lds_x, s, kk);
+    hipLaunchKernelGGL((ntt_pass_kernel<C, FWD, EPI, FOLD, HX, PRO>), grid, dim3(C::THREADS), lds_x, s, kk, o);
 #else
-    hipLaunchKernelGGL((ntt_pass_kernel<C, FWD, EPI, FOLD, HX, PRO>), grid, dim3(C::THREADS), lds_bytes, s, kk);
+    hipLaunchKernelGGL((ntt_pass_kernel<C, FWD, EPI, FOLD, HX, PRO>), grid, dim3(C::THREADS), lds_bytes, s, kk, o);
 #endif
     check_launch();
 }
@@ -592,10 +605,10 @@ static bool launch_fused(Context &c, const NttKArgs &kA_in, const NttKArgs &kB_i
 
 // the inverse transform's last pass (the strided one, or the whole transform) with the epilogue the caller asked for
 template <class P>
-static void launch_inverse_last(const NttKArgs &k, int epi, hipStream_t s) {
-    if (epi == EPI_INV_SCALE) launch_pass<P, false, EPI_INV_SCALE, true>(k, s);
-    else if (epi == EPI_INV_CANON_ADD) launch_pass<P, false, EPI_INV_CANON_ADD, true>(k, s);
-    else launch_pass<P, false, EPI_INV_CANON, true>(k, s);
+static void launch_inverse_last(const NttKArgs &k, int epi, hipStream_t s, const PassOrder *order = nullptr) {
+    if (epi == EPI_INV_SCALE) launch_pass<P, false, EPI_INV_SCALE, true>(k, s, order);
+    else if (epi == EPI_INV_CANON_ADD) launch_pass<P, false, EPI_INV_CANON_ADD, true>(k, s, order);
+    else launch_pass<P, false, EPI_INV_CANON, true>(k, s, order);
 }
 
 // N = 4096 / 8192 as ONE pass (the transform fits a tile): T1 = 1, T2 = N
@@ -624,45 +637,54 @@ static void inverse_whole(NttKArgs k, int epi, hipStream_t s) {
 #ifndef PHA_ZLOOP_MIN_BATCH
 #define PHA_ZLOOP_MIN_BATCH 8
 #endif
-template <class C, bool FWD, int EPI, bool FOLD>
-static bool launch_zloop(const NttKArgs &k, hipStream_t s) {
-    if (k.batch < (uint32_t)PHA_ZLOOP_MIN_BATCH || k.pro_src) return false;
+// the launcher rule: does this launch take ntt_zloop_kernel for its contiguous pass, and with which work map
+template <class C>
+static bool plan_zloop(const NttKArgs &k, ZloopMap &m) {
+    if (k.pro_src || k.sel.count > 128) return false;
     const size_t n = (size_t)1 << k.log_n;
     const unsigned tiles_per_limb = (unsigned)(n >> C::LOGTILE);
-    const size_t waves_per_poly = (size_t)tiles_per_limb * k.sel.count * (C::THREADS / 64);
-    // resident wavefront slots at this kernel's register budget (4 per SIMD) x 3 generations
-    const size_t want = (size_t)256 * 4 * 4 * 3;
-    // polynomials per workgroup: the gain saturates at 4-8 (r04 sweep: 4 / 8 / 16 per workgroup -> 274 / 275 / 290 us per 720-limb step),
-    // so at most 8, split evenly over the workgroups of a tile, fewer while the launch would not fill the device three times
-    uint32_t zper = (k.batch + ((k.batch + 7) / 8) - 1) / ((k.batch + 7) / 8);
-    while (zper > 4 && waves_per_poly * ((k.batch + zper - 1) / zper) < want) zper = (zper + 1) / 2;
-    if (waves_per_poly * ((k.batch + zper - 1) / zper) < want / 3) return false;   // too small a launch: the plain pass
+    uint32_t zper = zloop_zper(k.batch, (size_t)tiles_per_limb * k.sel.count, C::THREADS / 64, PHA_ZLOOP_MIN_BATCH);
+    if (!zper) return false;
 #if defined(PHA_X_KNOBS)
     static const unsigned zper_x = std::getenv("PHA_X_ZPER") ? (unsigned)std::atol(std::getenv("PHA_X_ZPER")) : 0u;
     if (zper_x) zper = zper_x;
 #endif
     // which limbs of the selection run on the FP64 back end (the others: runs of consecutive limbs through the plain kernel)
-    auto is_fp = [&](uint32_t y) {
+    uint8_t fp[128];
+    for (uint32_t y = 0; y < k.sel.count; y++) {
         const uint32_t twr = k.sel.start + y, prime = twr >= k.sel.remap_from ? twr + k.sel.remap_add : twr;
-        return k.fpinfo != nullptr && (k.h_primes[prime] >> 50) == 0;
-    };
-    if (k.sel.count > 128) return false;
-    ZloopMap m{};
-    m.zper = zper;
-    m.tiles = tiles_per_limb;
-    for (uint32_t y = 0; y < k.sel.count; y++)
-        if (!is_fp(y)) m.limb[m.n_int++] = (uint8_t)y;
-    for (uint32_t y = 0; y < k.sel.count; y++)
-        if (is_fp(y)) m.limb[m.n_int + m.n_fp++] = (uint8_t)y;
-    if (m.n_fp * 2 < k.sel.count) return false;   // mostly wide primes: the plain pass for everything
-    m.int_blocks = m.n_int * tiles_per_limb * k.batch;
+        fp[y] = k.fpinfo != nullptr && (k.h_primes[prime] >> 50) == 0;
+    }
+    return zloop_fill(m, k.sel.count, fp, k.batch, zper, tiles_per_limb);
+}
+template <class C, bool FWD, int EPI, bool FOLD>
+static void launch_zloop(const NttKArgs &k, const ZloopMap &m, hipStream_t s) {
     NttKArgs kk = k;
     kk.zfast_tiles = 0;
-    const unsigned blocks = m.int_blocks + m.n_fp * tiles_per_limb * ((k.batch + zper - 1) / zper);
     const size_t lds_bytes = (size_t)C::LDS_WORDS * sizeof(u64);
-    hipLaunchKernelGGL((ntt_zloop_kernel<C, FWD, EPI, FOLD>), dim3(blocks), dim3(C::THREADS), lds_bytes, s, kk, m);
+    hipLaunchKernelGGL((ntt_zloop_kernel<C, FWD, EPI, FOLD>), dim3(zloop_blocks(m, k.batch)), dim3(C::THREADS), lds_bytes, s, kk, m);
     check_launch();
-    return true;
+}
+template <class C>
+static void launch_zloop_forward(const NttKArgs &k, const ZloopMap &m, int epi, hipStream_t s) {
+    if (epi == EPI_FWD_MODDOWN) launch_zloop<C, true, EPI_FWD_MODDOWN, false>(k, m, s);
+    else if (epi == EPI_FWD_MODDOWN_ADD) launch_zloop<C, true, EPI_FWD_MODDOWN_ADD, false>(k, m, s);
+    else if (epi == EPI_FWD_KSRESCALE) launch_zloop<C, true, EPI_FWD_KSRESCALE, false>(k, m, s);
+    else launch_zloop<C, true, EPI_FWD_CANON, false>(k, m, s);
+}
+
+constexpr size_t kLastLevelCacheBytes = (size_t)256 << 20;   // Infinity Cache of the MI355X
+// limbs [lo, lo + cnt) of the selection of k
+static NttKArgs limb_range(const NttKArgs &k, uint32_t lo, uint32_t cnt) {
+    NttKArgs h = k;
+    h.sel.start = k.sel.start + lo;
+    h.sel.count = cnt;
+    return h;
+}
+// how many limb ranges the pair is issued in (order 2: two, for a selection whose words exceed the cache)
+static uint32_t order_parts(const NttKArgs &k) {
+    const size_t bytes = ((size_t)k.sel.count * k.batch << k.log_n) * sizeof(u64);
+    return PHA_NTT_PASS_ORDER == 2 && k.sel.count >= 2 && bytes > kLastLevelCacheBytes ? 2u : 1u;
 }
 
 #ifndef PHA_IP_PLAN
@@ -702,21 +724,36 @@ static void forward_impl(NttKArgs k, int epi, hipStream_t s, Context *fused = nu
 #endif
     // (the strided pass in the batched form measured SLOWER -- 720 limbs 282 -> 302 us: its twiddles are few and shared by a tile's columns,
     //  and a 512-thread workgroup that walks several polynomials keeps its barrier schedule for all of them)
-    if (k.first_pass_done) {
-    } else if (k1.pro_t) launch_pass<P1, true, EPI_NONE, false, PRO_LIFT>(k1, s);   // (a plaintext's words lifted as they are loaded)
-    else launch_pass<P1, true, EPI_NONE, false>(k1, s);
-    if (k.first_pass_only) return;
-    // pass 1 ran in -> mid with the input stride; pass 2 reads mid and writes out with the output stride
+    auto strided = [&](const NttKArgs &ka, const PassOrder *order) {
+        if (ka.pro_t) launch_pass<P1, true, EPI_NONE, false, PRO_LIFT>(ka, s, order);   // (a plaintext's words lifted as they are loaded)
+        else launch_pass<P1, true, EPI_NONE, false>(ka, s, order);
+    };
+    // pass 1 runs in -> mid with the input stride; pass 2 reads mid and writes out with the output stride
 #if !defined(PHA_NO_ZLOOP)
     if constexpr (VARIANT == 10 || VARIANT == 3 || VARIANT == 4) {   // the product's plans: batched launches take the twiddle-resident contiguous pass
         using Z2 = typename NttPlan<LOGN, VARIANT == 4 ? 3 : VARIANT>::P2;   // (with the twiddles out of the loop there is nothing to form on the fly)
-        const bool done = epi == EPI_FWD_MODDOWN ? launch_zloop<Z2, true, EPI_FWD_MODDOWN, false>(k, s)
-                          : epi == EPI_FWD_MODDOWN_ADD ? launch_zloop<Z2, true, EPI_FWD_MODDOWN_ADD, false>(k, s)
-                          : epi == EPI_FWD_KSRESCALE ? launch_zloop<Z2, true, EPI_FWD_KSRESCALE, false>(k, s)
-                                                     : launch_zloop<Z2, true, EPI_FWD_CANON, false>(k, s);
-        if (done) return;
+        ZloopMap m;
+        if (!k.first_pass_only && plan_zloop<Z2>(k, m)) {
+            if (k.first_pass_done) return launch_zloop_forward<Z2>(k, m, epi, s);
+            if (PHA_NTT_PASS_ORDER == 0) {
+                strided(k1, nullptr);
+                return launch_zloop_forward<Z2>(k, m, epi, s);
+            }
+            // the strided pass ends where the contiguous pass begins, and the next transform of the buffer starts where this one ended
+            const uint32_t parts = order_parts(k), cut = pass_order_half(k.sel.count);
+            for (uint32_t h = 0; h < parts; h++) {
+                const uint32_t lo = h * cut, hi = parts == 1 ? k.sel.count : h ? k.sel.count : cut;
+                const ZloopMap mh = parts == 1 ? m : zloop_sub(m, lo, hi, k.batch);
+                const PassOrder o = pass_order_reverse(mh, (uint32_t)(((size_t)1 << k.log_n) >> P1::LOGTILE), PHA_NTT_ORDER_INT_HEAD != 0);
+                strided(limb_range(k1, lo, hi - lo), &o);
+                launch_zloop_forward<Z2>(limb_range(k, lo, hi - lo), mh, epi, s);
+            }
+            return;
+        }
     }
 #endif
+    if (!k.first_pass_done) strided(k1, nullptr);
+    if (k.first_pass_only) return;
     if (epi == EPI_FWD_MODDOWN) launch_pass<P2, true, EPI_FWD_MODDOWN, false>(k, s);
     else if (epi == EPI_FWD_MODDOWN_ADD) launch_pass<P2, true, EPI_FWD_MODDOWN_ADD, false>(k, s);
     else if (epi == EPI_FWD_KSRESCALE) launch_pass<P2, true, EPI_FWD_KSRESCALE, false>(k, s);
@@ -760,8 +797,25 @@ static void inverse_impl(NttKArgs k, int epi, hipStream_t s, Context *fused = nu
 #if !defined(PHA_NO_ZLOOP)
     if constexpr (VARIANT == 10 || VARIANT == 3 || VARIANT == 4) {   // batched launches: the contiguous pass with the twiddles resident (ntt_zloop_kernel)
         using Z2 = typename NttPlan<LOGN, VARIANT == 4 ? 3 : VARIANT>::P2;
-        if (!launch_zloop<Z2, false, EPI_NONE, false>(k1, s)) launch_pass<P2, false, EPI_NONE, false>(k1, s);
-        launch_inverse_last<P1>(k, epi, s);
+        ZloopMap m;
+        if (!plan_zloop<Z2>(k1, m)) {
+            launch_pass<P2, false, EPI_NONE, false>(k1, s);
+            launch_inverse_last<P1>(k, epi, s);
+            return;
+        }
+        if (PHA_NTT_PASS_ORDER == 0) {
+            launch_zloop<Z2, false, EPI_NONE, false>(k1, m, s);
+            launch_inverse_last<P1>(k, epi, s);
+            return;
+        }
+        const uint32_t parts = order_parts(k), cut = pass_order_half(k.sel.count);
+        for (uint32_t h = 0; h < parts; h++) {
+            const uint32_t lo = h * cut, hi = parts == 1 ? k.sel.count : h ? k.sel.count : cut;
+            const ZloopMap mh = parts == 1 ? m : zloop_sub(m, lo, hi, k.batch);
+            const PassOrder o = pass_order_reverse(mh, (uint32_t)(((size_t)1 << k.log_n) >> P1::LOGTILE), PHA_NTT_ORDER_INT_HEAD != 0);
+            launch_zloop<Z2, false, EPI_NONE, false>(limb_range(k1, lo, hi - lo), mh, s);
+            launch_inverse_last<P1>(limb_range(k, lo, hi - lo), epi, s, &o);
+        }
         return;
     }
 #endif

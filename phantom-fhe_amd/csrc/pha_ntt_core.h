@@ -952,4 +952,106 @@ using WholePlan13 = PassCfg<13, false, 4, 4, 4, 16, false, 13, true, 1>;
 // intt_2d.cu:724-757 at BASELINE config 2's degree)
 using WholePlan14 = PassCfg<14, false, 4, 4, 4, 16, false, 14, true, 2>;
 
+// ---- work maps of the batched launch pair (strided pass: ntt_pass_kernel, contiguous pass: ntt_zloop_kernel) -----------------------
+// Plain integers only, so that the host (launchers, tests/emu/emu_ntt_order.cpp) and the kernels share one statement of the rules.
+//
+// Work map of one ntt_zloop_kernel launch, order S: a 1-D grid, the integer-back-end limbs FIRST (their tiles are the longest: one
+// polynomial per workgroup, so that they run side by side from the start), then the FP64 limbs ascending with zper polynomials per
+// workgroup; inside a limb the polynomials (z-groups), inside those the tiles.
+struct ZloopMap {
+    uint32_t n_int, n_fp;      // limbs of each kind in the selection
+    uint32_t zper;             // polynomials per FP64 workgroup
+    uint32_t tiles;            // tiles per limb
+    uint32_t int_blocks;       // n_int * tiles * batch
+    uint8_t limb[128];         // selection-relative limb indices: the n_int integer limbs, then the n_fp FP64 limbs
+};
+
+// The size rule of the twiddle-resident contiguous pass: launches of >= 8 polynomials that fill the device several times over.
+// wgs_per_poly = tiles per limb x limbs, waves_per_wg = wavefronts of one workgroup.  Gives the polynomials per workgroup, or 0
+// where the launch is too small and takes the plain pass.
+inline uint32_t zloop_zper(uint32_t batch, size_t wgs_per_poly, uint32_t waves_per_wg, uint32_t min_batch) {
+    if (batch < min_batch) return 0;
+    const size_t waves_per_poly = wgs_per_poly * waves_per_wg;
+    // resident wavefront slots at this kernel's register budget (4 per SIMD) x 3 generations
+    const size_t want = (size_t)256 * 4 * 4 * 3;
+    // polynomials per workgroup: the gain saturates at 4-8 (r04 sweep: 4 / 8 / 16 per workgroup -> 274 / 275 / 290 us per 720-limb step),
+    // so at most 8, split evenly over the workgroups of a tile, fewer while the launch would not fill the device three times
+    uint32_t zper = (batch + ((batch + 7) / 8) - 1) / ((batch + 7) / 8);
+    while (zper > 4 && waves_per_poly * ((batch + zper - 1) / zper) < want) zper = (zper + 1) / 2;
+    if (waves_per_poly * ((batch + zper - 1) / zper) < want / 3) return 0;   // too small a launch: the plain pass
+    return zper;
+}
+
+// The limb lists of S for a selection of `count` limbs, fp[y] != 0 where selection-relative limb y runs on the FP64 back end.
+// false: more limbs than the map holds, or mostly wide primes (the plain pass for everything).
+inline bool zloop_fill(ZloopMap &m, uint32_t count, const uint8_t *fp, uint32_t batch, uint32_t zper, uint32_t tiles_per_limb) {
+    if (count > 128) return false;
+    m = ZloopMap{};
+    m.zper = zper;
+    m.tiles = tiles_per_limb;
+    for (uint32_t y = 0; y < count; y++)
+        if (!fp[y]) m.limb[m.n_int++] = (uint8_t)y;
+    for (uint32_t y = 0; y < count; y++)
+        if (fp[y]) m.limb[m.n_int + m.n_fp++] = (uint8_t)y;
+    if (m.n_fp * 2 < count) return false;
+    m.int_blocks = m.n_int * tiles_per_limb * batch;
+    return true;
+}
+inline uint32_t zloop_blocks(const ZloopMap &m, uint32_t batch) { return m.int_blocks + m.n_fp * m.tiles * ((batch + m.zper - 1) / m.zper); }
+
+// The part of map `m` that lies in limbs [lo, hi) of its selection, as the map of that sub-selection (limb indices relative to lo):
+// the same order, the same zper (limb-range halves of a launch that is larger than the last-level cache).
+inline ZloopMap zloop_sub(const ZloopMap &m, uint32_t lo, uint32_t hi, uint32_t batch) {
+    ZloopMap s{};
+    s.zper = m.zper;
+    s.tiles = m.tiles;
+    for (uint32_t i = 0; i < m.n_int + m.n_fp; i++) {
+        if (m.limb[i] < lo || m.limb[i] >= hi) continue;
+        s.limb[s.n_int + s.n_fp] = (uint8_t)(m.limb[i] - lo);
+        if (i < m.n_int) s.n_int++;
+        else s.n_fp++;
+    }
+    s.int_blocks = s.n_int * s.tiles * batch;
+    return s;
+}
+
+// Block order of the strided pass when its launch pair's contiguous pass is ntt_zloop_kernel.  The two passes walk the same buffer;
+// the contiguous pass walks it in order S, and the next transform of the buffer starts over.  With the strided pass in the REVERSE of
+// S -- limb-major, the last FP64 limb first, polynomials descending inside a limb -- each pass begins with the lines the other
+// touched last, which are the ones a last-level cache smaller than the launch still holds; walked the same way round, every line
+// has been evicted by the time it is needed again.  Blocks are dispatched in ascending linear id (x fastest, then y, then z), so
+// the order is the grid (tile, polynomial, limb position) and the decode of a block's three indices: no division, one scalar
+// load that depends on nothing but blockIdx.z.
+struct PassOrder {
+    uint32_t tiles;            // 0 = the pass's plain grid (tile, limb, polynomial); else tiles per limb = gridDim.x of this form
+    uint32_t count;            // limbs = gridDim.z
+    uint32_t limb4[32];        // selection-relative limb indices in the order the pass walks them, four to a word (low byte first)
+};
+PHA_HD uint32_t pass_order_limb(const PassOrder &o, uint32_t i) { return (o.limb4[i >> 2] >> ((i & 3u) * 8u)) & 0xffu; }
+// int_head: the integer limbs (the slowest tiles) stay at the head of the strided launch, in S's order, and the FP64 limbs follow
+// descending (the integer limbs then miss the cache); else the exact reverse of S, integer limbs last
+inline PassOrder pass_order_reverse(const ZloopMap &m, uint32_t tiles_per_limb, bool int_head) {
+    PassOrder o{};
+    o.tiles = tiles_per_limb;
+    o.count = m.n_int + m.n_fp;
+    uint32_t at = 0;
+    auto put = [&](uint32_t y) { o.limb4[at >> 2] |= y << ((at & 3u) * 8u); at++; };
+    if (int_head)
+        for (uint32_t i = 0; i < m.n_int; i++) put(m.limb[i]);
+    for (uint32_t i = o.count; i-- > (int_head ? m.n_int : 0u);) put(m.limb[i]);
+    return o;
+}
+// limbs of the first of the two limb-range halves of a launch of `count` limbs (the second half takes the rest)
+inline uint32_t pass_order_half(uint32_t count) { return (count + 1) / 2; }
+// the grid: x = tile, y = polynomial (descending), z = position in the limb list
+inline void pass_order_grid(const PassOrder &o, uint32_t batch, uint32_t &gx, uint32_t &gy, uint32_t &gz) { gx = o.tiles; gy = batch; gz = o.count; }
+// false: the block lies outside the launch
+PHA_HD bool pass_order_decode(const PassOrder &o, uint32_t batch, uint32_t bx, uint32_t by, uint32_t bz, uint32_t &y, uint32_t &z, uint32_t &tile) {
+    if (bx >= o.tiles || by >= batch || bz >= o.count) return false;
+    tile = bx;
+    z = batch - 1 - by;
+    y = pass_order_limb(o, bz);
+    return true;
+}
+
 }  // namespace pha
