@@ -111,9 +111,6 @@ struct PassCfg {
     }
 };
 
-#ifndef PHA_FPSEL
-#define PHA_FPSEL(a) ((a).fp)   // experiment hook: -D'PHA_FPSEL(a)=true' builds FP64-only kernels (timing only)
-#endif
 // Per-workgroup arguments (all uniform across the workgroup -> SGPRs).
 struct PassArgs {
     const u64 *in;     // limb base to read (first round only)
@@ -168,14 +165,14 @@ PHA_HD void decode_group(int g, int &v, int &hi, int &lo) {
 
 // Twiddles of one radix-2^R group, preloaded in heap order: stage j, sub-group kk -> t[(1 << j) - 1 + kk],
 // taken from tw[(base0 << j) + kk] (base0 = rho * 2^s0 + hi, see round_compute).
-// One table entry: the integer path reads the (W, W') pair, the FP64 path the double W (PHA_FPSEL(a) is uniform).
+// One table entry: the integer path reads the (W, W') pair, the FP64 path the double W (a.fp is uniform).
 PHA_HD u64x2 tw_entry(const PassArgs &a, u32 idx) {
-    if (PHA_FPSEL(a)) return u64x2{a.twd[idx], 0};
+    if (a.fp) return u64x2{a.twd[idx], 0};
     return a.tw[idx];
 }
 template <int R>
 PHA_HD void load_group_twiddles(u64x2 *t, const PassArgs &a, u32 base0) {
-    if (PHA_FPSEL(a)) {
+    if (a.fp) {
 #pragma unroll
         for (int j = 0; j < R; j++)
 #pragma unroll
@@ -364,21 +361,21 @@ PHA_HD u64 apply_epilogue_fp(u64 x, const PassArgs &a, u64 aux, u64 acc) {
 template <int EPI>
 PHA_HD u64 apply_epilogue_v(u64 x, const PassArgs &a, u64 aux, u64 acc) {
     const u64 q = a.q;
-    if (fp_epilogue(EPI) && PHA_FPSEL(a)) return apply_epilogue_fp<EPI>(x, a, aux, acc);   // (uniform)
-    // otherwise the FP64 path hands over canonical residues (fp_to_canon in fp_before_global_store); PHA_FPSEL(a) is uniform per workgroup
-    if (EPI == EPI_FWD_CANON) return PHA_FPSEL(a) ? x : csub(csub(csub(x, q << 2), q << 1), q);
+    if (fp_epilogue(EPI) && a.fp) return apply_epilogue_fp<EPI>(x, a, aux, acc);   // (uniform)
+    // otherwise the FP64 path hands over canonical residues (fp_to_canon in fp_before_global_store); a.fp is uniform per workgroup
+    if (EPI == EPI_FWD_CANON) return a.fp ? x : csub(csub(csub(x, q << 2), q << 1), q);
     if (EPI == EPI_FWD_MODDOWN || EPI == EPI_FWD_MODDOWN_ADD) {
-        const u64 t = PHA_FPSEL(a) ? x : csub(csub(csub(x, q << 2), q << 1), q);
+        const u64 t = a.fp ? x : csub(csub(csub(x, q << 2), q << 1), q);
         const u64 r = shoup(sub_mod(aux, t, q), a.scale, q);
         return EPI == EPI_FWD_MODDOWN_ADD ? add_mod(acc, r, q) : r;
     }
     if (EPI == EPI_FWD_KSRESCALE) {   // acc carries the ct word
-        const u64 t = PHA_FPSEL(a) ? x : csub(csub(csub(x, q << 2), q << 1), q);
+        const u64 t = a.fp ? x : csub(csub(csub(x, q << 2), q << 1), q);
         const u64 u = add_mod(acc, shoup(aux, a.scale2, q), q);
         return shoup(sub_mod(u, t, q), a.scale, q);
     }
-    if (EPI == EPI_INV_CANON) return PHA_FPSEL(a) ? x : csub(csub(x, q << 1), q);
-    if (EPI == EPI_INV_CANON_ADD) return add_mod(aux, PHA_FPSEL(a) ? x : csub(csub(x, q << 1), q), q);   // aux carries acc's word
+    if (EPI == EPI_INV_CANON) return a.fp ? x : csub(csub(x, q << 1), q);
+    if (EPI == EPI_INV_CANON_ADD) return add_mod(aux, a.fp ? x : csub(csub(x, q << 1), q), q);   // aux carries acc's word
     if (EPI == EPI_INV_SCALE) return shoup(x, a.scale, q);
     return x;
 }
@@ -403,15 +400,9 @@ PHA_HD u64 coherent_load(const u64 *p) {
 #endif
 }
 
-// r04 experiment hook (compile-time, default off): cache policy of the coefficient traffic of a pass.  PHA_X_NT bits: 1 = strided pass
-// loads, 2 = strided pass stores, 4 = contiguous pass loads, 8 = contiguous pass stores are nontemporal (`nt`: streamed through the
-// L2 / MALL without displacing the twiddle rows).  tools/stream_calib.hip: an in-place read-modify-write stream runs at 5.9 TB/s with
-// the default policy and at 6.6 TB/s nontemporal on buffers beyond the MALL.
-#ifndef PHA_X_NT
-#define PHA_X_NT 0
-#endif
-template <class C, bool LOAD>
-constexpr bool x_nt() { return ((PHA_X_NT >> ((C::STRIDED ? 0 : 2) + (LOAD ? 0 : 1))) & 1) != 0; }
+// Global accesses of 8 and 16 bytes, NT: nontemporal (`nt`: streamed through the L2 / MALL without displacing what else lives there),
+// which the fused accumulate of pha_rns.hip uses.  (r04: nontemporal coefficient traffic in the NTT passes themselves, in any
+// combination, was measured and not kept: profiles/r04_experiments.md -- the passes below ask for the plain form.)
 #if defined(__clang__)
 typedef unsigned long long u64v2 __attribute__((ext_vector_type(2)));
 #endif
@@ -503,13 +494,13 @@ PHA_HD void round_load(const PassArgs &a, const u64 *lds, int tid, u64 *reg) {
                 const u64x2 *p = reinterpret_cast<const u64x2 *>(a.in + global_index<C>(a, e0, v));
 #pragma unroll
                 for (int k = 0; k < K; k += 2) {
-                    u64x2 t = gload2<x_nt<C, true>()>(p + (k >> 1));
+                    u64x2 t = gload2<false>(p + (k >> 1));
                     rg[k] = t.x;
                     rg[k + 1] = t.y;
                 }
             } else {
 #pragma unroll
-                for (int k = 0; k < K; k++) rg[k] = gload<x_nt<C, true>()>(a.in + global_index<C>(a, e0 + (k << LOGD), v));
+                for (int k = 0; k < K; k++) rg[k] = gload<false>(a.in + global_index<C>(a, e0 + (k << LOGD), v));
             }
         } else {
 #pragma unroll
@@ -546,12 +537,7 @@ PHA_HD void round_load_tw(const PassArgs &a, int tid, u64x2 *twreg) {
         int v, hi, lo;
         decode_group<C, RI>(tid + C::THREADS * gi, v, hi, lo);
         const u32 rho = C::STRIDED ? 1u : (a.rho0 + a.tile * C::V + (u32)v);
-#if defined(PHA_EXP_CONST_TW)   // timing experiment only (wrong results): every twiddle from the first 16 entries
-        const u32 base0 = 1;
-        (void)rho; (void)hi;
-#else
         const u32 base0 = (rho << s0) + (u32)hi;
-#endif
         load_group_twiddles<r>(twreg + C::tw_off(RI) + gi * (K - 1), a, base0);
     }
 }
@@ -571,7 +557,7 @@ PHA_HD void round_compute(const PassArgs &a, int tid, u64 *reg, const u64x2 *twr
         for (int gi = 0; gi < G; gi++) {
             u64 *rg = reg + gi * K;
             const u64x2 *tr = tc + (K - 1) + gi * r;
-            if (PHA_FPSEL(a)) {
+            if (a.fp) {
                 if (FWD ? a.fpm.ct_light : a.fpm.gs_light) ot_round_fp<r, FWD, true>(rg, tc, tr, a.fpm);
                 else ot_round_fp<r, FWD, false>(rg, tc, tr, a.fpm);
             } else {
@@ -580,7 +566,7 @@ PHA_HD void round_compute(const PassArgs &a, int tid, u64 *reg, const u64x2 *twr
         }
         return;
     }
-    if (PHA_FPSEL(a)) {  // uniform per workgroup
+    if (a.fp) {  // uniform per workgroup
 #pragma unroll
         for (int gi = 0; gi < G; gi++) {
             u64 *rg = reg + gi * K;
@@ -654,13 +640,13 @@ PHA_HD void round_out(const PassArgs &a, u64 *lds, int tid, const u64 *reg) {
                     u64x2 t;
                     t.x = apply_epilogue_v<EPI>(rg[k], a, aux.x, acc.x);
                     t.y = apply_epilogue_v<EPI>(rg[k + 1], a, aux.y, acc.y);
-                    gstore2<x_nt<C, false>()>(p + (k >> 1), t);
+                    gstore2<false>(p + (k >> 1), t);
                 }
             } else {
 #pragma unroll
                 for (int k = 0; k < K; k++) {
                     const size_t gidx = global_index<C>(a, e0 + (k << LOGD), v);
-                    gstore<x_nt<C, false>()>(a.out + gidx, apply_epilogue<EPI>(rg[k], a, gidx));
+                    gstore<false>(a.out + gidx, apply_epilogue<EPI>(rg[k], a, gidx));
                 }
             }
         } else {
@@ -690,6 +676,17 @@ PHA_HD void tile_sync() {
     }
 #endif
 }
+
+// How PassProgram runs a segment: MODE says where the first segment's coefficients come from and where the last
+// segment's go:
+//   SEG_PLAIN      loaded from global memory here (with the load prologue), stored to global memory with the epilogue;
+//   SEG_PREFETCHED the caller filled the registers in the first round's layout (prefetch(), or a fused producer such as the
+//                  mod-up's base conversion), already past any prologue;
+//   SEG_KEEP       the last segment WITHOUT its store: the registers keep the transform's outputs in the last round's layout
+//                  (group gi of the thread = K consecutive coefficients starting at global_index(e0, v), see round_out), lazy
+//                  integers or lazy doubles -- what a fused consumer (the key inner product as the epilogue of the mod-up's
+//                  contiguous pass) takes over.
+enum SegMode { SEG_PLAIN = 0, SEG_PREFETCHED = 1, SEG_KEEP = 2 };
 
 template <class C, bool FWD, int EPI, bool FOLD, int HOIST = 1, bool COH = false, int PRO = PRO_NONE>
 struct PassProgram {
@@ -766,7 +763,7 @@ struct PassProgram {
     // pass: the doubles of the first pass -- centred already when the forward pass re-centred them before its store (primes from
     // 2^47), lazy otherwise (the inverse, and the forward's never-re-centred path below 2^47) and then centred here.
     PHA_HD static void fp_after_global_load(const PassArgs &a, u64 *reg) {
-        if (!PHA_FPSEL(a)) return;
+        if (!a.fp) return;
         if (!FIRST_PASS && !(FWD ? a.fpm.ct_light : a.fpm.gs_light)) return;   // (uniform) the first pass stored centred values
 #pragma unroll
         for (int i = 0; i < C::EPT; i++)
@@ -774,7 +771,7 @@ struct PassProgram {
     }
     // FP64 path, last pass: doubles -> canonical integers (the integer epilogue then sees [0,q))
     PHA_HD static void fp_before_global_store(const PassArgs &a, u64 *reg) {
-        if (!PHA_FPSEL(a) || !LAST_PASS) return;
+        if (!a.fp || !LAST_PASS) return;
         if (fp_epilogue(EPI)) return;   // the epilogue takes the doubles as they are (apply_epilogue_fp)
 #pragma unroll
         for (int i = 0; i < C::EPT; i++) reg[i] = fp_to_canon(as_f64(reg[i]), a.fpm);
@@ -785,9 +782,6 @@ struct PassProgram {
     // tile, more registers); otherwise each round requests its own when it starts (fewer registers).
     static constexpr int round_of(int seg) { return FWD ? seg : C::NR - 1 - seg; }
     PHA_HD static void load_twiddles(const PassArgs &a, int tid, u64x2 *twreg) {
-#if defined(PHA_X_NOCOMPUTE) && PHA_X_NOCOMPUTE >= 2
-        return;
-#endif
         if (HOIST == 1) {
             round_load_tw<C, 0>(a, tid, twreg);
             round_load_tw<C, 1>(a, tid, twreg);
@@ -799,81 +793,95 @@ struct PassProgram {
     }
     template <int SEG>
     PHA_HD static void segment_twiddles(const PassArgs &a, int tid, u64x2 *twreg) {
-#if defined(PHA_X_NOCOMPUTE) && PHA_X_NOCOMPUTE >= 2   // 2: no twiddle loads either
-        return;
-#endif
         if (HOIST == 0) round_load_tw<C, round_of(SEG)>(a, tid, twreg);
         if (HOIST == 2 && SEG + 1 < C::NR) round_load_tw<C, round_of(SEG + 1 < C::NR ? SEG + 1 : SEG)>(a, tid, twreg);
     }
 
-    template <int SEG>
-    PHA_HD static void run(const PassArgs &a, u64 *lds, int tid, u64 *reg, u64x2 *twreg) {
-        constexpr int RI = FWD ? SEG : C::NR - 1 - SEG;
+    // One barrier-separated segment of the pass (MODE: SegMode).
+    template <int SEG, int MODE>
+    PHA_HD static void segment(const PassArgs &a, u64 *lds, int tid, u64 *reg, u64x2 *twreg) {
+        constexpr int RI = round_of(SEG);
         constexpr bool first = SEG == 0, last = SEG == C::NR - 1;
+        static_assert(MODE != SEG_KEEP || (last && !first), "the kept segment is the last one of a multi-round pass");
+        static_assert(MODE != SEG_KEEP || !(fp_sched().recentre[SEG] || fp_sched().full[SEG]), "a kept segment hands over what the rounds left");
         segment_twiddles<SEG>(a, tid, twreg);
-        round_load<C, RI, first, COH>(a, lds, tid, reg);
+        if constexpr (!(first && MODE == SEG_PREFETCHED)) round_load<C, RI, first, COH>(a, lds, tid, reg);
+        if constexpr (first && MODE == SEG_PLAIN) {
 #if defined(__HIP_DEVICE_COMPILE__)
-        // r04: ntt_pass_kernel starts every wavefront at raised priority, so that the ~100 scalar / address instructions in front of
-        // its global loads are not queued behind the butterflies of the older wavefronts of its SIMD (oldest-first issue): the loads
-        // go out at once, the butterflies then run at normal priority (720 limbs -2 %, tools/build_variant.sh prioA)
-        if (first) __builtin_amdgcn_s_setprio(0);
+            // r04: ntt_pass_kernel starts every wavefront at raised priority, so that the ~100 scalar / address instructions in front of
+            // its global loads are not queued behind the butterflies of the older wavefronts of its SIMD (oldest-first issue): the loads
+            // go out at once, the butterflies then run at normal priority (720 limbs -2 %, tools/build_variant.sh prioA)
+            __builtin_amdgcn_s_setprio(0);
 #endif
-        if constexpr (PRO == PRO_LIFT) {   // BFV plain lift: the words just loaded are a plaintext's, below t
-            static_assert(FWD && FIRST_PASS, "the plain lift is the load prologue of a forward transform's first pass");
-            if (first) {
+            if constexpr (PRO == PRO_LIFT) {   // BFV plain lift: the words just loaded are a plaintext's, below t
+                static_assert(FWD && FIRST_PASS, "the plain lift is the load prologue of a forward transform's first pass");
 #pragma unroll
                 for (int i = 0; i < C::EPT; i++) reg[i] = bfv_lift_word(reg[i], a.pro_half, a.pro_inc);
-            }
-        } else if (first && FWD && FIRST_PASS && a.pro_reduce) {  // uniform per workgroup
+            } else if (FWD && FIRST_PASS && a.pro_reduce) {  // uniform per workgroup
 #pragma unroll
-            for (int i = 0; i < C::EPT; i++) reg[i] = barrett64(reg[i], a.q, a.pro_ratio1);
+                for (int i = 0; i < C::EPT; i++) reg[i] = barrett64(reg[i], a.q, a.pro_ratio1);
+            }
         }
+        static_assert(PRO != PRO_LIFT || MODE == SEG_PLAIN, "the load prologue belongs to the pass that loads");
         if (first) fp_after_global_load(a, reg);
         // FP64 forward, whole-transform plans beyond 13 stages: magnitudes grow by q/2 + 1 per stage, and the exactness
         // budget of pha_arith.h (|x| < 2^52.6 ~ 6 q at 50 bits going into a multiply) is spent after 13 of them (q + 13 (q/2 + 1)
         // = 7.5 q < 2^52.9 still passes, 14 stages reach 8 q = 2^53), so the registers are re-centred once, after the
         // first 8 stages (3 operations per coefficient)
-        if (FWD && C::WHOLE && C::LOGT >= 14 && SEG == 2 && PHA_FPSEL(a)) {
+        if (FWD && C::WHOLE && C::LOGT >= 14 && SEG == 2 && a.fp) {
 #pragma unroll
             for (int i = 0; i < C::EPT; i++) reg[i] = as_u64(fp_reduce(as_f64(reg[i]), a.fpm));
         }
-#if !defined(PHA_X_NOCOMPUTE)   // r04 timing experiment (wrong results): the pass without its butterflies = its memory + LDS floor
         round_compute<C, RI, FWD, FOLD && RI == 0, fp_sched().recentre[SEG], fp_sched().full[SEG]>(a, tid, reg, twreg);
-#endif
-        if (last) fp_before_global_store(a, reg);
-        round_out<C, RI, last, last ? EPI : (int)EPI_NONE>(a, lds, tid, reg);
+        if constexpr (MODE != SEG_KEEP) {
+            if (last) fp_before_global_store(a, reg);
+            round_out<C, RI, last, last ? EPI : (int)EPI_NONE>(a, lds, tid, reg);
+        }
     }
-
-    // Last segment WITHOUT its store: the registers keep the transform's outputs in the last round's layout (group gi of the
-    // thread = K consecutive coefficients starting at global_index(e0, v), see round_out), lazy integers or lazy doubles -- what a
-    // fused consumer (the key inner product as the epilogue of the mod-up's contiguous pass) takes over.
+    // the names the CPU replay (tests/emu) drives segment by segment
     template <int SEG>
-    PHA_HD static void run_keep(const PassArgs &a, u64 *lds, int tid, u64 *reg, u64x2 *twreg) {
-        constexpr int RI = FWD ? SEG : C::NR - 1 - SEG;
-        static_assert(SEG == C::NR - 1 && SEG > 0, "run_keep is the last segment of a multi-round pass");
-        segment_twiddles<SEG>(a, tid, twreg);
-        round_load<C, RI, false, COH>(a, lds, tid, reg);
-        round_compute<C, RI, FWD, FOLD && RI == 0>(a, tid, reg, twreg);
-    }
-
-    // Pieces for the software-pipelined (persistent) kernel: the first round's global load is issued
-    // one tile ahead of its computation.
-    static constexpr int RI_FIRST = FWD ? 0 : C::NR - 1;
-    PHA_HD static void prefetch(const PassArgs &a, int tid, u64 *reg) {
-        round_load<C, RI_FIRST, true>(a, nullptr, tid, reg);
-    }
+    PHA_HD static void run(const PassArgs &a, u64 *lds, int tid, u64 *reg, u64x2 *twreg) { segment<SEG, SEG_PLAIN>(a, lds, tid, reg, twreg); }
     template <int SEG>
-    PHA_HD static void run_prefetched(const PassArgs &a, u64 *lds, int tid, u64 *reg, u64x2 *twreg) {
-        constexpr int RI = FWD ? SEG : C::NR - 1 - SEG;
-        constexpr bool first = SEG == 0, last = SEG == C::NR - 1;
-        segment_twiddles<SEG>(a, tid, twreg);
-        if (!first) round_load<C, RI, false>(a, lds, tid, reg);
-        if (first) fp_after_global_load(a, reg);
-        round_compute<C, RI, FWD, FOLD && RI == 0, fp_sched().recentre[SEG], fp_sched().full[SEG]>(a, tid, reg, twreg);
-        if (last) fp_before_global_store(a, reg);
-        round_out<C, RI, last, last ? EPI : (int)EPI_NONE>(a, lds, tid, reg);
+    PHA_HD static void run_prefetched(const PassArgs &a, u64 *lds, int tid, u64 *reg, u64x2 *twreg) { segment<SEG, SEG_PREFETCHED>(a, lds, tid, reg, twreg); }
+    template <int SEG>
+    PHA_HD static void run_keep(const PassArgs &a, u64 *lds, int tid, u64 *reg, u64x2 *twreg) { segment<SEG, SEG_KEEP>(a, lds, tid, reg, twreg); }
+
+    // The first round's global load on its own: a software-pipelined caller issues it one tile ahead of SEG_PREFETCHED segments.
+    PHA_HD static void prefetch(const PassArgs &a, int tid, u64 *reg) { round_load<C, round_of(0), true>(a, nullptr, tid, reg); }
+
+    // The whole pass: segments 0 .. NSEG-1 with the hand-over between them (load_twiddles comes first and is the caller's, who may
+    // keep the twiddles across several passes).  MODE as above, SEG_KEEP keeping the LAST segment's outputs in registers.
+    // TAIL_SYNC: a hand-over after the last segment too, for a caller whose next pass writes the same LDS words.
+    template <int MODE, bool TAIL_SYNC, int SEG = 0>
+    PHA_HD static void run_pass(const PassArgs &a, u64 *lds, int tid, u64 *reg, u64x2 *twreg) {
+        constexpr bool last = SEG == NSEG - 1;
+        segment<SEG, (MODE == SEG_KEEP && !last) ? (int)SEG_PLAIN : MODE>(a, lds, tid, reg, twreg);
+        if constexpr (!last) {
+            tile_sync<C>();
+            run_pass<MODE, TAIL_SYNC, SEG + 1>(a, lds, tid, reg, twreg);
+        } else if constexpr (TAIL_SYNC) {
+            tile_sync<C>();
+        }
     }
 };
+
+// A pass body emitted twice, once with a.fp known true and once known false (a.fp is uniform per workgroup): each copy is then
+// scheduled and register-allocated like a kernel that has only that butterfly back end (sweep at 2^16, 60 / 240 / 1020 limbs:
+// 36.3 / 118 / 505 us with one shared body, 32.8 / 107 / 458 us specialised).
+// PHA_WITH_FP_KNOWN(a, cond, body); runs body(b) on a copy b of the PassArgs `a` with b.fp = cond, a statement.  A macro, because the
+// idiom is about what text the compiler sees: handing the body to a function template as a callable gives the same results but, in
+// exec_pass, other instruction schedules for the ntt_pass_kernel instantiations and other spill counts for two of the experiments
+// library's (profiles/ntt_launchers_refactor.md, "Shapes that were compiled and not kept").
+#define PHA_WITH_FP_KNOWN(a, cond, body) \
+    if (cond) {                          \
+        PassArgs b_ = (a);               \
+        b_.fp = true;                    \
+        body(b_);                        \
+    } else {                             \
+        PassArgs b_ = (a);               \
+        b_.fp = false;                   \
+        body(b_);                        \
+    }
 
 // Split N = T1 * T2 per log2 N, with the round schedules of each pass.
 // VARIANT 0: 16 coefficients per thread (radix-16 rounds, one LDS exchange per pass).
@@ -997,7 +1005,100 @@ inline bool zloop_fill(ZloopMap &m, uint32_t count, const uint8_t *fp, uint32_t 
     m.int_blocks = m.n_int * tiles_per_limb * batch;
     return true;
 }
+// The launcher rule in one piece: does a two-pass launch of `count` limbs x `batch` polynomials take ntt_zloop_kernel for its contiguous
+// pass (tiles_per_limb tiles of waves_per_wg wavefronts), and with which map.  false: the plan's own contiguous pass.
+inline bool zloop_plan(ZloopMap &m, uint32_t count, const uint8_t *fp, uint32_t batch, uint32_t tiles_per_limb, uint32_t waves_per_wg,
+                       uint32_t min_batch) {
+    if (count > 128) return false;
+    const uint32_t zper = zloop_zper(batch, (size_t)tiles_per_limb * count, waves_per_wg, min_batch);
+    return zper && zloop_fill(m, count, fp, batch, zper, tiles_per_limb);
+}
+// the NttPlan variant whose contiguous pass ntt_zloop_kernel runs for a launch on plan `variant`, or -1 where the plan has no such form:
+// the product's plans, and with the twiddles out of the loop there is nothing to form on the fly, so plan 4 runs plan 3's
+constexpr int zloop_variant(int variant) { return variant == 4 ? 3 : (variant == 3 || variant == 10) ? variant : -1; }
 inline uint32_t zloop_blocks(const ZloopMap &m, uint32_t batch) { return m.int_blocks + m.n_fp * m.tiles * ((batch + m.zper - 1) / m.zper); }
+
+// ---- which plan a launch takes --------------------------------------------------------------------------------------------------
+// What a launch of `limbs` limbs x `batch` polynomials takes (measured rules):
+//   * N = 4096: the whole transform in one launch; N = 8192: the same from 64 limb-polynomials per launch (one 512-thread
+//     workgroup per limb: 1 / 10 / 60 / 240 / 1020 limbs 10.4 / 10.8 / 11.5 / 13.7 / 53.8 us against 8.7 / 9.4 / 12.0 / 26.2 / 58.2
+//     in two passes);
+//   * otherwise two passes, 8 coefficients per thread, one-wavefront workgroups in the contiguous pass;
+//   * launches of >= 8 polynomials and >= 8192 tiles run the polynomials of a (tile, limb) back to back on one XCD, which then
+//     fetches the twiddle rows they share once (r02: +4.6 % on 16 x 45 limbs at N = 2^16; -3 % on the 16-polynomial launches of
+//     config 4 at N = 2^15 and on the 2- / 3-polynomial launches of a key switch, hence the size rule);
+//   * other launches of >= 1024 tiles (the memory-bound throughput regime) form the last round's twiddles on the fly; small ones
+//     are latency-bound and keep the table-driven last round (r01c).
+// Variant bits (experiments build: pha_set_tuning key 0): bit 0 = 8 coefficients/thread (else 16), bit 3 = integer butterflies for
+// every prime (FP64 path off), bit 4 = on-the-fly twiddles in the contiguous pass (implies bit 0), bit 5 = bit 4 automatically for
+// launches of >= 1024 tiles, bit 6 = one-wavefront workgroups in the contiguous pass (NttPlan variants 3 / 4), bit 7 = N = 4096
+// through the two-pass plans too, bit 8 = the one-workgroup plans of N = 8192 / 16384 for every launch size, bit 9 / 10 = always /
+// never both passes in one launch (L2 hand-off), bit 11 = polynomial-fastest, XCD-grouped block order in the contiguous pass of
+// batched launches, bit 12 (r04) = N = 2^16 as 64 x 1024 (NttPlan<16, 10>: strided tiles of 64 rows x 64 columns, i.e. 512-byte runs and
+// ONE exchange; 1024-point rows, two wavefronts each), bit 13 = the same with one wavefront x 16 coefficients per row (plan 12),
+// bit 14 = 2^16 as 128 x 512 (plan 8).  r04 (profiles/r04_experiments.md): 720 limbs 333 -> 317 us, one 45-limb polynomial 28.4 -> 26.5 us.
+constexpr int kDefaultVariant = 1 | 32 | 64 | 2048 | 4096;   // 8 coefficients per thread, one-wavefront contiguous pass, on-the-fly twiddles for >= 1024 tiles of fewer than 8 polynomials, polynomial-fastest block order in large batched contiguous passes, 2^16 = 64 x 1024
+constexpr size_t kEpt4MaxWaves = 8192;   // = 8 wavefronts per SIMD: 32 limb-polynomials at N = 2^16, 64 at 2^15, 128 at 2^14
+constexpr int kSmallPlan = 5;            // NttPlan variant of small launches (5: four coefficients per thread in the contiguous pass; 6 / 7: r03 experiments)
+constexpr uint32_t kZloopMinBatch = 8;   // polynomials from which a launch may take ntt_zloop_kernel (zloop_zper)
+
+struct PlanShape {
+    int log_n;
+    uint32_t limbs, batch;
+    bool first_pass_only;      // forward: the caller runs its own (fused) second pass
+    bool second_pass_only;     // inverse: the contiguous pass ran in the producer of the intermediate (the fused mod-up, on plan 3's split)
+    int variant_bits;
+    // the test-only library alone (all false / 0 in the product, which builds one plan per degree and launch size)
+    bool experiments;          // every geometry is built: the variant bits are honoured as they are
+    size_t whole14_min;        // limb-polynomials from which N = 2^14 takes its one-workgroup plan
+    size_t one_launch_min_tiles;   // tiles from which the two passes share one launch
+    bool xcd_round_robin;      // workgroup b is known to run on XCD b % 8 (the one-launch form's hand-off needs it)
+};
+struct ResolvedPlan {
+    int log_n;
+    int variant;       // NttPlan<log_n, variant> of the two-pass form
+    int whole;         // 0: two passes; 12 / 13 / 14: the one-workgroup plan of that degree
+    bool zfast;        // polynomial-fastest block order in the contiguous pass
+    bool one_launch;   // experiments: both passes in one launch, the intermediate handed over in the L2 (plans 3 / 4)
+    bool one_launch_asked;   // the tuning state asks for that form, whether or not this plan has it (the fused base conversion declines then)
+};
+inline ResolvedPlan resolve_plan(const PlanShape &p) {
+    const auto has = [&](int mask) { return (p.variant_bits & mask) != 0; };
+    const size_t n = (size_t)1 << p.log_n, batch = p.batch ? p.batch : 1;
+    const size_t tiles = (n / kTileElems) * p.limbs * batch, limb_polys = (size_t)p.limbs * batch;
+    const bool shared_tables = has(2048) && batch >= 8 && tiles >= 8192;
+    const bool ot = has(16) || (has(32) && has(1) && tiles >= 1024 && !shared_tables), wave = has(64) && has(1);
+    ResolvedPlan r{p.log_n, ot ? (wave ? 4 : 2) : wave ? 3 : has(1), 0, shared_tables, false, false};
+    // launches that fit ONE co-resident generation of 256-coefficient wavefronts: four coefficients per thread in the contiguous
+    // pass, i.e. twice the wavefronts with half the serial work each (r03; N = 2^14 .. 2^16).  Same-box A/B (profiles/r03_experiments.md;
+    // kernel traces): a win of 0.4-1.1 us per launch pair up to 8 wavefronts per SIMD (2^16: 1-24 limbs, the 2 x 16-limb
+    // inverse of key switch + rescale 14.9 -> 13.6 us; 2^15: every size up to 60 limbs), a loss of 1-2.5 us beyond (2^16: 40-60 limbs)
+    if (r.variant == 3 && p.log_n >= 14 && p.log_n <= 16 && limb_polys * (n >> 8) <= kEpt4MaxWaves) r.variant = kSmallPlan;
+    // r04: N = 2^16 as 64 x 1024 for every launch that is not the first half of the fused mod-up (whose contiguous pass, with the key
+    // inner product as its epilogue, is the 256-point one-wavefront pass of plan 3)
+    if (p.log_n == 16 && (r.variant == 3 || r.variant == 4) && !p.first_pass_only && !p.second_pass_only) {
+        if (has(4096)) r.variant = 10;
+        else if (p.experiments && has(8192)) r.variant = 12;
+        else if (p.experiments && has(16384)) r.variant = 8;
+    }
+    if (p.log_n == 12 && !has(128)) r.whole = 12;
+    if (p.log_n == 13 && !has(128) && (has(256) || limb_polys >= 64)) r.whole = 13;
+    if (p.experiments && p.log_n == 14 && !has(128) && (has(256) || limb_polys >= p.whole14_min)) r.whole = 14;
+    // both passes in one launch (hand-off through the XCD's L2): launches of >= one_launch_min_tiles tiles (bit 9: every launch;
+    // bit 10: never), only where workgroup b is known to run on XCD b % 8
+    bool one_launch = p.experiments && p.xcd_round_robin && wave && !has(1024) && (has(512) || tiles >= p.one_launch_min_tiles);
+    if (p.second_pass_only) {   // the other half ran in the fused mod-up: two launches' worth of plan, the split of plan 3
+        r.whole = 0;
+        one_launch = false;
+        if (r.variant > 5) r.variant = 3;
+    }
+    // the product library instantiates plan 3 alone for N = 8192 (below 64 limb-polynomials: never 1024 tiles) and plans 3, 4, 5 and
+    // 10 (N = 2^16) beyond
+    if (!p.experiments && (p.log_n == 13 || !(r.variant == 4 || r.variant == kSmallPlan || r.variant == 10))) r.variant = 3;
+    r.one_launch_asked = one_launch;
+    r.one_launch = one_launch && !r.whole && (r.variant == 3 || r.variant == 4);   // (the hand-off kernel is built on those two geometries)
+    return r;
+}
 
 // The part of map `m` that lies in limbs [lo, hi) of its selection, as the map of that sub-selection (limb indices relative to lo):
 // the same order, the same zper (limb-range halves of a launch that is larger than the last-level cache).

@@ -1,7 +1,10 @@
 #!/bin/bash
 # tools/build_variant.sh NAME "<extra -D flags>" [sources...]: an experiment build of the product library with compile-time switches
-# (PHA_X_NT, PHA_X_SPLIT16, PHA_X_VARIANT, PHA_X_KNOBS, ...) -> phantom-fhe_amd/phantom_fhe_amd/libphantom_amd_NAME.so, loaded through
-# PHA_LIB_OVERRIDE.  Only the listed sources (default: pha_ntt.hip) are recompiled; the rest links the product's objects.
+# -> phantom-fhe_amd/phantom_fhe_amd/libphantom_amd_NAME.so, loaded through PHA_LIB_OVERRIDE.  Only the listed sources (default:
+# pha_ntt.hip) are recompiled; the rest links the product's objects.
+# The NTT sources read two switches today: -DPHA_NTT_PASS_ORDER=0|1|2 and -DPHA_NTT_ORDER_INT_HEAD=0|1 (tools/time_ntt_order.py); a new
+# experiment adds its own switch for as long as it is being measured.  The r03-r06 switches (PHA_X_NT, PHA_X_VARIANT, PHA_X_KNOBS,
+# PHA_X_OCC_*, PHA_EXP_STAMPS, ...) were decided and removed: profiles/EXPERIMENTS.md, "Retired build switches".
 set -e
 NAME=$1; FLAGS=$2; shift 2 || true
 SRCS=${@:-pha_ntt.hip}
