@@ -217,7 +217,7 @@ PHA_HD u64 mont_redc128(u64 lo, u64 hi, u64 p, u64 ninv) {
 //           <= 16 H^2 + 2^35 - 48 = 2^64 - 32;                               V / B^2 = x
 //   step 3  m3 = x n30 mod B;  r = (x + m3 p) >> 30 = (x >> 30) + m3 p1 + ((x mod B + m3 p0) >> 30) < 2^34 + 2^60 + 2^30
 // r = (V + (m1 + m2 B + m3 B^2) p) / B^3 < V / 2^90 + p, and V < 15 * 2^60 * p for rows below p, so r < 2p: one conditional subtract.
-// The rows of such a converter hold qhat_i * 2^90 mod p_j (BConv::r90, pha_context.hip).  A sixteenth term would overflow step 1:
+// The rows of such a converter hold qhat_i * 2^90 mod p_j (BConv::r90, pha_rns_tables.h).  A sixteenth term would overflow step 1:
 // converters with 16 inputs keep the 64-bit form.  Checked against big-integer arithmetic at the corners by tests/test_emu_fp.py.
 PHA_HD u64 mont_redc90_split(u64 ll, u64 lh, u64 hl, u64 hh, u64 p, u32 p0, u32 p1, u32 n30) {
     constexpr u32 M = (1u << 30) - 1;

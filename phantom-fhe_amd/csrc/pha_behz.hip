@@ -83,13 +83,20 @@ __global__ __launch_bounds__(256) void sk_fix_kernel(SkArgs k) {
 }
 
 
+// `polys` polynomials through one converter, phase 1 on load: dst + z * dst_stride <- src + z * src_stride
+static void convert(Context &c, const BConv &conv, u64 *dst, size_t dst_stride, const u64 *src, size_t src_stride, uint32_t polys, hipStream_t s,
+                    const BConvEpilogue *epi = nullptr) {
+    BConvCall k = bconv_call(conv);
+    k.polys = polys; k.dst = dst; k.dst_stride = dst_stride; k.src = src; k.src_stride = src_stride; k.epi = epi;
+    launch_bconv(c, k, s);
+}
+
 // ---- the DRNSTool stages of the BEHZ multiply on `polys` polynomials per launch (blockIdx.z; strides in words).  The multiply
 //      runs them on the 2 B or 3 B polynomials of a chunk, the pha_* step entries at the end of this file on one. ----
 // fastbconv_m_tilde rns.cu:1249-1278: src [.][Q][N] -> dst [polys][Bsk + 1][N] packed.  Phase 1 with m_tilde * qhat^-1 (the
 // converter's own scale-in factors, Context::behz), one conversion for all Bsk + 1 outputs
 static void launch_fastbconv_m_tilde(Context &c, Behz &b, u64 *dst, const u64 *src, size_t src_stride, uint32_t polys, hipStream_t s) {
-    launch_bconv(c, b.d_q_to_bskmt.p, 0, polys, b.size_q, b.size_bsk + 1, b.q_to_bskmt.split_kind, dst, (size_t)(b.size_bsk + 1) * c.n,
-                 src, src_stride, nullptr, true, s);
+    convert(c, b.q_to_bskmt, dst, (size_t)(b.size_bsk + 1) * c.n, src, src_stride, polys, s);
 }
 // sm_mrq rns.cu:1326-1338: src [polys][Bsk + 1][N] packed -> dst [.][Bsk][N]
 static void launch_sm_mrq(Context &c, Behz &b, u64 *dst, size_t dst_stride, const u64 *src, uint32_t polys, hipStream_t s) {
@@ -103,7 +110,7 @@ static void launch_fast_floor(Context &c, Behz &b, u64 *dst, const u64 *x_q, siz
                               u64 *conv, uint32_t polys, hipStream_t s) {
     const uint32_t n = (uint32_t)c.n;
     const size_t bn = (size_t)b.size_bsk * n;
-    launch_bconv(c, b.d_q_to_bsk.p, 0, polys, b.size_q, b.size_bsk, b.q_to_bsk.split_kind, conv, bn, x_q, q_stride, nullptr, true, s);
+    convert(c, b.q_to_bsk, conv, bn, x_q, q_stride, polys, s);
     FloorArgs fa{dst, x_bsk, conv, c.d_mod.p, b.inv_prod_q_mod_bsk.p, b.aux0, n, bn, bsk_stride, bn};
     hipLaunchKernelGGL(fast_floor_kernel, dim3(n / 256, b.size_bsk, polys), dim3(256), 0, s, fa);
     check_launch();
@@ -112,8 +119,8 @@ static void launch_fast_floor(Context &c, Behz &b, u64 *dst, const u64 *x_q, siz
 static void launch_fastbconv_sk(Context &c, Behz &b, u64 *out_q, const u64 *x, u64 *msk, uint32_t polys, hipStream_t s) {
     const uint32_t n = (uint32_t)c.n;
     const size_t qn = (size_t)b.size_q * n, bn = (size_t)b.size_bsk * n;
-    launch_bconv(c, b.d_b_to_msk.p, 0, polys, b.size_b, 1, b.b_to_msk.split_kind, msk, n, x, bn, nullptr, true, s);   // B -> m_sk
-    launch_bconv(c, b.d_b_to_q.p, 0, polys, b.size_b, b.size_q, b.b_to_q.split_kind, out_q, qn, x, bn, nullptr, true, s);
+    convert(c, b.b_to_msk, msk, n, x, bn, polys, s);   // B -> m_sk
+    convert(c, b.b_to_q, out_q, qn, x, bn, polys, s);
     SkArgs ka{out_q, msk, x + (size_t)b.size_b * n, c.d_mod.p, b.prod_b_mod_q.p, b.inv_prod_b_mod_msk, b.m_sk, n, qn, n, bn};
     hipLaunchKernelGGL(sk_fix_kernel, dim3(n / 256, b.size_q, polys), dim3(256), 0, s, ka);
     check_launch();
@@ -331,7 +338,7 @@ void launch_bconv_phase1(Context &c, const BConv &conv, u64 *dst, const u64 *src
 // DBaseConverter::bConv_HPS on `batch` polynomials (strides in words): dst [osz][N] <- src [isz][N].  Up to 32 inputs the
 // correction term rides in the conversion kernel (one launch for all the polynomials); wider bases: conversion, phase 1 and
 // fix-up per polynomial, y [isz][N] scratch.
-static void bconv_hps(Context &c, const BConv &conv, const BConvDev *d_conv, const double *inv, const u64 *alpha_mod,
+static void bconv_hps(Context &c, const BConv &conv, const double *inv, const u64 *alpha_mod,
                       u64 *dst, const u64 *src, u64 *y, hipStream_t s, uint32_t batch = 1, size_t dst_stride = 0,
                       size_t src_stride = 0) {
     const uint32_t n = (uint32_t)c.n;
@@ -339,12 +346,11 @@ static void bconv_hps(Context &c, const BConv &conv, const BConvDev *d_conv, con
         BConvEpilogue e{};
         e.hps_inv = inv;
         e.hps_alpha = alpha_mod;
-        launch_bconv(c, d_conv, 0, batch, conv.isz, conv.osz, conv.split_kind, dst, dst_stride, src, src_stride, nullptr, true, s, 0,
-                     0, &e);
+        convert(c, conv, dst, dst_stride, src, src_stride, batch, s, &e);
         return;
     }
-    for (uint32_t b = 1; b < batch; b++) bconv_hps(c, conv, d_conv, inv, alpha_mod, dst + b * dst_stride, src + b * src_stride, y, s);
-    launch_bconv(c, d_conv, 0, 1, conv.isz, conv.osz, conv.split_kind, dst, 0, src, 0, nullptr, true, s);
+    for (uint32_t b = 1; b < batch; b++) bconv_hps(c, conv, inv, alpha_mod, dst + b * dst_stride, src + b * src_stride, y, s);
+    convert(c, conv, dst, 0, src, 0, 1, s);
     launch_bconv_phase1(c, conv, y, src, s);   // the fix-up needs the phase-1 values themselves
     HpsFixArgs fa{dst, y, inv, alpha_mod, c.d_mod.p, conv.d_oprime.p, conv.isz, conv.osz, n};
     hipLaunchKernelGGL(hps_fix_kernel, dim3(n / 256), dim3(256), 0, s, fa);
@@ -556,7 +562,7 @@ static void hps_multiply(Context &c, Hps &h, const u64 *ct1, const u64 *ct2, u64
             const u64 *ct = (w ? ct2 : ct1) + b0 * 2 * qn;
             u64 *x = w ? xb : xa;
             lift_q_ntt(c, ct, qn, x, qrn, sq, 2 * B, s);
-            bconv_hps(c, h.q_to_r, h.d_q_to_r.p, h.q_inv.p, h.alpha_q_mod_r.p, x + qn, ct, y, s, 2 * B, qrn, qn);
+            bconv_hps(c, h.q_to_r, h.q_inv.p, h.alpha_q_mod_r.p, x + qn, ct, y, s, 2 * B, qrn, qn);
             NttExtra xr;
             xr.batch = 2 * B;
             xr.poly_stride = qrn;
@@ -570,7 +576,7 @@ static void hps_multiply(Context &c, Hps &h, const u64 *ct1, const u64 *ct2, u64
         // scale by t/Q and round into base R, then R -> Q (evaluate.cu:800-808)
         ScaleRoundArgs ka{tmp, xp, h.frac.p, h.div_mod_r.p, c.d_mod.p, sq, sr, h.aux0, n, rn, qrn};
         launch_scale_round(c, ka, s, 3 * B);
-        bconv_hps(c, h.r_to_q, h.d_r_to_q.p, h.r_inv.p, h.alpha_r_mod_q.p, dst + b0 * 3 * qn, tmp, y, s, 3 * B, qn, rn);
+        bconv_hps(c, h.r_to_q, h.r_inv.p, h.alpha_r_mod_q.p, dst + b0 * 3 * qn, tmp, y, s, 3 * B, qn, rn);
     }
 }
 
@@ -597,17 +603,16 @@ static void hps_overq_multiply(Context &c, HpsQ &h, const u64 *ct1, const u64 *c
         // first operand: (scaled down to Ql when levels are dropped, :709-710) exact lift to Ql || Rl
         if (h.drop) {
             launch_scale_round_q(c, xa, in1, h.frac_drop.p, h.div_mod_q_drop.p, sq, h.drop, s, 2 * B, qrn, qfn);
-            bconv_hps(c, h.q_to_r, h.d_q_to_r.p, h.q_inv.p, h.alpha_q_mod_r.p, xa + qn, xa, y, s, 2 * B, qrn, qrn);
+            bconv_hps(c, h.q_to_r, h.q_inv.p, h.alpha_q_mod_r.p, xa + qn, xa, y, s, 2 * B, qrn, qrn);
             ntt_forward(c, xa, xa, xa, qr_sel(sq, sr, h.aux0), EPI_FWD_CANON, xf, s);
         } else {
             lift_q_ntt(c, in1, qfn, xa, qrn, sq, 2 * B, s);
-            bconv_hps(c, h.q_to_r, h.d_q_to_r.p, h.q_inv.p, h.alpha_q_mod_r.p, xa + qn, in1, y, s, 2 * B, qrn, qfn);
+            bconv_hps(c, h.q_to_r, h.q_inv.p, h.alpha_q_mod_r.p, xa + qn, in1, y, s, 2 * B, qrn, qfn);
             ntt_forward(c, xa, xa, xa, qr_tail_sel(sq, sr, h.aux0), EPI_FWD_CANON, xf, s);
         }
         if (!square) {   // second operand: Q -> Rl by bConv_BEHZ_var1, then Rl -> Ql exactly (:745-751)
-            launch_bconv(c, h.d_q_to_r_var1.p, 0, 2 * B, h.q_to_r_var1.isz, sr, h.q_to_r_var1.split_kind, xb + qn, qrn, in2, qfn, nullptr,
-                         true, s);
-            bconv_hps(c, h.r_to_q, h.d_r_to_q.p, h.r_inv.p, h.alpha_r_mod_q.p, xb, xb + qn, y, s, 2 * B, qrn, qrn);
+            convert(c, h.q_to_r_var1, xb + qn, qrn, in2, qfn, 2 * B, s);
+            bconv_hps(c, h.r_to_q, h.r_inv.p, h.alpha_r_mod_q.p, xb, xb + qn, y, s, 2 * B, qrn, qrn);
             ntt_forward(c, xb, xb, xb, qr_sel(sq, sr, h.aux0), EPI_FWD_CANON, xf, s);
         }
         launch_tensor_batched(c, xa, square ? xa : xb, xp, sqr, sq, h.aux0 - sq, square, B, s);
@@ -751,13 +756,10 @@ extern "C" int pha_bfv_mul_relin_hps_overq_leveled(pha_context_t ctx, size_t siz
 struct pha_base_converter {
     pha_context_t ctx;
     pha::BConv conv;
-    pha::DevBuf<pha::BConvDev> d_conv;
     pha::DevBuf<double> inv;          // 1 / q_i of the input base (src/host/rns.cu:321-323)
     pha::DevBuf<pha::u64> alpha_mod;  // [isz + 1][osz] alpha * prod(ibase) mod p_j (:459-466)
-    bool split_ok = true;
     // bConv_BEHZ_var1 (negPQHatInvModq / QInvModp, src/host/rns.cu:469-496): built on first use
     std::unique_ptr<pha::BConv> var1;
-    pha::DevBuf<pha::BConvDev> d_var1;
     std::mutex var1_lock;
     // exact_convert_array (src/rns_bconv.cu:374-431): ONE output modulus, which may be a raw value outside the prime table (the
     // plain modulus t of base_q_to_t_conv_, src/rns.cu:283-284)
@@ -803,37 +805,16 @@ __global__ __launch_bounds__(256) void exact_convert_kernel(const ExactArgs k) {
 // constants of exact_convert_array for (input rows, ONE output modulus): qhat_i^-1 mod q_i, qhat_i mod t, prod(ibase)
 static void build_exact(pha::Context &c, pha_base_converter &h) {
     using namespace pha;
-    using u128 = unsigned __int128;
     const size_t isz = h.irows.size();
     std::vector<u64x2> hat_inv(isz);
-    std::vector<u64> mat(isz), q(isz), big(isz + 1, 0);
+    std::vector<u64> mat(isz), q(isz);
+    Big big{1};
     const u64 t = h.out_mod.value;
-    size_t len = 1;
-    big[0] = 1;
     for (size_t i = 0; i < isz; i++) {
-        const u64 qi = c.primes[h.irows[i]];
-        q[i] = qi;
-        u64 hat_q = 1 % qi, hat_t = 1 % t;
-        for (size_t kx = 0; kx < isz; kx++)
-            if (kx != i) {
-                hat_q = (u64)((u128)hat_q * (c.primes[h.irows[kx]] % qi) % qi);
-                hat_t = (u64)((u128)hat_t * (c.primes[h.irows[kx]] % t) % t);
-            }
-        u64 inv = 1, base = hat_q, e = qi - 2;    // q_i is prime
-        while (e) {
-            if (e & 1) inv = (u64)((u128)inv * base % qi);
-            base = (u64)((u128)base * base % qi);
-            e >>= 1;
-        }
-        hat_inv[i] = u64x2{inv, (u64)(((u128)inv << 64) / qi)};
-        mat[i] = hat_t;
-        u64 carry = 0;
-        for (size_t w = 0; w < len; w++) {
-            const u128 x = (u128)big[w] * qi + carry;
-            big[w] = (u64)x;
-            carry = (u64)(x >> 64);
-        }
-        if (carry) big[len++] = carry;
+        const u64 qi = q[i] = c.primes[h.irows[i]];
+        hat_inv[i] = h_pair(h_invmod(prod_mod(c.primes, h.irows, qi, i), qi), qi);
+        mat[i] = prod_mod(c.primes, h.irows, t, i);
+        big_mul(big, qi);
     }
     big.resize(isz);
     h.x_hat_inv.upload(hat_inv);
@@ -863,22 +844,8 @@ int pha_base_converter_create(pha_context_t ctx, const uint32_t *ibase, size_t i
     auto h = std::make_unique<pha_base_converter>();
     h->ctx = ctx;
     build_bconv(c, h->conv, ip, op);
-    describe_conv(h->conv, h->d_conv);
-    std::vector<double> inv(ip.size());
-    for (size_t i = 0; i < ip.size(); i++) {
-        inv[i] = 1.0 / (double)c.primes[ip[i]];
-        if (c.primes[ip[i]] >> 60) h->split_ok = false;
-    }
-    std::vector<u64> am((ip.size() + 1) * op.size());
-    for (size_t j = 0; j < op.size(); j++) {
-        const u64 p = c.primes[op[j]];
-        if (p >> 60) h->split_ok = false;
-        u64 prod = 1 % p;
-        for (uint32_t row : ip) prod = (u64)((unsigned __int128)prod * (c.primes[row] % p) % p);
-        for (size_t a = 0; a <= ip.size(); a++) am[a * op.size() + j] = (u64)((unsigned __int128)a * prod % p);
-    }
-    h->inv.upload(inv);
-    h->alpha_mod.upload(am);
+    h->inv.upload(inverse_doubles(c.primes, ip));
+    h->alpha_mod.upload(alpha_table(c.primes, ip, op));
     h->irows = ip;
     if (op.size() == 1) h->out_mod = c.mods[op[0]];
     *out = h.release();
@@ -922,8 +889,7 @@ int pha_bConv_BEHZ(pha_base_converter_t conv, uint64_t *dst, const uint64_t *src
     if (!conv || !dst || !src) throw std::invalid_argument("null pointer");
     if (conv->raw) throw std::invalid_argument("a converter to a raw modulus supports exact_convert_array only");
     Context &c = conv->ctx->c;
-    launch_bconv(c, conv->d_conv.p, 0, 1, conv->conv.isz, conv->conv.osz, conv->conv.split_kind, dst, 0, src, 0, nullptr, true,
-                 as_stream(stream));
+    convert(c, conv->conv, dst, 0, src, 0, 1, as_stream(stream));
     PHA_API_END
 }
 
@@ -933,7 +899,7 @@ int pha_bConv_HPS(pha_base_converter_t conv, uint64_t *dst, const uint64_t *src,
     if (conv->raw) throw std::invalid_argument("a converter to a raw modulus supports exact_convert_array only");
     Context &c = conv->ctx->c;
     u64 *y = c.scratch(stream, (size_t)conv->conv.isz * c.n);
-    bconv_hps(c, conv->conv, conv->d_conv.p, conv->inv.p, conv->alpha_mod.p, dst, src, y, as_stream(stream));
+    bconv_hps(c, conv->conv, conv->inv.p, conv->alpha_mod.p, dst, src, y, as_stream(stream));
     PHA_API_END
 }
 
@@ -949,12 +915,10 @@ int pha_bConv_BEHZ_var1(pha_base_converter_t conv, uint64_t *dst, const uint64_t
         if (!conv->var1) {
             auto v = std::make_unique<BConv>();
             build_bconv_var1(c, *v, conv->conv.iprime, conv->conv.oprime);
-            describe_conv(*v, conv->d_var1);
             conv->var1 = std::move(v);
         }
     }
-    launch_bconv(c, conv->d_var1.p, 0, 1, conv->var1->isz, conv->var1->osz, conv->var1->split_kind, dst, 0, src, 0, nullptr, true,
-                 as_stream(stream));
+    convert(c, *conv->var1, dst, 0, src, 0, 1, as_stream(stream));
     PHA_API_END
 }
 

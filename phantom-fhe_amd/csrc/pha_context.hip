@@ -6,6 +6,9 @@
 // Written independently of oracle/ (different inverse / primality / root-search code paths) so the
 // two can check each other.  Each prime's tables are computed once and shared by every level
 // (the reference recomputes them per ContextData).
+// The constants of the per-level tools (Tool, Behz, Hps, HpsQ) and of every converter are computed by the host-only
+// functions of pha_rns_tables.h; this file chooses the bases, calls them and uploads.  Nothing is read back from
+// the device (pha_context_download_twiddle and the experiments library's placement census excepted).
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -42,9 +45,7 @@ int translate_exception() {
 // ------------------------------------------------------------------------------------------------
 // host number theory
 // ------------------------------------------------------------------------------------------------
-typedef unsigned __int128 u128;
-
-u64 h_mulmod(u64 a, u64 b, u64 q) { return (u64)(((u128)a * b) % q); }
+// (h_mulmod / h_invmod / h_shoup: pha_rns_tables.h)
 u64 h_powmod(u64 a, u64 e, u64 q) {
     u64 r = 1 % q;
     a %= q;
@@ -54,19 +55,6 @@ u64 h_powmod(u64 a, u64 e, u64 q) {
     }
     return r;
 }
-// extended Euclid (the reference's try_invert_uint_mod is xgcd as well, src/host/numth.cu)
-u64 h_invmod(u64 a, u64 q) {
-    __int128 t = 0, nt = 1, r = q, nr = a % q;
-    while (nr) {
-        __int128 k = r / nr;
-        __int128 tmp = t - k * nt; t = nt; nt = tmp;
-        tmp = r - k * nr; r = nr; nr = tmp;
-    }
-    if (r != 1) throw std::logic_error("value is not invertible modulo q");
-    if (t < 0) t += q;
-    return (u64)t;
-}
-u64 h_shoup(u64 w, u64 q) { return (u64)(((u128)w << 64) / q); }
 DModulus h_modulus(u64 q) {
     u128 r = (~(u128)0) / q;  // floor(2^128/q) for q not a power of two
     return DModulus{q, (u64)r, (u64)(r >> 64)};
@@ -335,8 +323,34 @@ uint32_t Context::add_aux_moduli(const std::vector<u64> &ntt_primes, u64 table_l
     return first;
 }
 
-void describe_conv(const BConv &b, DevBuf<BConvDev> &out) {
-    out.upload({BConvDev{b.hat_inv.p, b.d_iprime.p, b.d_oprime.p, b.mat.p, b.mat30.p, b.mont ? b.oninv.p : nullptr, b.isz, b.osz, 0xffffffffu, 0, 0, 0, b.row_pad, b.r90 ? 1u : 0u}});
+// ---- tools: every constant comes from pha_rns_tables.h (host arithmetic, checked on the CPU); the functions below choose the
+//      bases, call it and upload ----
+
+// finish a converter: constants to the device, host copy of the phase-1 factors, device description
+void upload_bconv(BConv &b, const Rows &ip, const Rows &op, const BConvTables &t, const BConvPlace &place) {
+    b.isz = (uint32_t)ip.size();
+    b.osz = (uint32_t)op.size();
+    b.iprime = ip;
+    b.oprime = op;
+    b.split_kind = t.split_kind;
+    b.mont = t.mont;
+    b.r90 = t.r90;
+    b.row_pad = t.row_pad;
+    b.place = place;
+    b.h_hat_inv = t.hat_inv;
+    b.hat_inv.upload(t.hat_inv);
+    b.mat.upload(t.mat);
+    b.mat30.upload(t.mat30);
+    b.oninv.upload(t.oninv);
+    b.d_iprime.upload(ip);
+    b.d_oprime.upload(op);
+    b.dev.upload({b.describe()});
+}
+void build_bconv(Context &c, BConv &b, const Rows &ip, const Rows &op, const std::vector<u64> *out_scale, u64 in_scale, const BConvPlace &place) {
+    upload_bconv(b, ip, op, bconv_tables(c.primes, ip, op, out_scale, in_scale), place);
+}
+void build_bconv_var1(Context &c, BConv &b, const Rows &ip, const Rows &op, const BConvPlace &place) {
+    upload_bconv(b, ip, op, bconv_tables_var1(c.primes, ip, op), place);
 }
 
 // DRNSTool constructor, HPS multiply part (src/rns.cu:687-790; converters src/host/rns.cu:282-337,438-466).
@@ -359,75 +373,18 @@ Hps &Context::hps() {
         if (r.size() < sr) throw std::logic_error("failed to find enough qualifying primes 2");
     }
     h->aux0 = add_aux_moduli(r, 0);
-    std::vector<uint32_t> iq, ir;
-    for (uint32_t i = 0; i < sq; i++) iq.push_back(i);
-    for (uint32_t j = 0; j < sr; j++) ir.push_back(h->aux0 + j);
+    const Rows iq = row_range(0, sq), ir = row_range(h->aux0, sr);
     build_bconv(*this, h->q_to_r, iq, ir);
     build_bconv(*this, h->r_to_q, ir, iq);
-    describe_conv(h->q_to_r, h->d_q_to_r);
-    describe_conv(h->r_to_q, h->d_r_to_q);
-    auto prod_mod = [&](const std::vector<uint32_t> &rows_, u64 m) {
-        u64 p = 1 % m;
-        for (uint32_t row : rows_) p = h_mulmod(p, primes[row] % m, m);
-        return p;
-    };
-    {
-        std::vector<double> qi(sq), ri(sr);
-        for (uint32_t i = 0; i < sq; i++) qi[i] = 1.0 / (double)primes[i];
-        for (uint32_t j = 0; j < sr; j++) ri[j] = 1.0 / (double)r[j];
-        h->q_inv.upload(qi);
-        h->r_inv.upload(ri);
-        std::vector<u64> aq((size_t)(sq + 1) * sr), ar((size_t)(sr + 1) * sq);
-        for (uint32_t j = 0; j < sr; j++) {
-            const u64 qm = prod_mod(iq, r[j]);
-            for (uint32_t a = 0; a <= sq; a++) aq[(size_t)a * sr + j] = h_mulmod(a, qm, r[j]);
-        }
-        for (uint32_t i = 0; i < sq; i++) {
-            const u64 rm = prod_mod(ir, primes[i]);
-            for (uint32_t a = 0; a <= sr; a++) ar[(size_t)a * sq + i] = h_mulmod(a, rm, primes[i]);
-        }
-        h->alpha_q_mod_r.upload(aq);
-        h->alpha_r_mod_q.upload(ar);
-    }
-    {   // t/Q scale-and-round tables (rns.cu:727-790): x_i = t * R * (S / s_i)^-1 mod s_i as big integers, S = Q || R
-        std::vector<u64> s_all(primes.begin(), primes.begin() + sq);
-        s_all.insert(s_all.end(), r.begin(), r.end());
-        std::vector<double> frac(sq);
-        std::vector<u64> tab((size_t)sr * (sq + 1));
-        auto mul_small = [](std::vector<u64> &b, u64 m) {
-            u64 carry = 0;
-            for (auto &w : b) { const u128 t = (u128)w * m + carry; w = (u64)t; carry = (u64)(t >> 64); }
-            if (carry) b.push_back(carry);
-        };
-        auto mod_small = [](const std::vector<u64> &b, u64 m) {
-            u128 rem = 0;
-            for (size_t i = b.size(); i-- > 0;) rem = ((rem << 64) | b[i]) % m;
-            return (u64)rem;
-        };
-        auto div_small = [](std::vector<u64> &b, u64 m) {
-            u128 rem = 0;
-            for (size_t i = b.size(); i-- > 0;) { const u128 cur = (rem << 64) | b[i]; b[i] = (u64)(cur / m); rem = cur % m; }
-        };
-        for (uint32_t i = 0; i < sq + sr; i++) {
-            u64 hat = 1;
-            for (uint32_t k = 0; k < sq + sr; k++)
-                if (k != i) hat = h_mulmod(hat, s_all[k] % s_all[i], s_all[i]);
-            const u64 shat_inv = h_invmod(hat, s_all[i]);
-            std::vector<u64> x{1};
-            for (u64 rj : r) mul_small(x, rj);
-            mul_small(x, plain_t);
-            mul_small(x, shat_inv);
-            if (i < sq) frac[i] = (double)mod_small(x, s_all[i]) / (double)s_all[i];
-            div_small(x, s_all[i]);
-            if (i < sq) {
-                for (uint32_t j = 0; j < sr; j++) tab[(size_t)j * (sq + 1) + i] = mod_small(x, r[j]);
-            } else {
-                tab[(size_t)(i - sq) * (sq + 1) + sq] = mod_small(x, r[i - sq]);
-            }
-        }
-        h->frac.upload(frac);
-        h->div_mod_r.upload(tab);
-    }
+    h->q_inv.upload(inverse_doubles(primes, iq));
+    h->r_inv.upload(inverse_doubles(primes, ir));
+    h->alpha_q_mod_r.upload(alpha_table(primes, iq, ir));
+    h->alpha_r_mod_q.upload(alpha_table(primes, ir, iq));
+    std::vector<double> frac;   // t/Q scale-and-round into R (rns.cu:727-790)
+    std::vector<u64> tab;
+    scale_round_tables(primes, iq, ir, plain_t, frac, tab);
+    h->frac.upload(frac);
+    h->div_mod_r.upload(tab);
     hps_tool = std::move(h);
     return *hps_tool;
 }
@@ -455,103 +412,26 @@ HpsQ &Context::hps_overq(uint32_t size_ql) {
     h->size_q_full = size_q;
     h->drop = drop;
     h->aux0 = base.aux0;
-    std::vector<uint32_t> iq, ir, iq_full;
-    std::vector<u64> r(sr);
-    for (uint32_t i = 0; i < sq; i++) iq.push_back(i);
-    for (uint32_t i = 0; i < size_q; i++) iq_full.push_back(i);
-    for (uint32_t j = 0; j < sr; j++) { ir.push_back(h->aux0 + j); r[j] = primes[h->aux0 + j]; }
+    const Rows iq = row_range(0, sq), ir = row_range(h->aux0, sr), dropped = row_range(sq, drop);
     build_bconv(*this, h->q_to_r, iq, ir);
     build_bconv(*this, h->r_to_q, ir, iq);
-    build_bconv_var1(*this, h->q_to_r_var1, drop ? iq_full : iq, ir);
-    describe_conv(h->q_to_r, h->d_q_to_r);
-    describe_conv(h->r_to_q, h->d_r_to_q);
-    describe_conv(h->q_to_r_var1, h->d_q_to_r_var1);
-    auto prod_mod = [&](const std::vector<uint32_t> &rows_, u64 m) {
-        u64 p = 1 % m;
-        for (uint32_t row : rows_) p = h_mulmod(p, primes[row] % m, m);
-        return p;
-    };
-    {
-        std::vector<double> qi(sq), ri(sr);
-        for (uint32_t i = 0; i < sq; i++) qi[i] = 1.0 / (double)primes[i];
-        for (uint32_t j = 0; j < sr; j++) ri[j] = 1.0 / (double)r[j];
-        h->q_inv.upload(qi);
-        h->r_inv.upload(ri);
-        std::vector<u64> aq((size_t)(sq + 1) * sr), ar((size_t)(sr + 1) * sq);
-        for (uint32_t j = 0; j < sr; j++) {
-            const u64 qm = prod_mod(iq, r[j]);
-            for (uint32_t a = 0; a <= sq; a++) aq[(size_t)a * sr + j] = h_mulmod(a, qm, r[j]);
-        }
-        for (uint32_t i = 0; i < sq; i++) {
-            const u64 rm = prod_mod(ir, primes[i]);
-            for (uint32_t a = 0; a <= sr; a++) ar[(size_t)a * sq + i] = h_mulmod(a, rm, primes[i]);
-        }
-        h->alpha_q_mod_r.upload(aq);
-        h->alpha_r_mod_q.upload(ar);
-    }
-    auto mul_small = [](std::vector<u64> &b, u64 m) {
-        u64 carry = 0;
-        for (auto &w : b) { const u128 t = (u128)w * m + carry; w = (u64)t; carry = (u64)(t >> 64); }
-        if (carry) b.push_back(carry);
-    };
-    auto mod_small = [](const std::vector<u64> &b, u64 m) {
-        u128 rem = 0;
-        for (size_t i = b.size(); i-- > 0;) rem = ((rem << 64) | b[i]) % m;
-        return (u64)rem;
-    };
-    auto div_small = [](std::vector<u64> &b, u64 m) {
-        u128 rem = 0;
-        for (size_t i = b.size(); i-- > 0;) { const u128 cur = (rem << 64) | b[i]; b[i] = (u64)(cur / m); rem = cur % m; }
-    };
-    // scale-and-round tables of the shape [Ql][extra + 1] + fractions [extra]: x_i = factor * prod(Ql) * (S / s_i)^-1 mod
-    // s_i as big integers over S = Ql || extra primes
-    auto scale_tables = [&](const std::vector<u64> &extra, u64 factor, std::vector<double> &frac, std::vector<u64> &tab) {
-        const uint32_t ne = (uint32_t)extra.size();
-        std::vector<u64> s_all(primes.begin(), primes.begin() + sq);
-        s_all.insert(s_all.end(), extra.begin(), extra.end());
-        frac.assign(ne, 0.0);
-        tab.assign((size_t)sq * (ne + 1), 0);
-        for (uint32_t i = 0; i < sq + ne; i++) {
-            u64 hat = 1;
-            for (uint32_t k = 0; k < sq + ne; k++)
-                if (k != i) hat = h_mulmod(hat, s_all[k] % s_all[i], s_all[i]);
-            const u64 shat_inv = h_invmod(hat, s_all[i]);
-            std::vector<u64> x{1};
-            for (uint32_t k = 0; k < sq; k++) mul_small(x, primes[k]);
-            if (factor != 1) mul_small(x, factor);
-            mul_small(x, shat_inv);
-            if (i >= sq) frac[i - sq] = (double)mod_small(x, s_all[i]) / (double)s_all[i];
-            div_small(x, s_all[i]);
-            if (i >= sq) {
-                for (uint32_t l = 0; l < sq; l++) tab[(size_t)l * (ne + 1) + (i - sq)] = mod_small(x, primes[l]);
-            } else {
-                tab[(size_t)i * (ne + 1) + ne] = mod_small(x, primes[i]);
-            }
-        }
-    };
-    {   // t/Rl scale-and-round (rns.cu:836-885)
-        std::vector<double> frac;
-        std::vector<u64> tab;
-        scale_tables(r, plain_t, frac, tab);
-        h->frac.upload(frac);
-        h->div_mod_q.upload(tab);
-    }
+    build_bconv_var1(*this, h->q_to_r_var1, drop ? row_range(0, size_q) : iq, ir);
+    h->q_inv.upload(inverse_doubles(primes, iq));
+    h->r_inv.upload(inverse_doubles(primes, ir));
+    h->alpha_q_mod_r.upload(alpha_table(primes, iq, ir));
+    h->alpha_r_mod_q.upload(alpha_table(primes, ir, iq));
+    std::vector<double> frac;
+    std::vector<u64> tab;
+    scale_round_tables(primes, ir, iq, plain_t, frac, tab);   // t/Rl scale-and-round into Ql (rns.cu:836-885)
+    h->frac.upload(frac);
+    h->div_mod_q.upload(tab);
     if (drop) {   // Ql/Q scale-and-round (rns.cu:918-972) and the expansion constants (base_Ql_to_QlDrop_conv.PModq)
-        std::vector<u64> dropped(primes.begin() + sq, primes.begin() + size_q);
-        std::vector<double> frac;
-        std::vector<u64> tab;
-        scale_tables(dropped, 1, frac, tab);
+        scale_round_tables(primes, dropped, iq, 1, frac, tab);
         h->frac_drop.upload(frac);
         h->div_mod_q_drop.upload(tab);
-        std::vector<u64> dm(sq), dms(sq);
-        for (uint32_t i = 0; i < sq; i++) {
-            u64 p = 1;
-            for (u64 d : dropped) p = h_mulmod(p, d % primes[i], primes[i]);
-            dm[i] = p;
-            dms[i] = h_shoup(p, primes[i]);
-        }
+        const std::vector<u64> dm = prod_mod_limbs(primes, dropped, sq, false);
         h->drop_mod_q.upload(dm);
-        h->drop_mod_q_shoup.upload(dms);
+        h->drop_mod_q_shoup.upload(shoup_of(primes, iq, dm));
     }
     HpsQ &ref = *h;
     hpsq_tools[size_ql] = std::move(h);
@@ -566,20 +446,7 @@ Behz &Context::behz() {
     auto b = std::make_unique<Behz>();
     b->size_q = size_q;
     b->plain_t = plain_t;
-    // |prod(q)| exactly (get_significant_bit_count_uint of the big modulus)
-    std::vector<u64> acc{1};
-    for (uint32_t i = 0; i < size_q; i++) {
-        u64 carry = 0;
-        for (auto &w : acc) {
-            const u128 t = (u128)w * primes[i] + carry;
-            w = (u64)t;
-            carry = (u64)(t >> 64);
-        }
-        if (carry) acc.push_back(carry);
-    }
-    const int total_bits = (int)(acc.size() - 1) * 64 + (64 - __builtin_clzll(acc.back()));
-    const int t_bits = 64 - __builtin_clzll(plain_t);
-    b->size_b = size_q + ((32 + t_bits + total_bits >= 61 * (int)size_q + 61) ? 1 : 0);  // rns.cu:398-406
+    b->size_b = behz_size_b(primes, size_q, plain_t);
     b->size_bsk = b->size_b + 1;
     // get_primes(n, 61, size_b + 1): m_sk first, then B (rns.cu:413-419); descending from 2^61 - 2n + 1 in steps of 2n
     std::vector<u64> found;
@@ -591,176 +458,25 @@ Behz &Context::behz() {
     bsk.push_back(b->m_sk);
     const u64 m_tilde = (u64)1 << 32;
     b->aux0 = add_aux_moduli(bsk, m_tilde);
-    const uint32_t mt_row = b->aux0 + b->size_bsk;
-    std::vector<uint32_t> iq, ib, obskmt, obsk, omsk{b->aux0 + b->size_b};
-    for (uint32_t i = 0; i < size_q; i++) iq.push_back(i);
-    for (uint32_t i = 0; i < b->size_b; i++) ib.push_back(b->aux0 + i);
-    for (uint32_t i = 0; i < b->size_bsk; i++) obsk.push_back(b->aux0 + i);
-    obskmt = obsk;
-    obskmt.push_back(mt_row);
-    build_bconv(*this, b->q_to_bskmt, iq, obskmt);
+    const Rows iq = row_range(0, size_q), ib = row_range(b->aux0, b->size_b), obsk = row_range(b->aux0, b->size_bsk);
+    // the Q -> Bsk u {m_tilde} converter is only ever fed m_tilde * x (BEHZ_mul_1): its phase-1 factors carry the m_tilde (:450-465), so
+    // the conversion kernel scales on load and no scaled copy of the input is written
+    build_bconv(*this, b->q_to_bskmt, iq, row_range(b->aux0, b->size_bsk + 1), nullptr, m_tilde);
     build_bconv(*this, b->q_to_bsk, iq, obsk);
     build_bconv(*this, b->b_to_q, ib, iq);
-    build_bconv(*this, b->b_to_msk, ib, omsk);
-    describe_conv(b->q_to_bskmt, b->d_q_to_bskmt);
-    describe_conv(b->q_to_bsk, b->d_q_to_bsk);
-    describe_conv(b->b_to_q, b->d_b_to_q);
-    describe_conv(b->b_to_msk, b->d_b_to_msk);
-    auto pair = [](u64 v, u64 q) { return u64x2{v, h_shoup(v, q)}; };
-    auto prod_mod = [&](uint32_t first, uint32_t cnt, u64 m) {
-        u64 p = 1 % m;
-        for (uint32_t i = 0; i < cnt; i++) p = h_mulmod(p, primes[first + i] % m, m);
-        return p;
-    };
-    {   // m_tilde * qhat_i^-1 mod q_i (:450-465)
-        std::vector<u64x2> hi(size_q), v(size_q);
-        PHA_HIP(hipMemcpy(hi.data(), b->q_to_bsk.hat_inv.p, size_q * sizeof(u64x2), hipMemcpyDeviceToHost));
-        for (uint32_t i = 0; i < size_q; i++) v[i] = pair(h_mulmod(m_tilde % primes[i], hi[i].x, primes[i]), primes[i]);
-        b->mt_qhatinv.upload(v);
-        // the Q -> Bsk u {m_tilde} converter is only ever fed m_tilde * x (BEHZ_mul_1): its phase-1 factors carry the m_tilde, so
-        // the conversion kernel scales on load and no scaled copy of the input is written (describe_conv keeps this pointer)
-        b->q_to_bskmt.hat_inv.upload(v);
-    }
-    {
-        std::vector<u64x2> ipq(b->size_bsk), imt(b->size_bsk);
-        std::vector<u64> pq(b->size_bsk);
-        for (uint32_t j = 0; j < b->size_bsk; j++) {
-            const u64 p = primes[b->aux0 + j];
-            pq[j] = prod_mod(0, size_q, p);                         // :548-553
-            ipq[j] = pair(h_invmod(pq[j], p), p);                   // :508-518
-            imt[j] = pair(h_invmod(m_tilde % p, p), p);             // :537-546
-        }
-        b->inv_prod_q_mod_bsk.upload(ipq);
-        b->inv_mt_mod_bsk.upload(imt);
-        b->prod_q_mod_bsk.upload(pq);
-    }
-    {
-        std::vector<u64> pb(size_q);
-        for (uint32_t i = 0; i < size_q; i++) pb[i] = prod_mod(b->aux0, b->size_b, primes[i]);
-        b->prod_b_mod_q.upload(pb);
-        // t (:467-479) by limb of a [Q || Bsk] buffer: one inverse transform over both bases multiplies by it
-        std::vector<u64> tqb, tqbs;
-        for (uint32_t i = 0; i < size_q + b->size_bsk; i++) {
-            tqb.push_back(plain_t);
-            tqbs.push_back(h_shoup(plain_t, primes[i < size_q ? i : b->aux0 + i - size_q]));
-        }
-        b->t_qb.upload(tqb);
-        b->t_qb_shoup.upload(tqbs);
-    }
-    const u64 inv_q_mt = h_invmod(prod_mod(0, size_q, m_tilde), m_tilde);
-    b->neg_inv_prod_q_mod_mt = pair((m_tilde - inv_q_mt) % m_tilde, m_tilde);
-    b->inv_prod_b_mod_msk = pair(h_invmod(prod_mod(b->aux0, b->size_b, b->m_sk), b->m_sk), b->m_sk);
+    build_bconv(*this, b->b_to_msk, ib, Rows{b->aux0 + b->size_b});
+    b->mt_qhatinv.upload(b->q_to_bskmt.h_hat_inv);
+    const BehzTables t = behz_tables(primes, size_q, b->aux0, b->size_b, plain_t);
+    b->inv_prod_q_mod_bsk.upload(t.inv_prod_q_mod_bsk);
+    b->inv_mt_mod_bsk.upload(t.inv_mt_mod_bsk);
+    b->prod_q_mod_bsk.upload(t.prod_q_mod_bsk);
+    b->prod_b_mod_q.upload(t.prod_b_mod_q);
+    b->t_qb.upload(t.t_qb);
+    b->t_qb_shoup.upload(t.t_qb_shoup);
+    b->neg_inv_prod_q_mod_mt = t.neg_inv_prod_q_mod_mt;
+    b->inv_prod_b_mod_msk = t.inv_prod_b_mod_msk;
     behz_tool = std::move(b);
     return *behz_tool;
-}
-
-// q-hat_i^-1 mod q_i and q-hat_i mod p_j for an (ibase -> obase) converter: src/host/rns.cu:282-337,438-457
-// upload converter constants: hat_inv [isz] (value, Shoup), mat [osz][isz]
-static void upload_bconv(Context &c, BConv &b, const std::vector<uint32_t> &ip, const std::vector<uint32_t> &op,
-                         const std::vector<u64x2> &hat_inv, const std::vector<u64> &mat, uint32_t family_isz = 0) {
-    b.isz = (uint32_t)ip.size();
-    b.osz = (uint32_t)op.size();
-    b.iprime = ip;
-    b.oprime = op;
-    // which carry-free split the kernel may use with these constants (BConv::split_kind)
-    auto bits_of = [](u64 v) { int n = 0; while (v) { n++; v >>= 1; } return n; };
-    int by = 0, bm = 0;       // residues of the input primes are below 2^by, matrix entries (residues of the output moduli) below 2^bm
-    for (uint32_t row : ip) by = std::max(by, bits_of(c.primes[row] - 1));
-    for (uint32_t row : op) bm = std::max(bm, bits_of(c.primes[row] - 1));
-    uint32_t sm = 30;         // the matrix entries are cut at this bit
-    b.split_kind = 0;
-    b.row_pad = kBcRowPad;
-    const uint32_t widest = std::max(b.isz, family_isz);   // converters launched together (mod-up digits) take one kind
-    if (widest <= (uint32_t)kBcRowPad && by <= 60 && bm <= 60) b.split_kind = 1;
-    else if (widest <= 32 && by <= 60 && bm <= 62) { b.split_kind = 2; sm = 31; }
-    else if (widest <= 32 && by <= 62 && bm <= 60) { b.split_kind = 3; sm = 30; }
-    if (b.split_kind >= 2 && b.isz > (uint32_t)kBcRowPad) b.row_pad = 32;
-    // Montgomery form for the split-accumulator kernel: rows hold qhat_i * 2^64 mod p_j, so that REDC of the accumulated
-    // sum gives sum_i y_i * qhat_i mod p_j directly (valid for odd p_j; the BEHZ converter with m_tilde = 2^32 keeps Barrett)
-    // and for sum_i y_i * entry < 2^64 p_j: 16 inputs of 60 bits, or in general sum_i q_i < 2^64
-    unsigned __int128 sum_q = 0;
-    for (uint32_t row : ip) sum_q += c.primes[row];
-    b.mont = b.split_kind == 1 || (b.split_kind != 0 && (sum_q >> 64) == 0);
-    for (uint32_t j = 0; j < b.osz; j++) b.mont = b.mont && (c.primes[op[j]] & 1);
-    // r06: with at most 15 inputs and the 30 / 30 cuts the kernels reduce word by word in base 2^30 straight from the four split
-    // accumulators (mont_redc90_split, pha_arith.h): the rows then carry 2^90.  A sixteenth term would overflow its first step.
-    b.r90 = b.mont && b.split_kind == 1 && widest <= 15;
-    std::vector<u64> oninv(b.osz, 0);
-    if (b.mont)
-        for (uint32_t j = 0; j < b.osz; j++) {
-            const u64 pj = c.primes[op[j]];
-            u64 inv = pj;                                        // Newton: inv * pj = 1 mod 2^(3 * 2^k)
-            for (int it = 0; it < 6; it++) inv *= 2 - pj * inv;
-            oninv[j] = 0 - inv;
-        }
-    std::vector<uint32_t> mat30((size_t)b.osz * b.row_pad * 2, 0u);
-    if (b.isz <= b.row_pad)
-        for (uint32_t j = 0; j < b.osz; j++)
-            for (uint32_t i = 0; i < b.isz; i++) {
-                u64 m = mat[(size_t)j * b.isz + i];
-                if (b.mont) {
-                    const u64 pj = c.primes[op[j]];
-                    m = (u64)((((unsigned __int128)m) << 64) % pj);
-                    if (b.r90) m = (u64)((((unsigned __int128)m) << 26) % pj);   // 2^64 * 2^26 = 2^90
-                }
-                mat30[((size_t)j * b.row_pad + i) * 2] = (uint32_t)(m & ((1u << sm) - 1));
-                mat30[((size_t)j * b.row_pad + i) * 2 + 1] = (uint32_t)(m >> sm);
-            }
-    b.hat_inv.upload(hat_inv);
-    b.mat.upload(mat);
-    b.mat30.upload(mat30);
-    b.oninv.upload(oninv);
-    b.d_iprime.upload(ip);
-    b.d_oprime.upload(op);
-}
-
-// out_scale (optional, [osz]): row j of the matrix is multiplied by out_scale[j] mod p_j, i.e. the converter delivers
-// out_scale[j] * (converted value) mod p_j at no extra cost (pha_keyswitch_rescale: P^-1 mod q_j)
-void build_bconv(Context &c, BConv &b, const std::vector<uint32_t> &ip, const std::vector<uint32_t> &op,
-                 const std::vector<u64> *out_scale, uint32_t family_isz) {
-    const uint32_t isz = (uint32_t)ip.size(), osz = (uint32_t)op.size();
-    std::vector<u64x2> hat_inv(isz);
-    for (uint32_t i = 0; i < isz; i++) {
-        const u64 qi = c.primes[ip[i]];
-        u64 h = 1;
-        for (uint32_t k = 0; k < isz; k++)
-            if (k != i) h = h_mulmod(h, c.primes[ip[k]] % qi, qi);
-        const u64 inv = h_invmod(h, qi);
-        hat_inv[i] = u64x2{inv, h_shoup(inv, qi)};
-    }
-    std::vector<u64> mat((size_t)osz * isz);
-    for (uint32_t j = 0; j < osz; j++) {
-        const u64 pj = c.primes[op[j]];
-        for (uint32_t i = 0; i < isz; i++) {
-            u64 h = out_scale ? (*out_scale)[j] % pj : 1;
-            for (uint32_t k = 0; k < isz; k++)
-                if (k != i) h = h_mulmod(h, c.primes[ip[k]] % pj, pj);
-            mat[(size_t)j * isz + i] = h;
-        }
-    }
-    upload_bconv(c, b, ip, op, hat_inv, mat, family_isz);
-}
-
-// bConv_BEHZ_var1 (src/rns_bconv.cu:231-246, constants src/host/rns.cu:469-496): the quotient-style conversion
-// x -> about P * x / Q in base P: phase 1 multiplies by -P * qhat_i^-1 mod q_i, the matrix is q_i^-1 mod p_j.
-void build_bconv_var1(Context &c, BConv &b, const std::vector<uint32_t> &ip, const std::vector<uint32_t> &op) {
-    const uint32_t isz = (uint32_t)ip.size(), osz = (uint32_t)op.size();
-    std::vector<u64x2> hat_inv(isz);
-    for (uint32_t i = 0; i < isz; i++) {
-        const u64 qi = c.primes[ip[i]];
-        u64 h = 1, pm = 1;
-        for (uint32_t k = 0; k < isz; k++)
-            if (k != i) h = h_mulmod(h, c.primes[ip[k]] % qi, qi);
-        for (uint32_t j = 0; j < osz; j++) pm = h_mulmod(pm, c.primes[op[j]] % qi, qi);
-        const u64 v = qi - h_mulmod(pm, h_invmod(h, qi), qi);
-        hat_inv[i] = u64x2{v, h_shoup(v, qi)};
-    }
-    std::vector<u64> mat((size_t)osz * isz);
-    for (uint32_t j = 0; j < osz; j++) {
-        const u64 pj = c.primes[op[j]];
-        for (uint32_t i = 0; i < isz; i++) mat[(size_t)j * isz + i] = h_invmod(c.primes[ip[i]] % pj, pj);
-    }
-    upload_bconv(c, b, ip, op, hat_inv, mat);
 }
 
 Tool &Context::tool(uint32_t size_ql) {
@@ -773,145 +489,78 @@ Tool &Context::tool(uint32_t size_ql) {
     t->size_ql = size_ql;
     t->alpha = size_p;
     t->size_qlp = size_ql + size_p;
-    for (uint32_t i = 0; i < size_ql; i++) t->qlp_prime.push_back(i);
-    for (uint32_t i = 0; i < size_p; i++) t->qlp_prime.push_back(size_q + i);
+    const Rows data = row_range(0, size_ql), special = row_range(size_q, size_p);
+    t->qlp_prime = data;
+    t->qlp_prime.insert(t->qlp_prime.end(), special.begin(), special.end());
     t->d_qlp_prime.upload(t->qlp_prime);
-    // rescale: q_last^-1 mod q_i (rns.cu:66-80)
-    if (size_ql > 1) {
-        std::vector<u64> v(size_ql - 1), vs(size_ql - 1);
-        std::vector<u64x2> v2(size_ql - 1);
-        for (uint32_t i = 0; i + 1 < size_ql; i++) {
-            v[i] = h_invmod(primes[size_ql - 1] % primes[i], primes[i]);
-            vs[i] = h_shoup(v[i], primes[i]);
-            v2[i] = u64x2{v[i], vs[i]};
-        }
+    if (size_ql > 1) {   // rescale: q_last^-1 mod q_i (rns.cu:66-80)
+        const std::vector<u64> v = prod_mod_limbs(primes, Rows{size_ql - 1}, size_ql - 1, true);
         t->inv_q_last.upload(v);
-        t->inv_q_last_shoup.upload(vs);
-        t->inv_q_last2.upload(v2);
+        t->inv_q_last_shoup.upload(shoup_of(primes, data, v));
+        t->inv_q_last2.upload(pairs_of(primes, data, v));
     }
     if (size_p) {
-        // P^-1 mod q_i (rns.cu:110-123)
-        std::vector<u64> v(size_ql), vs(size_ql);
-        std::vector<u64x2> v2(size_ql);
-        for (uint32_t i = 0; i < size_ql; i++) {
-            u64 p = 1;
-            for (uint32_t k = 0; k < size_p; k++) p = h_mulmod(p, primes[size_q + k] % primes[i], primes[i]);
-            v[i] = h_invmod(p, primes[i]);
-            vs[i] = h_shoup(v[i], primes[i]);
-            v2[i] = u64x2{v[i], vs[i]};
-        }
-        t->pinv.upload(v);
-        t->pinv_shoup.upload(vs);
-        t->pinv2.upload(v2);
-        {   // P mod q_i (bigP_mod_q, rns.cu:110-123): key generation and the bgv mod-down
-            std::vector<u64x2> pm(size_ql);
-            for (uint32_t i = 0; i < size_ql; i++) {
-                u64 p = 1;
-                for (uint32_t k = 0; k < size_p; k++) p = h_mulmod(p, primes[size_q + k] % primes[i], primes[i]);
-                pm[i] = u64x2{p, h_shoup(p, primes[i])};
-            }
-            t->p_mod_q2.upload(pm);
-        }
-        // digits (rns.cu:152-190)
-        t->beta = (size_ql + t->alpha - 1) / t->alpha;
+        // P mod q_i and P^-1 mod q_i (bigP_mod_q, bigPInv_mod_q rns.cu:110-123)
+        const std::vector<u64> pm = prod_mod_limbs(primes, special, size_ql, false);
+        t->h_pinv.resize(size_ql);
+        for (uint32_t i = 0; i < size_ql; i++) t->h_pinv[i] = h_invmod(pm[i], primes[i]);
+        t->p_mod_q2.upload(pairs_of(primes, data, pm));
+        t->pinv.upload(t->h_pinv);
+        t->pinv_shoup.upload(shoup_of(primes, data, t->h_pinv));
+        t->pinv2.upload(pairs_of(primes, data, t->h_pinv));
+        // digits (rns.cu:152-190); their phase-1 factors, concatenated, are what the mod-up's inverse transform multiplies by
+        const std::vector<DigitTables> digits = digit_tables(primes, t->qlp_prime, size_ql, t->alpha);
+        t->beta = (uint32_t)digits.size();
         t->digit.resize(t->beta);
-        std::vector<u64> phi(size_ql), phis(size_ql);
+        std::vector<u64> phi, phis;
+        for (const u64x2 &h : part_hat_inv(digits)) { phi.push_back(h.x); phis.push_back(h.y); }
+        std::vector<BConvDev> dd;
+        t->modup_mont30 = true;
         for (uint32_t b = 0; b < t->beta; b++) {
-            const uint32_t s = t->alpha * b;
-            const uint32_t len = (b == t->beta - 1) ? size_ql - t->alpha * (t->beta - 1) : t->alpha;
-            std::vector<uint32_t> ip, op;
-            for (uint32_t j = 0; j < t->size_qlp; j++) {
-                if (j >= s && j < s + len) ip.push_back(t->qlp_prime[j]);
-                else op.push_back(t->qlp_prime[j]);
-            }
-            build_bconv(*this, t->digit[b], ip, op, nullptr, t->alpha);
-            std::vector<u64x2> hi(len);
-            PHA_HIP(hipMemcpy(hi.data(), t->digit[b].hat_inv.p, len * sizeof(u64x2), hipMemcpyDeviceToHost));
-            for (uint32_t i = 0; i < len; i++) { phi[s + i] = hi[i].x; phis[s + i] = hi[i].y; }
+            BConv &d = t->digit[b];
+            const uint32_t own = t->alpha * b;   // the digit writes around its own limbs, which the same launch copies verbatim
+            upload_bconv(d, digits[b].ip, digits[b].op, digits[b].conv, BConvPlace{own, (uint32_t)digits[b].ip.size(), own, 1});
+            dd.push_back(d.describe());
+            // the carry-free form the conversion launches may use: the digits' common kind (1 = the 30 / 30 split of the headline
+            // sets; 2 / 3 = special bases of 17..32 primes or 61-bit primes, BConv::split_kind), 0 if they differ
+            if (b == 0) t->modup_split = d.split_kind;
+            else if (d.split_kind != t->modup_split) t->modup_split = 0;
+            t->modup_max_osz = std::max(t->modup_max_osz, d.osz);
+            t->modup_mont30 = t->modup_mont30 && d.mont30();
         }
+        t->modup_mont30 = t->modup_mont30 && t->modup_split == 1;
         t->part_hat_inv.upload(phi);
         t->part_hat_inv_shoup.upload(phis);
-        // P -> Ql (rns.cu:196-198)
-        std::vector<uint32_t> ip, op;
-        for (uint32_t i = 0; i < size_p; i++) ip.push_back(size_q + i);
-        for (uint32_t i = 0; i < size_ql; i++) op.push_back(i);
-        build_bconv(*this, t->p_to_ql, ip, op);
-        build_bconv(*this, t->p_to_ql_pinv, ip, op, &v);   // the same converter delivering P^-1 * (.) mod q_j (key switch + rescale)
+        t->d_digit_convs.upload(dd);
+        // P -> Ql (rns.cu:196-198) from the P limbs of a [Ql || P] buffer, and the same converter delivering P^-1 * (.) mod q_j
+        // (key switch + rescale)
+        const BConvPlace from_p{0xffffffffu, 0, size_ql, 0};
+        build_bconv(*this, t->p_to_ql, special, data, nullptr, 1, from_p);
+        build_bconv(*this, t->p_to_ql_pinv, special, data, &t->h_pinv, 1, from_p);
         {   // the P -> Ql converter's phase-1 factors, addressable by the limb index of a [Ql || P] buffer
-            std::vector<u64x2> hi(size_p);
-            PHA_HIP(hipMemcpy(hi.data(), t->p_to_ql.hat_inv.p, size_p * sizeof(u64x2), hipMemcpyDeviceToHost));
             std::vector<u64> v(t->size_qlp, 1), vs(t->size_qlp);
             for (uint32_t i = 0; i < t->size_qlp; i++) vs[i] = h_shoup(1, primes[t->qlp_prime[i]]);
-            for (uint32_t i = 0; i < size_p; i++) { v[size_ql + i] = hi[i].x; vs[size_ql + i] = hi[i].y; }
+            for (uint32_t i = 0; i < size_p; i++) { v[size_ql + i] = t->p_to_ql.h_hat_inv[i].x; vs[size_ql + i] = t->p_to_ql.h_hat_inv[i].y; }
             t->p_hat_inv_by_limb.upload(v);
             t->p_hat_inv_by_limb_shoup.upload(vs);
         }
-        // device descriptors for the batched launches
-        auto describe = [](const BConv &b, uint32_t pad_start, uint32_t pad_len, uint32_t src_limb, uint32_t copy_own) {
-            return BConvDev{b.hat_inv.p, b.d_iprime.p, b.d_oprime.p, b.mat.p, b.mat30.p, b.mont ? b.oninv.p : nullptr, b.isz, b.osz,
-                            pad_start, pad_len, src_limb, copy_own, b.row_pad, b.r90 ? 1u : 0u};
-        };
-        std::vector<BConvDev> dd;
-        for (uint32_t b = 0; b < t->beta; b++) {
-            const uint32_t s = t->alpha * b;
-            dd.push_back(describe(t->digit[b], s, t->digit[b].isz, s, 1));
-        }
-        t->d_digit_convs.upload(dd);
-        t->d_p_to_ql_conv.upload({describe(t->p_to_ql, 0xffffffffu, 0, size_ql, 0)});
-        t->d_p_to_ql_pinv_conv.upload({describe(t->p_to_ql_pinv, 0xffffffffu, 0, size_ql, 0)});
         t->split_ok = true;
         for (uint32_t i = 0; i < t->size_qlp; i++)
             if (primes[t->qlp_prime[i]] >> 60) t->split_ok = false;
-        // the carry-free form the conversion launches may use: the digits' common kind (1 = the 30 / 30 split of the headline
-        // sets; 2 / 3 = special bases of 17..32 primes or 61-bit primes, BConv::split_kind), 0 if they differ
-        t->modup_split = t->digit[0].split_kind;
-        for (uint32_t b = 1; b < t->beta; b++)
-            if (t->digit[b].split_kind != t->modup_split) t->modup_split = 0;
-        t->moddown_split = t->p_to_ql.split_kind;
     }
     if (plain_t) {
-        // rns.cu:200-212 (q_last, q_last^-1 mod t), :270-284 (P, P^-1 mod t; P -> {t} converter row)
-        const u64 pt = plain_t;
-        t->t_mod = h_modulus(pt);
-        const u64 iq = h_invmod(primes[size_ql - 1] % pt, pt);
-        t->inv_q_last_mod_t = u64x2{iq, h_shoup(iq, pt)};
-        if (size_ql > 1) {
-            std::vector<u64x2> v(size_ql - 1);
-            for (uint32_t i = 0; i + 1 < size_ql; i++) {
-                const u64 r = primes[size_ql - 1] % primes[i];
-                v[i] = u64x2{r, h_shoup(r, primes[i])};
-            }
-            t->q_last_mod_q2.upload(v);
-        }
+        const PlainTables pt = plain_tables(primes, size_ql, special, plain_t);
+        t->t_mod = h_modulus(plain_t);
+        t->inv_q_last_mod_t = pt.inv_q_last_mod_t;
+        if (size_ql > 1) t->q_last_mod_q2.upload(pairs_of(primes, data, pt.q_last_mod_q));
         if (size_p) {
-            u64 p_t = 1 % pt;
-            std::vector<u64> hat(size_p);
-            for (uint32_t k = 0; k < size_p; k++) {
-                p_t = h_mulmod(p_t, primes[size_q + k] % pt, pt);
-                u64 h = 1 % pt;
-                for (uint32_t j = 0; j < size_p; j++)
-                    if (j != k) h = h_mulmod(h, primes[size_q + j] % pt, pt);
-                hat[k] = h;
-            }
-            const u64 ip = h_invmod(p_t, pt);
-            t->pinv_mod_t = u64x2{ip, h_shoup(ip, pt)};
-            t->p_hat_mod_t.upload(hat);
+            t->pinv_mod_t = pt.pinv_mod_t;
+            t->p_hat_mod_t.upload(pt.p_hat_mod_t);
         }
-        {   // BFV enc / add / sub (rns.cu:292-324): -Ql mod t and t^-1 mod q_i; q_i - t for the plain lift
-            u64 ql_t = 1 % pt;
-            std::vector<u64> ti(size_ql), tis(size_ql), inc(size_ql);
-            for (uint32_t i = 0; i < size_ql; i++) {
-                ql_t = h_mulmod(ql_t, primes[i] % pt, pt);
-                ti[i] = h_invmod(pt % primes[i], primes[i]);
-                tis[i] = h_shoup(ti[i], primes[i]);
-                inc[i] = primes[i] - pt;
-            }
-            const u64 neg = pt - ql_t;
-            t->neg_ql_mod_t = u64x2{neg, h_shoup(neg, pt)};
-            t->t_inv_mod_q.upload(ti);
-            t->t_inv_mod_q_shoup.upload(tis);
-            t->plain_upper_half_increment.upload(inc);
-        }
+        t->neg_ql_mod_t = pt.neg_ql_mod_t;
+        t->t_inv_mod_q.upload(pt.t_inv_mod_q);
+        t->t_inv_mod_q_shoup.upload(shoup_of(primes, data, pt.t_inv_mod_q));
+        t->plain_upper_half_increment.upload(pt.plain_upper_half_increment);
         t->bgv_ready = true;
     }
     Tool &ref = *t;

@@ -1,4 +1,6 @@
 // pha_internal.h -- host-side state behind the C ABI (include/phantom_amd.h).
+// Base converters: BConv is one object (constants, host copy, placement, device description); BConvCall describes one launch;
+// the numbers come from pha_rns_tables.h (host only).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -13,6 +15,7 @@
 #include <vector>
 
 #include "pha_arith.h"
+#include "pha_rns_tables.h"
 
 namespace pha {
 
@@ -97,8 +100,6 @@ struct DevBuf {
     }
 };
 
-constexpr int kBcRowPad = 16;  // row pitch (entries) of the split base-conversion matrix
-
 // per-prime constants of the FP64 NTT path
 struct FpInfo {
     double q, qinv;
@@ -125,10 +126,19 @@ struct BConvDev {
 };
 
 
+// Where a converter reads and writes inside the buffers of its launches (BConvDev has the fields).  The default is a converter
+// between two packed bases; the mod-up digits and P -> Ql work inside [Ql || P] buffers.
+struct BConvPlace {
+    uint32_t pad_start = 0xffffffffu, pad_len = 0, src_limb = 0, copy_own = 0;
+};
+
+// One converter: its constants on the device, the host copy of what the host computed, and its device description `dev` (one
+// BConvDev, written by describe()).  build_bconv / build_bconv_var1 finish the object; nothing is edited afterwards.
 struct BConv {
     uint32_t isz = 0, osz = 0;
     std::vector<uint32_t> iprime, oprime;  // indices into the QP table
-    DevBuf<u64x2> hat_inv;                 // [isz]  qhat_i^-1 mod q_i (+Shoup)
+    std::vector<u64x2> h_hat_inv;          // host copy of hat_inv
+    DevBuf<u64x2> hat_inv;                 // [isz]  in_scale * qhat_i^-1 mod q_i (+Shoup)
     DevBuf<u64> mat;                       // [osz][isz]  qhat_i mod p_j
     DevBuf<uint32_t> mat30;                // [osz][kBcRowPad][2] 30-bit halves of mat (Montgomery form when mont), zero-padded rows
     DevBuf<u64> oninv;                     // [osz] -p_j^-1 mod 2^64
@@ -140,6 +150,15 @@ struct BConv {
     int split_kind = 0;
     uint32_t row_pad = kBcRowPad;
     DevBuf<uint32_t> d_iprime, d_oprime;
+    BConvPlace place;
+    DevBuf<BConvDev> dev;                  // [1]
+    // 30 / 30 cuts, Montgomery rows, 16-entry pitch: what bconv_rescale_kernel and the conversions fused into the strided NTT pass
+    // (modup_conv_strided) hard-code
+    bool mont30() const { return split_kind == 1 && mont && row_pad == (uint32_t)kBcRowPad; }
+    BConvDev describe() const {
+        return BConvDev{hat_inv.p, d_iprime.p, d_oprime.p, mat.p, mat30.p, mont ? oninv.p : nullptr, isz, osz, place.pad_start, place.pad_len,
+                        place.src_limb, place.copy_own, row_pad, r90 ? 1u : 0u};
+    }
 };
 
 // ---- DRNSTool of one level (src/rns.cu:11-200), hot-path constants only ----------------------
@@ -149,11 +168,16 @@ struct Tool {
     DevBuf<uint32_t> d_qlp_prime;
     DevBuf<u64> part_hat_inv, part_hat_inv_shoup;  // partQlHatInv_mod_Ql_concat (rns.cu:152-182)
     std::vector<BConv> digit;                      // part Ql -> complement of QlP, per digit
-    BConv p_to_ql;                                 // base_P_to_Ql_conv (rns.cu:196-198)
+    BConv p_to_ql;                                 // base_P_to_Ql_conv (rns.cu:196-198), reading the P limbs of a [Ql || P] buffer
     BConv p_to_ql_pinv;                            // the same with every output row pre-multiplied by P^-1 mod q_j
-    DevBuf<BConvDev> d_digit_convs, d_p_to_ql_conv, d_p_to_ql_pinv_conv; // device descriptors used by the batched launches
+    DevBuf<BConvDev> d_digit_convs;                // [beta] BConv::describe() of the digits: one mod-up launch indexes them
     bool split_ok = false;                         // every prime <= 60 bits: carry-free split MAC is valid
-    int modup_split = 0, moddown_split = 0;        // BConv::split_kind of the digit converters (if common) and of P -> Ql
+    // the digit family as one launch sees it: the common BConv::split_kind (0 if the digits differ), the widest output base, and
+    // whether every digit has BConv::mont30()
+    int modup_split = 0;
+    uint32_t modup_max_osz = 0;
+    bool modup_mont30 = false;
+    std::vector<u64> h_pinv;                       // host copy of pinv
     DevBuf<u64> pinv, pinv_shoup;                  // bigPInv_mod_q (rns.cu:110-123)
     DevBuf<u64> inv_q_last, inv_q_last_shoup;      // rns.cu:66-80
     DevBuf<u64x2> inv_q_last2;                     // same, interleaved
@@ -177,7 +201,6 @@ struct Behz {
     uint32_t size_q = 0, size_b = 0, size_bsk = 0, aux0 = 0;
     u64 plain_t = 0, m_sk = 0;
     BConv q_to_bskmt, q_to_bsk, b_to_q, b_to_msk;      // Q -> Bsk u {m_tilde}; Q -> Bsk; B -> Q; B -> {m_sk}
-    DevBuf<BConvDev> d_q_to_bskmt, d_q_to_bsk, d_b_to_q, d_b_to_msk;
     DevBuf<u64x2> mt_qhatinv;                            // [Q]   m_tilde * qhat_i^-1 mod q_i
     DevBuf<u64x2> inv_prod_q_mod_bsk, inv_mt_mod_bsk;    // [Bsk]
     DevBuf<u64> prod_q_mod_bsk;                          // [Bsk]
@@ -191,7 +214,6 @@ struct Behz {
 struct Hps {
     uint32_t size_q = 0, size_r = 0, aux0 = 0;
     BConv q_to_r, r_to_q;
-    DevBuf<BConvDev> d_q_to_r, d_r_to_q;
     DevBuf<double> q_inv, r_inv;                 // 1 / q_i, 1 / r_j (src/host/rns.cu:321-323)
     DevBuf<u64> alpha_q_mod_r, alpha_r_mod_q;    // [|ibase| + 1][|obase|] alpha * prod(ibase) mod p_j (:459-466)
     DevBuf<double> frac;                         // [Q]        tRSHatInvModsDivsFrac
@@ -203,7 +225,6 @@ struct Hps {
 struct HpsQ {
     uint32_t size_q = 0, size_r = 0, aux0 = 0;
     BConv q_to_r, r_to_q, q_to_r_var1;           // exact Q -> Rl, exact Rl -> Q, quotient-style Q -> Rl (bConv_BEHZ_var1)
-    DevBuf<BConvDev> d_q_to_r, d_r_to_q, d_q_to_r_var1;
     DevBuf<double> q_inv, r_inv;
     DevBuf<u64> alpha_q_mod_r, alpha_r_mod_q;
     DevBuf<double> frac;                         // [Rl]        tQlSlHatInvModsDivsFrac
@@ -293,10 +314,8 @@ struct Context {
 };
 
 // host number theory (independent of oracle/)
-u64 h_mulmod(u64 a, u64 b, u64 q);
+// (h_mulmod / h_invmod / h_shoup and the table functions: pha_rns_tables.h)
 u64 h_powmod(u64 a, u64 e, u64 q);
-u64 h_invmod(u64 a, u64 q);
-u64 h_shoup(u64 w, u64 q);
 bool h_is_prime(u64 n);
 u64 h_minimal_primitive_root(u64 degree, u64 q);
 DModulus h_modulus(u64 q);
@@ -481,6 +500,22 @@ inline void with_beta(uint32_t beta, F &&fn) {
         default: fn(std::integral_constant<int, FALLBACK>{}); break;
     }
 }
+// calls fn(std::integral_constant<int, P>{}) with P = the register-resident input count (ISZ_PAD) the base-conversion kernels are
+// instantiated for: the ladder 2, 4, 8, 15 (exactly fifteen inputs: no padded sixteenth term), 16, 32, with steps below MIN taken
+// as MIN.  Returns false and calls nothing above MAX (the caller has another kernel, or has ruled such a base out).
+template <int MIN, int MAX, class F>
+inline bool with_isz_pad(uint32_t isz, F &&fn) {
+    if (isz > (uint32_t)MAX) return false;
+    auto at = [&](auto P) { if constexpr (decltype(P)::value >= MIN && decltype(P)::value <= MAX) fn(P); };
+    const uint32_t i = std::max<uint32_t>(isz, MIN);
+    if (i <= 2) at(std::integral_constant<int, 2>{});
+    else if (i <= 4) at(std::integral_constant<int, 4>{});
+    else if (i <= 8) at(std::integral_constant<int, 8>{});
+    else if (i == 15) at(std::integral_constant<int, 15>{});
+    else if (i <= 16) at(std::integral_constant<int, 16>{});
+    else at(std::integral_constant<int, 32>{});
+    return true;
+}
 
 // shared launchers (pha_rns.hip / pha_poly.hip)
 // optional epilogue of a conversion: store dst_j (+)= (cx_j - converted_j) * cst_j instead of converted_j (BFV mod-down)
@@ -495,15 +530,43 @@ struct BConvEpilogue {
     const double *hps_inv = nullptr;      // [isz] 1 / q_i
     const u64 *hps_alpha = nullptr;       // [isz + 1][osz]
 };
-void launch_bconv(Context &c, const BConvDev *convs, uint32_t conv_step, uint32_t batch, uint32_t max_isz,
-                  uint32_t max_osz, int split_kind, u64 *dst, size_t dst_stride, const u64 *src, size_t src_stride,
-                  const u64 *own, bool scale_in, hipStream_t s, uint32_t conv_count = 0, size_t group_stride = 0,
-                  const BConvEpilogue *epi = nullptr, size_t own_group_stride = 0);
-// converter constants for arbitrary bases given as rows of the context's prime table (pha_context.hip)
+// One conversion launch, filled by name.  bconv_call() fills what belongs to the converter(s); the call site adds where the
+// polynomials are.  Polynomial z of the launch (blockIdx.z) is dst + z * dst_stride <- src + z * src_stride.
+struct BConvCall {
+    const BConvDev *convs = nullptr;   // device array
+    uint32_t conv_step = 0;            // converter of polynomial z = convs[z * conv_step] (0: one converter for every z)
+    uint32_t max_isz = 0, max_osz = 0; // over the converters used
+    int split_kind = 0;                // BConv::split_kind of the converters (0: none)
+    uint32_t polys = 1;
+    u64 *dst = nullptr;
+    const u64 *src = nullptr;
+    size_t dst_stride = 0, src_stride = 0;
+    const u64 *own = nullptr;          // copy_own source (the NTT-form input of mod-up); null: no copy
+    bool scale_in = true;              // false: the inputs already carry the converter's phase-1 factors
+    // batches of ciphertexts (mod-up): polynomial z = (ciphertext z / conv_count, digit z % conv_count); per-ciphertext strides of
+    // src and own (own_group_stride 0 = group_stride)
+    uint32_t conv_count = 0;
+    size_t group_stride = 0, own_group_stride = 0;
+    const BConvEpilogue *epi = nullptr;
+};
+inline BConvCall bconv_call(const BConv &b) {
+    BConvCall k;
+    k.convs = b.dev.p; k.max_isz = b.isz; k.max_osz = b.osz; k.split_kind = b.split_kind;
+    return k;
+}
+// the digit family of a level: polynomial z takes digit z (or z % beta, BConvCall::conv_count)
+inline BConvCall bconv_call(const Tool &t) {
+    BConvCall k;
+    k.convs = t.d_digit_convs.p; k.conv_step = 1; k.max_isz = t.alpha; k.max_osz = t.modup_max_osz; k.split_kind = t.modup_split;
+    return k;
+}
+void launch_bconv(Context &c, const BConvCall &k, hipStream_t s);
+// converter constants for arbitrary bases given as rows of the context's prime table (pha_context.hip; the tables:
+// pha_rns_tables.h bconv_tables / bconv_tables_var1)
 void build_bconv(Context &c, BConv &b, const std::vector<uint32_t> &ip, const std::vector<uint32_t> &op,
-                 const std::vector<u64> *out_scale = nullptr, uint32_t family_isz = 0);
-void build_bconv_var1(Context &c, BConv &b, const std::vector<uint32_t> &ip, const std::vector<uint32_t> &op);
-void describe_conv(const BConv &b, DevBuf<BConvDev> &out);
+                 const std::vector<u64> *out_scale = nullptr, u64 in_scale = 1, const BConvPlace &place = {});
+void build_bconv_var1(Context &c, BConv &b, const std::vector<uint32_t> &ip, const std::vector<uint32_t> &op, const BConvPlace &place = {});
+void upload_bconv(BConv &b, const Rows &ip, const Rows &op, const BConvTables &t, const BConvPlace &place);   // what both end with
 void launch_tensor(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, size_t mod_start, bool square,
                    hipStream_t s, size_t poly_limbs = 0);
 void launch_tensor_batched(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, uint32_t remap_from, uint32_t remap_add,

@@ -11,6 +11,9 @@
 //   * the q-hat^-1 scaling (bconv phase 1) is fused into the load (no temp round trip);
 //   * limb index = blockIdx.y everywhere (no tid / N);
 //   * mod-down and rescale reuse the forward NTT's fused epilogue (cx - NTT(delta)) * c.
+// A conversion launch is one BConvCall (pha_internal.h) filled by name: bconv_call() fills the converter's part from a BConv or,
+// for the mod-up digits, from the Tool; launch_bconv() turns it into the kernel's BConvLaunch and picks the instantiation with
+// with_isz_pad, as the fused rescale conversion does.  The mod-down's P -> Ql step is p_to_ql_delta().
 #include "../../include/phantom_amd.h"
 #include "pha_internal.h"
 #include <algorithm>
@@ -270,61 +273,50 @@ static uint32_t bconv_groups(const Context &c, uint32_t osz, uint32_t polys) {
     return (osz + cap - 1) / cap;
 }
 
-// convs: device array; max_isz / max_osz over the converters used; split_kind: BConv::split_kind of the converters (0: none;
-// a Tool passes its split_ok: 1 = every prime <= 60 bits)
-void launch_bconv(Context &c, const BConvDev *convs, uint32_t conv_step, uint32_t batch, uint32_t max_isz,
-                         uint32_t max_osz, int split_kind, u64 *dst, size_t dst_stride, const u64 *src,
-                         size_t src_stride, const u64 *own, bool scale_in, hipStream_t s, uint32_t conv_count,
-                         size_t group_stride, const BConvEpilogue *epi, size_t own_group_stride) {
+// the instantiation with P register-resident inputs: the 30 / 30 cuts (or no split), and the wide cuts of kinds 2 and 3
+template <int P>
+static void launch_bconv_kernel(bool scale_in, bool split, dim3 grid, dim3 block, hipStream_t s, const BConvLaunch &L) {
+    if (scale_in && split) hipLaunchKernelGGL((bconv_kernel<P, true, true>), grid, block, 0, s, L);
+    else if (scale_in) hipLaunchKernelGGL((bconv_kernel<P, true, false>), grid, block, 0, s, L);
+    else if (split) hipLaunchKernelGGL((bconv_kernel<P, false, true>), grid, block, 0, s, L);
+    else hipLaunchKernelGGL((bconv_kernel<P, false, false>), grid, block, 0, s, L);
+}
+template <int P, int SY, int SM>
+static void launch_bconv_kernel_cut(bool scale_in, dim3 grid, dim3 block, hipStream_t s, const BConvLaunch &L) {
+    if (scale_in) hipLaunchKernelGGL((bconv_kernel<P, true, true, SY, SM>), grid, block, 0, s, L);
+    else hipLaunchKernelGGL((bconv_kernel<P, false, true, SY, SM>), grid, block, 0, s, L);
+}
+// (BConvCall: pha_internal.h)
+void launch_bconv(Context &c, const BConvCall &k, hipStream_t s) {
     BConvLaunch L{};
-    if (epi) {
-        if (max_isz > 32) throw std::logic_error("the fused conversion epilogues need the register-resident converter");
-        L.epi_cx = epi->cx; L.epi_dst = epi->dst; L.epi_cst = epi->cst;
-        L.epi_cx_stride = epi->cx_stride; L.epi_dst_stride = epi->dst_stride; L.epi_acc = epi->accumulate ? 1 : 0;
-        L.hps_inv = epi->hps_inv; L.hps_alpha = epi->hps_alpha;
+    if (k.epi) {
+        if (k.max_isz > 32) throw std::logic_error("the fused conversion epilogues need the register-resident converter");
+        L.epi_cx = k.epi->cx; L.epi_dst = k.epi->dst; L.epi_cst = k.epi->cst;
+        L.epi_cx_stride = k.epi->cx_stride; L.epi_dst_stride = k.epi->dst_stride; L.epi_acc = k.epi->accumulate ? 1 : 0;
+        L.hps_inv = k.epi->hps_inv; L.hps_alpha = k.epi->hps_alpha;
     }
-    L.conv_count = conv_count; L.src_group_stride = group_stride; L.own_group_stride = own_group_stride ? own_group_stride : group_stride;
-    L.convs = convs; L.conv_step = conv_step; L.dst = dst; L.src = src; L.own = own;
-    L.dst_stride = dst_stride; L.src_stride = src_stride; L.mod = c.d_mod.p; L.n = (uint32_t)c.n;
-    const uint32_t groups = bconv_groups(c, max_osz, batch);
-    L.out_per_block = (max_osz + groups - 1) / groups;
-    dim3 grid((unsigned)(c.n / kBcThreads), groups, batch);
-    dim3 block(kBcThreads);
-    // the 30 / 30 split accumulators hold at most 16 terms; wider bases or wider primes take the 30 / 31 cuts or the 128-bit accumulate
-    if (split_kind >= 2 && max_isz <= 32 && bconv_split_on()) {
-#define PHA_BCW(P, SY, SM)                                                                                       \
-    do {                                                                                                         \
-        if (scale_in) hipLaunchKernelGGL((bconv_kernel<P, true, true, SY, SM>), grid, block, 0, s, L);            \
-        else hipLaunchKernelGGL((bconv_kernel<P, false, true, SY, SM>), grid, block, 0, s, L);                    \
-    } while (0)
-        if (split_kind == 2) {
-            if (max_isz <= 16) PHA_BCW(16, 30, 31);
-            else PHA_BCW(32, 30, 31);
-        } else {
-            if (max_isz <= 16) PHA_BCW(16, 31, 30);
-            else PHA_BCW(32, 31, 30);
-        }
-#undef PHA_BCW
-        check_launch();
-        return;
+    L.conv_count = k.conv_count; L.src_group_stride = k.group_stride;
+    L.own_group_stride = k.own_group_stride ? k.own_group_stride : k.group_stride;
+    L.convs = k.convs; L.conv_step = k.conv_step; L.dst = k.dst; L.src = k.src; L.own = k.own;
+    L.dst_stride = k.dst_stride; L.src_stride = k.src_stride; L.mod = c.d_mod.p; L.n = (uint32_t)c.n;
+    const uint32_t groups = bconv_groups(c, k.max_osz, k.polys);
+    L.out_per_block = (k.max_osz + groups - 1) / groups;
+    const dim3 grid((unsigned)(c.n / kBcThreads), groups, k.polys), block(kBcThreads);
+    // the 30 / 30 split accumulators hold at most 16 terms; wider bases or wider primes take the 30 / 31 cuts (16 or 32 inputs in
+    // registers) or the 128-bit accumulate, and more than 32 inputs the kernel that re-reads them
+    bool resident;
+    if (k.split_kind == 2 && bconv_split_on()) {
+        resident = with_isz_pad<16, 32>(k.max_isz, [&](auto P) { launch_bconv_kernel_cut<decltype(P)::value, 30, 31>(k.scale_in, grid, block, s, L); });
+    } else if (k.split_kind == 3 && bconv_split_on()) {
+        resident = with_isz_pad<16, 32>(k.max_isz, [&](auto P) { launch_bconv_kernel_cut<decltype(P)::value, 31, 30>(k.scale_in, grid, block, s, L); });
+    } else {
+        const bool split = k.split_kind == 1 && k.max_isz <= 16 && bconv_split_on();
+        resident = with_isz_pad<2, 32>(k.max_isz, [&](auto P) { launch_bconv_kernel<decltype(P)::value>(k.scale_in, split, grid, block, s, L); });
     }
-    const bool split = split_kind == 1 && max_isz <= 16 && bconv_split_on();
-#define PHA_BC(P)                                                                                        \
-    do {                                                                                                 \
-        if (scale_in && split) hipLaunchKernelGGL((bconv_kernel<P, true, true>), grid, block, 0, s, L);   \
-        else if (scale_in) hipLaunchKernelGGL((bconv_kernel<P, true, false>), grid, block, 0, s, L);      \
-        else if (split) hipLaunchKernelGGL((bconv_kernel<P, false, true>), grid, block, 0, s, L);         \
-        else hipLaunchKernelGGL((bconv_kernel<P, false, false>), grid, block, 0, s, L);                   \
-    } while (0)
-    if (max_isz <= 2) PHA_BC(2);
-    else if (max_isz <= 4) PHA_BC(4);
-    else if (max_isz <= 8) PHA_BC(8);
-    else if (max_isz == 15) PHA_BC(15);  // alpha = 15 (C3 / C4): no padded sixteenth term
-    else if (max_isz <= 16) PHA_BC(16);
-    else if (max_isz <= 32) PHA_BC(32);  // BFV multiply at 30-limb chains: inputs still live in registers
-    else if (scale_in) hipLaunchKernelGGL((bconv_wide_kernel<true>), grid, block, 0, s, L);
-    else hipLaunchKernelGGL((bconv_wide_kernel<false>), grid, block, 0, s, L);
-#undef PHA_BC
+    if (!resident) {
+        if (k.scale_in) hipLaunchKernelGGL((bconv_wide_kernel<true>), grid, block, 0, s, L);
+        else hipLaunchKernelGGL((bconv_wide_kernel<false>), grid, block, 0, s, L);
+    }
     check_launch();
 }
 
@@ -917,16 +909,10 @@ void modup(Context &c, Tool &t, u64 *dst, const u64 *cks, int scheme, u64 *t_cks
     if (alpha > 1) {
         // own limbs are copied verbatim by the same kernel (modup_copy_partQl_kernel :522-528);
         // BFV still needs the q-hat^-1 scaling (bconv_mult_kernel :603-607), ckks/bgv got it in the iNTT
-        uint32_t max_osz = 0;
-        bool mont_split = t.modup_split == 1;
-        for (const BConv &b : t.digit) {
-            max_osz = b.osz > max_osz ? b.osz : max_osz;
-            mont_split = mont_split && b.split_kind == 1 && b.mont && b.row_pad == (uint32_t)kBcRowPad;
-        }
         // r05: NTT-form input, N = 2^16, the separate (batched) inner product: the conversion is the load of the forward
         // transform's strided pass (modup_conv_strided, pha_ntt.hip); the transform then runs its contiguous pass only
         if (ntt_dom && !fused_ip) {
-            const ModupConvArgs mc{t.d_digit_convs.p, t.beta, t_cks, (size_t)ql * n, own_in_place ? nullptr : cks, cks_stride, alpha, max_osz, mont_split};
+            const ModupConvArgs mc{t.d_digit_convs.p, t.beta, t_cks, (size_t)ql * n, own_in_place ? nullptr : cks, cks_stride, alpha, t.modup_max_osz, t.modup_mont30};
             if (modup_conv_strided(c, dst, sel, x, mc, s)) {
                 x.first_pass_done = true;
                 ntt_forward(c, dst, dst, dst, sel, EPI_FWD_CANON, x, s);
@@ -936,9 +922,12 @@ void modup(Context &c, Tool &t, u64 *dst, const u64 *cks, int scheme, u64 *t_cks
         // (coefficient-form input: the conversion reads c2 itself, at its own stride; NTT form: the dense t_cks, and c2 only
         //  for the verbatim copy of the digit's own limbs)
         // (fused inner product, NTT-form input: the own limbs are read from c2 by the fused pass, no copy)
-        launch_bconv(c, t.d_digit_convs.p, 1, t.beta * batch, alpha, max_osz, t.modup_split, dst, (size_t)qlp * n,
-                     ntt_dom ? t_cks : cks, 0, ((fused_ip || own_in_place) && ntt_dom) ? nullptr : cks, !ntt_dom, s, batch > 1 ? t.beta : 0,
-                     ntt_dom ? (size_t)ql * n : cks_stride, nullptr, cks_stride);
+        BConvCall k = bconv_call(t);
+        k.polys = t.beta * batch; k.dst = dst; k.dst_stride = (size_t)qlp * n;
+        k.src = ntt_dom ? t_cks : cks; k.scale_in = !ntt_dom;   // (every digit of a ciphertext reads the same polynomial: no src_stride)
+        k.own = ((fused_ip || own_in_place) && ntt_dom) ? nullptr : cks;
+        k.conv_count = batch > 1 ? t.beta : 0; k.group_stride = ntt_dom ? (size_t)ql * n : cks_stride; k.own_group_stride = cks_stride;
+        launch_bconv(c, k, s);
     }
     if (fused_ip) {
         ModupIpArgs ip = *fused_ip;
@@ -949,21 +938,13 @@ void modup(Context &c, Tool &t, u64 *dst, const u64 *cks, int scheme, u64 *t_cks
     ntt_forward(c, dst, dst, dst, sel, EPI_FWD_CANON, x, s);
 }
 
-// P^-1 mod q_limb (bigPInv_mod_q rns.cu:110-123) on the host
-static u64 h_invmod_p(Context &c, uint32_t limb) {
-    const u64 q = c.primes[limb];
-    u64 p = 1;
-    for (uint32_t k = 0; k < c.size_p; k++) p = h_mulmod(p, c.primes[c.size_q + k] % q, q);
-    return h_invmod(p, q);
-}
-
 // The fused-rescale fix-up fields of InnerArgs / ModupIpArgs (pha_keyswitch_rescale): the last data limb of cx receives
 // ct_last + cx_last * P^-1; fix_ct = null: off
 template <class Args>
 static void set_last_limb_fix(Context &c, Tool &t, const u64 *fix_ct, Args &k) {
     k.fix_limb = 0xffffffffu;
     if (!fix_ct) return;
-    const u64 pinv_last = h_invmod_p(c, t.size_ql - 1);
+    const u64 pinv_last = t.h_pinv[t.size_ql - 1];   // P^-1 mod q_last (bigPInv_mod_q rns.cu:110-123)
     k.fix_limb = t.size_ql - 1;
     k.fix_cst = u64x2{pinv_last, h_shoup(pinv_last, c.primes[t.size_ql - 1])};
     k.fix_ct = fix_ct;
@@ -1024,6 +1005,25 @@ static bool modup_inner_prod(Context &c, Tool &t, const KsScratch &k, const u64 
     return false;
 }
 
+// The mod-down's P -> Ql step on `polys` coefficient-form polynomials cx + z * cx_stride ([Ql || P] limbs): delta [polys][Ql][N].
+// alpha = 1 is a copy with a reduction (rns_bconv.cu:691-707), anything else the conversion; epi rides on the conversion only.
+static void p_to_ql_delta(Context &c, Tool &t, u64 *delta, const u64 *cx, size_t cx_stride, uint32_t polys, bool scale_in,
+                          const BConvEpilogue *epi, hipStream_t s) {
+    const size_t n = c.n, d_stride = (size_t)t.size_ql * n;
+    if (t.alpha == 1) {
+        for (uint32_t z = 0; z < polys; z++) {
+            SinglePArgs k{delta + z * d_stride, nullptr, cx + z * cx_stride + d_stride, c.d_mod.p, t.d_qlp_prime.p, t.size_ql, (uint32_t)n};
+            hipLaunchKernelGGL(single_p_kernel, dim3((unsigned)(n / 256), t.size_ql), dim3(256), 0, s, k);
+            check_launch();
+        }
+        return;
+    }
+    BConvCall k = bconv_call(t.p_to_ql);
+    k.polys = polys; k.dst = delta; k.dst_stride = d_stride; k.src = cx; k.src_stride = cx_stride;
+    k.scale_in = scale_in; k.epi = epi;
+    launch_bconv(c, k, s);
+}
+
 // (described with its declaration in pha_internal.h)
 void moddown_from_ntt(Context &c, Tool &t, u64 *ct, size_t ct_stride, u64 *cx, size_t cx_stride, uint32_t polys, int scheme,
                       bool accumulate, u64 *delta, hipStream_t s, bool folded, bool coeff_input) {
@@ -1056,29 +1056,20 @@ void moddown_from_ntt(Context &c, Tool &t, u64 *ct, size_t ct_stride, u64 *cx, s
     bool bfv_epilogue_fused = false, ckks_conv_fused = false;
     // r06, CKKS batches at N = 2^16 with the prescaled inputs: the P -> Ql conversion is the LOAD of the forward transform's strided
     // pass (mod-down form of modup_conv_s1_kernel, pha_ntt.hip): delta is never written in coefficient form
-    if (prescaled && polys > 1 && t.p_to_ql.split_kind == 1 && t.p_to_ql.mont && t.p_to_ql.row_pad == (uint32_t)kBcRowPad) {
+    if (prescaled && polys > 1 && t.p_to_ql.mont30()) {
         NttExtra xf;
         xf.batch = polys;
         xf.poly_stride = d_stride;
-        ModupConvArgs mc{t.d_p_to_ql_conv.p, 1, cx, cx_stride, nullptr, 0, t.alpha, ql, true, nullptr};
+        ModupConvArgs mc{t.p_to_ql.dev.p, 1, cx, cx_stride, nullptr, 0, t.alpha, ql, true, nullptr};
         mc.moddown = true;
         ckks_conv_fused = modup_conv_strided(c, delta, plain_sel(0, ql), xf, mc, s);
     }
-    if (ckks_conv_fused) {
-    } else if (t.alpha == 1) {
-        for (uint32_t z = 0; z < polys; z++) {
-            SinglePArgs k{delta + z * d_stride, nullptr, cx + z * cx_stride + (size_t)ql * n, c.d_mod.p,
-                          t.d_qlp_prime.p, ql, (uint32_t)n};
-            hipLaunchKernelGGL(single_p_kernel, dim3((unsigned)(n / 256), ql), dim3(256), 0, s, k);
-            check_launch();
-        }
-    } else {
+    if (!ckks_conv_fused) {
         // BFV: (cx - delta) * P^-1 (+ add_to_ct) rides on the conversion's output loop, delta is never stored -- for the
-        // register-resident converter (alpha <= 32); a wider P takes the conversion into delta and the element-wise kernel below
-        BConvEpilogue e{cx, ct, t.pinv2.p, cx_stride, ct_stride, accumulate};
-        bfv_epilogue_fused = scheme == PHA_SCHEME_BFV && t.alpha <= 32;
-        launch_bconv(c, t.d_p_to_ql_conv.p, 0, polys, t.alpha, ql, t.moddown_split, delta, d_stride, cx, cx_stride,
-                     nullptr, !prescaled, s, 0, 0, bfv_epilogue_fused ? &e : nullptr);
+        // register-resident converter (1 < alpha <= 32); a wider P takes the conversion into delta and the element-wise kernel below
+        const BConvEpilogue e{cx, ct, t.pinv2.p, cx_stride, ct_stride, accumulate};
+        bfv_epilogue_fused = scheme == PHA_SCHEME_BFV && t.alpha > 1 && t.alpha <= 32;
+        p_to_ql_delta(c, t, delta, cx, cx_stride, polys, !prescaled, bfv_epilogue_fused ? &e : nullptr, s);
     }
     if (scheme == PHA_SCHEME_BGV) {
         // [cx_P]_t lands in the first P limb of each polynomial, then the t-corrected division and the NTT
@@ -1166,8 +1157,7 @@ static void rescale_ntt(Context &c, Tool &t, u64 *src, uint32_t polys, u64 *dst,
 // never written.
 static bool keyswitch_rescale_fusable(const Tool &t) {
     // bconv_rescale_kernel hard-codes the 16-row padding and the 30 / 30 cuts of converter kind 1 (Montgomery entries)
-    return t.alpha > 1 && t.alpha <= (uint32_t)kBcRowPad && t.split_ok && t.p_to_ql_pinv.split_kind == 1 && t.p_to_ql_pinv.mont &&
-           t.p_to_ql_pinv.row_pad == (uint32_t)kBcRowPad && t.size_ql >= 2;
+    return t.alpha > 1 && t.alpha <= (uint32_t)kBcRowPad && t.split_ok && t.p_to_ql_pinv.mont30() && t.size_ql >= 2;
 }
 static void keyswitch_rescale(Context &c, Tool &t, const u64 *ct, const u64 *c2, const u64 *const *rlk, u64 *dst, uint32_t B,
                               const KsScratch &k, hipStream_t s) {
@@ -1199,21 +1189,19 @@ static void keyswitch_rescale(Context &c, Tool &t, const u64 *ct, const u64 *c2,
     // r06, batches at N = 2^16: the conversion (+ last-limb fold) is the LOAD of that transform's strided pass (modup_conv_s1_kernel's
     // rescale form, pha_ntt.hip): v is never written in coefficient form
     if (B > 1) {
-        const ModupConvArgs mc{t.d_p_to_ql_pinv_conv.p, 1, cx, qlp_n, nullptr, 0, t.alpha, (uint32_t)ql, true, cx + nl * n};
+        const ModupConvArgs mc{t.p_to_ql_pinv.dev.p, 1, cx, qlp_n, nullptr, 0, t.alpha, (uint32_t)ql, true, cx + nl * n};
         x.first_pass_done = modup_conv_strided(c, tmp, plain_sel(0, nl), x, mc, s);
     }
     if (!x.first_pass_done) {   // v_j = delta_j P^-1 + (c_last mod q_j)
         BConvRescaleLaunch L{};
-        L.conv = t.d_p_to_ql_pinv_conv.p; L.dst = tmp; L.cx = cx; L.dst_stride = ql_n; L.cx_stride = qlp_n;
+        L.conv = t.p_to_ql_pinv.dev.p; L.dst = tmp; L.cx = cx; L.dst_stride = ql_n; L.cx_stride = qlp_n;
         L.mod = c.d_mod.p; L.n = (uint32_t)n; L.ql = (uint32_t)ql;
         const uint32_t groups = bconv_groups(c, (uint32_t)nl, 2 * (uint32_t)B);
         L.out_per_block = ((uint32_t)nl + groups - 1) / groups;
         const dim3 grid((unsigned)(n / kBcThreads), groups, 2 * B), block(kBcThreads);
-        if (t.alpha <= 2) hipLaunchKernelGGL(bconv_rescale_kernel<2>, grid, block, 0, s, L);
-        else if (t.alpha <= 4) hipLaunchKernelGGL(bconv_rescale_kernel<4>, grid, block, 0, s, L);
-        else if (t.alpha <= 8) hipLaunchKernelGGL(bconv_rescale_kernel<8>, grid, block, 0, s, L);
-        else if (t.alpha == 15) hipLaunchKernelGGL(bconv_rescale_kernel<15>, grid, block, 0, s, L);
-        else hipLaunchKernelGGL(bconv_rescale_kernel<16>, grid, block, 0, s, L);
+        // (keyswitch_rescale_fusable: alpha <= 16)
+        if (!with_isz_pad<2, 16>(t.alpha, [&](auto P) { hipLaunchKernelGGL(bconv_rescale_kernel<decltype(P)::value>, grid, block, 0, s, L); }))
+            throw std::logic_error("fused key switch + rescale for a special base without one");
         check_launch();
     }
     ntt_forward(c, tmp, tmp, dst, plain_sel(0, nl), EPI_FWD_KSRESCALE, x, s);
@@ -1241,16 +1229,7 @@ static void keyswitch_mod_switch(Context &c, Tool &t, const u64 *ct, const u64 *
     xb.batch = polys;
     xb.poly_stride = qlp_n;
     ntt_inverse(c, cx, cx, cx, special_sel(0, t.size_qlp, c.size_qp, c.size_p), EPI_INV_CANON, xb, s);
-    if (t.alpha == 1) {   // the branches of the bgv mod-down
-        for (uint32_t z = 0; z < polys; z++) {
-            SinglePArgs sp{delta + z * ql_n, nullptr, cx + z * qlp_n + ql_n, c.d_mod.p, t.d_qlp_prime.p, (uint32_t)ql, (uint32_t)n};
-            hipLaunchKernelGGL(single_p_kernel, dim3((unsigned)(n / 256), (unsigned)ql), dim3(256), 0, s, sp);
-            check_launch();
-        }
-    } else {
-        launch_bconv(c, t.d_p_to_ql_conv.p, 0, polys, t.alpha, (uint32_t)ql, t.moddown_split, delta, ql_n, cx, qlp_n, nullptr, true, s, 0, 0,
-                     nullptr);
-    }
+    p_to_ql_delta(c, t, delta, cx, qlp_n, polys, true, nullptr, s);   // as the bgv mod-down
     BgvDownSwitchArgs a{};
     a.dst = dst; a.cx = cx; a.delta = delta; a.dst_stride = nl * n; a.cx_stride = qlp_n; a.delta_stride = ql_n;
     a.hat_inv = t.p_to_ql.hat_inv.p; a.iprime = t.p_to_ql.d_iprime.p; a.hat_mod_t = t.p_hat_mod_t.p;
@@ -1290,9 +1269,10 @@ int pha_bconv_P_to_Ql(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const ui
     Context &c = ctx->c;
     check_level(c, size_Ql, true);
     Tool &t = c.tool((uint32_t)size_Ql);
-    // src is the bare [P][N] block: the converter's src_limb offset (Ql) must not be applied
-    launch_bconv(c, t.d_p_to_ql_conv.p, 0, 1, t.alpha, (uint32_t)size_Ql, t.moddown_split, dst, 0,
-                 src - (size_t)size_Ql * c.n, 0, nullptr, true, as_stream(stream));
+    BConvCall k = bconv_call(t.p_to_ql);
+    k.dst = dst;
+    k.src = src - (size_t)size_Ql * c.n;   // src is the bare [P][N] block: the converter's src_limb offset (Ql) must not be applied
+    launch_bconv(c, k, as_stream(stream));
     PHA_API_END
 }
 
