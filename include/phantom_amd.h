@@ -57,7 +57,7 @@ const char *pha_last_error(void);
  *   environment when the library was first used.  In strict mode the dyadic, tensor, mod-up / inner-product / mod-down, key-switch,
  *   hoisting and BFV multiply entries check ct / c2 / t_mod_up / keys / weights / ct1 and ct2 before they compute (one
  *   synchronising pass per operand; among them pha_keyswitch_mod_switch, pha_keyswitch_mod_switch_batched,
- *   pha_inner_product_relin_mod_switch_batched, pha_hoisting_batched and pha_hoisting_weighted_batched) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
+ *   pha_inner_product_relin_mod_switch_batched, pha_hoisting_batched, pha_hoisting_weighted_batched and pha_hoisting_weighted_bsgs_batched) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
 int pha_check_canonical(pha_context_t ctx, const uint64_t *data, size_t coeff_modulus_size, size_t start_modulus_idx,
                         size_t size_P_tail, size_t polys, size_t poly_stride, uint64_t *bad_words, void *stream);
 int pha_check_canonical_keys(pha_context_t ctx, size_t size_Ql, const uint64_t *const *keys, size_t n_keys, uint64_t *bad_words,
@@ -431,6 +431,21 @@ int pha_hoisting_weighted(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const
 int pha_hoisting_weighted_bsgs(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const uint32_t *baby_elts, size_t n_baby,
                                const uint64_t *const *const *baby_glk, const uint32_t *giant_elts, size_t n_giant,
                                const uint64_t *const *const *giant_glk, const uint64_t *const *weights, int scheme, void *stream);
+/* the same for a BATCH of ciphertexts that share every Galois key and weight (one encrypted layer applied to `batch` encrypted
+ * inputs): ct and out are [batch][2][Ql][N]; the elements, key tables and weights [n_giant][n_baby] are exactly what
+ * pha_hoisting_weighted_bsgs takes and serve every ciphertext.  out[b] is word for word what pha_hoisting_weighted_bsgs writes into
+ * a copy of ct[b], for every `chunk`; ckks / bgv; every refusal of that entry applies, before the first launch.  ct is only read;
+ * out may be exactly ct (in place), any other overlap is refused.  `chunk` ciphertexts go through one set of launches -- one mod-up
+ * of chunk polynomials, the fused baby-step kernel, which reads each baby key limb, permutation entry and weight once per group of
+ * up to 4 ciphertexts, one mod-down of 2 * n_giant * chunk polynomials, the giant steps batched over the ciphertexts -- and size the
+ * scratch: with nk keyed giant steps, chunk * (4 n_giant |Ql| + (beta + 2 n_giant + nk beta + 2) |Ql + P| + nk |Ql|) * N words
+ * (2.2 GB per ciphertext at the C3 set, level 45, with 16 x 8 steps).  0 = 4; capped by batch and by the grid limits
+ * (2 * n_giant * chunk, chunk * nk * beta <= 65535).  A chunk of one ciphertext runs the launches of the single entry.
+ * batch = 0 does nothing. */
+int pha_hoisting_weighted_bsgs_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t batch,
+                                       const uint32_t *baby_elts, size_t n_baby, const uint64_t *const *const *baby_glk,
+                                       const uint32_t *giant_elts, size_t n_giant, const uint64_t *const *const *giant_glk,
+                                       const uint64_t *const *weights, int scheme, uint64_t *out, size_t chunk, void *stream);
 /* the same for n_blocks row blocks that share the input ciphertext and every Galois key (the rows of a matrix-vector product):
  * weights [n_blocks][n_giant][n_baby], out [n_blocks][2][Ql][N] (must not overlap ct, which is only read).  The fused baby-step
  * kernel serves the (block, giant step) pairs eight at a time, so the baby keys are streamed once per eight of them; each block's

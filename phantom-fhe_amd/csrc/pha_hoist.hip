@@ -1,13 +1,16 @@
 // pha_hoist.hip -- hoisted rotations on gfx950: one mod-up shared by many Galois elements (pha_hoisting), the plaintext-weighted
 // form (pha_hoisting_weighted), its baby-step / giant-step forms (pha_hoisting_weighted_bsgs, ..._blocks), and both hoisted forms for
-// a batch of ciphertexts that share the keys (pha_hoisting_batched, pha_hoisting_weighted_batched).
+// a batch of ciphertexts that share the keys (pha_hoisting_batched, pha_hoisting_weighted_batched), and the baby-step / giant-step
+// form for such a batch (pha_hoisting_weighted_bsgs_batched).
 //
 // Reference: src/evaluate.cu:1670-1866.  The mod-up, the mod-down and the Galois launchers these entries call live in pha_rns.hip
 // (declared in pha_internal.h).
 #include "../../include/phantom_amd.h"
 #include "pha_internal.h"
 #include "pha_hoist_batched.h"
+#include "pha_hoist_bsgs_batched.h"
 #include <algorithm>
+#include <cstddef>
 
 namespace pha {
 // ---- hoisted rotations (src/evaluate.cu:1670-1866): for every output coefficient, sum over the Galois
@@ -619,6 +622,18 @@ static void hoist_batched_core(Context &c, size_t size_Ql, const u64 *ct, size_t
     }
 }
 
+// ---- the fused baby-step kernel of the BSGS form for a batch of ciphertexts that share the baby keys, the tables and the weights
+//      (pha_hoisting_weighted_bsgs_batched).  The thread program is pha_hoist_bsgs_batched.h (replayed on the CPU by tests/emu): one
+//      thread owns one coefficient of one limb for NG giant-step accumulators of up to CB ciphertexts, blockIdx.z = group of CB
+//      ciphertexts of the chunk. ----
+static_assert(sizeof(BsgsBFp) == sizeof(FpInfo) && offsetof(BsgsBFp, qinv) == offsetof(FpInfo, qinv) &&
+                  offsetof(BsgsBFp, ok) == offsetof(FpInfo, ok),
+              "pha_hoist_bsgs_batched.h restates FpInfo");
+template <int NG, int CB, int BETA>
+__global__ __launch_bounds__(256) void hoist_bsgs_batched_kernel(const BsgsBArgs k) {
+    hoist_bsgs_batched_thread<NG, CB, BETA>(k, blockIdx.x * 256 + threadIdx.x, blockIdx.y, blockIdx.z);
+}
+
 }  // namespace pha
 
 using namespace pha;
@@ -740,6 +755,146 @@ static void bsgs_core(Context &c, Tool &t, const u64 *ct_in, size_t blocks, cons
         hipLaunchKernelGGL(inner_prod_multi_kernel, dim3((unsigned)(n / 512), t.size_qlp, (unsigned)blocks), dim3(256), 0, s, k);
         check_launch();
         moddown_from_ntt(c, t, out, ql_n, cxg, qlp_n, (uint32_t)(2 * blocks), scheme, true, tmp, s);
+    }
+}
+
+// Driver of pha_hoisting_weighted_bsgs_batched: `batch` ciphertexts that share every key, table and weight, `chunk` of them per set of
+// launches.  Per chunk of cb >= 2 ciphertexts: one mod-up of the cb c1 polynomials (the digits' own limbs copied -- the gather reads
+// them through the permutation), the fused baby-step kernel over groups of CB ciphertexts (pha_hoist_bsgs_batched.h), one mod-down of
+// 2 G cb polynomials, and the giant-step side on bsgs_core's kernels with the ciphertext where they have the row block.  A chunk of
+// one ciphertext is bsgs_core with one block.
+// No copy of the ciphertexts, in place included: the first write to out[b] is the combine kernel's, after the last read of ct[b] (by
+// the mod-up and the baby-step kernel of the same chunk, earlier on the stream); a later chunk reads only its own ciphertexts.
+// Scratch per call: chunk * (4 G |Ql| + (beta + 2 G + nk beta + 2) |QlP| + nk |Ql|) * N words + the pointer tables:
+//   tmp [2 G chunk][Ql][N] | mod-up [chunk][beta][QlP][N] | acc [chunk][G][2][QlP][N] | B [chunk][G][2][Ql][N] | g1 [chunk][nk][Ql][N] |
+//   giant mod-up [chunk][nk][beta][QlP][N] | cx [chunk][2][QlP][N] | tables (| a zero plane [QlP][N] for the missing weights)
+static void bsgs_batched_core(Context &c, size_t size_Ql, const u64 *ct, size_t batch, const uint32_t *baby_elts, size_t nb,
+                              const uint64_t *const *const *baby_glk, const uint32_t *giant_elts, size_t ng,
+                              const uint64_t *const *const *giant_glk, const uint64_t *const *weights, int scheme, u64 *out, size_t chunk,
+                              void *stream) {
+    check_level(c, size_Ql, true);
+    Tool &t = c.tool((uint32_t)size_Ql);
+    hipStream_t s = as_stream(stream);
+    const size_t n = c.n, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n, ct_words = 2 * ql_n, G = ng;
+    if (out != ct && overlaps(out, batch * ct_words, ct, batch * ct_words))
+        throw std::invalid_argument("out must be ct itself (in place) or must not overlap it");
+    // every refusal of bsgs_core, before the first launch
+    for (size_t j = 0; j < nb; j++) check_galois_elt(c, baby_elts[j]);
+    for (size_t i = 0; i < ng; i++) check_galois_elt(c, giant_elts[i]);
+    size_t nbk = 0, nk = 0;
+    for (size_t j = 0; j < nb; j++) {
+        if (baby_elts[j] != 1 && !baby_glk[j]) throw std::logic_error("Galois key not present in hoisting");
+        nbk += baby_elts[j] != 1;
+    }
+    for (size_t i = 0; i < ng; i++) {
+        if (giant_elts[i] != 1 && !giant_glk[i]) throw std::logic_error("Galois key not present in hoisting");
+        nk += giant_elts[i] != 1;
+    }
+    const size_t max_terms = acc_capacity(c);
+    if (nb + 1 > max_terms || nk * t.beta > max_terms || nbk > 255)
+        throw std::invalid_argument("too many steps for one call: the 128-bit accumulators hold floor(2^128 / q_max^2) - 1 products (at most "
+                                    "254 baby entries for primes up to 60 bits, 62 for 61-bit primes)");
+    if (2 * G > 65535 || nk * t.beta > 65535) throw std::invalid_argument("too many giant steps for one call");
+    if (t.beta > 4) throw std::invalid_argument("more than 4 key-switch digits are not supported by the baby-step / giant-step form");
+    if (strict_mode()) {
+        strict_operand(c, "hoisting ct", ct, rows_plain(0, size_Ql), (uint32_t)(2 * batch), ql_n, s);
+        for (size_t j = 0; j < nb; j++)
+            if (baby_glk[j]) strict_keys(c, "baby-step Galois key", baby_glk[j], t.beta, (uint32_t)size_Ql, s);
+        for (size_t i = 0; i < ng; i++)
+            if (giant_glk[i]) strict_keys(c, "giant-step Galois key", giant_glk[i], t.beta, (uint32_t)size_Ql, s);
+        for (size_t i = 0; i < G * nb; i++)
+            if (weights[i]) strict_operand(c, "BSGS weight", weights[i], rows_qlp(t.size_ql, c.size_q, c.size_p), 1, 0, s);
+    }
+    if (!chunk) chunk = 4;
+    chunk = std::min(std::min(chunk, batch), std::min((size_t)65535 / (2 * G), (size_t)65535 / std::max<size_t>(1, nk * t.beta)));
+    auto single = [&](size_t b) {
+        bsgs_core(c, t, ct + b * ct_words, 1, baby_elts, nb, baby_glk, giant_elts, ng, giant_glk, weights, out + b * ct_words, scheme, stream);
+    };
+    if (chunk == 1) {
+        for (size_t b = 0; b < batch; b++) single(b);
+        return;
+    }
+    bool any_null = false;
+    for (size_t i = 0; i < G * nb; i++) any_null = any_null || !weights[i];
+    std::vector<const void *> h_btab(nb), h_bkeys(nb), h_gtab(ng), h_gkeys;
+    std::vector<uint32_t> h_rank(ng);
+    for (size_t j = 0; j < nb; j++) {
+        h_btab[j] = c.galois_table(baby_elts[j]);
+        h_bkeys[j] = baby_elts[j] == 1 ? nullptr : baby_glk[j];
+    }
+    for (size_t i = 0; i < ng; i++) {
+        h_gtab[i] = c.galois_table(giant_elts[i]);
+        h_rank[i] = giant_elts[i] == 1 ? 0xffffffffu : (uint32_t)h_gkeys.size();
+        if (giant_elts[i] != 1) h_gkeys.push_back(giant_glk[i]);
+    }
+    const size_t ptr_words = 2 * nb + G * nb + 2 * ng + nk + (any_null ? qlp_n : 0);
+    u64 *base = c.scratch(stream, chunk * (4 * G * ql_n + ((size_t)t.beta + 2 * G + nk * t.beta + 2) * qlp_n + nk * ql_n) + ptr_words);
+    u64 *tmp = base, *t_mod_up = tmp + chunk * 2 * G * ql_n, *acc = t_mod_up + chunk * t.beta * qlp_n, *B = acc + chunk * G * 2 * qlp_n,
+        *g1 = B + chunk * G * 2 * ql_n, *mu_g = g1 + chunk * nk * ql_n, *cxg = mu_g + chunk * nk * t.beta * qlp_n,
+        *d_ptrs = cxg + chunk * 2 * qlp_n;
+    u64 *p_btab = d_ptrs, *p_bkeys = p_btab + nb, *p_w = p_bkeys + nb, *p_gtab = p_w + G * nb, *p_rank = p_gtab + ng, *p_gkeys = p_rank + ng;
+    PHA_HIP(hipMemcpyAsync(p_btab, h_btab.data(), nb * sizeof(void *), hipMemcpyHostToDevice, s));
+    PHA_HIP(hipMemcpyAsync(p_bkeys, h_bkeys.data(), nb * sizeof(void *), hipMemcpyHostToDevice, s));
+    std::vector<const void *> h_w(weights, weights + G * nb);
+    if (any_null) {
+        u64 *zero = p_gkeys + nk;
+        PHA_HIP(hipMemsetAsync(zero, 0, qlp_n * sizeof(u64), s));
+        for (auto &w : h_w)
+            if (!w) w = zero;
+    }
+    PHA_HIP(hipMemcpyAsync(p_w, h_w.data(), G * nb * sizeof(void *), hipMemcpyHostToDevice, s));
+    PHA_HIP(hipMemcpyAsync(p_gtab, h_gtab.data(), ng * sizeof(void *), hipMemcpyHostToDevice, s));
+    PHA_HIP(hipMemcpyAsync(p_rank, h_rank.data(), ng * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    if (nk) PHA_HIP(hipMemcpyAsync(p_gkeys, h_gkeys.data(), nk * sizeof(void *), hipMemcpyHostToDevice, s));
+    const u64 *const *const *d_gkeys = reinterpret_cast<const u64 *const *const *>(p_gkeys);
+
+    BsgsBArgs k{};
+    k.acc = acc; k.t_mod_up = t_mod_up; k.keys = reinterpret_cast<const u64 *const *const *>(p_bkeys);
+    k.tables = reinterpret_cast<const uint32_t *const *>(p_btab); k.weights = reinterpret_cast<const u64 *const *>(p_w);
+    k.mod = c.d_mod.p; k.qlp_prime = t.d_qlp_prime.p; k.n = (uint32_t)n; k.beta = t.beta; k.nb = (uint32_t)nb; k.g_total = (uint32_t)G;
+    k.qlp_n = qlp_n; k.qp_n = (size_t)c.size_qp * n; k.cc_stride = ct_words; k.p_mod_q = t.p_mod_q2.p; k.ql = (uint32_t)size_Ql;
+    k.ql_n = ql_n; k.fpinfo = reinterpret_cast<const BsgsBFp *>(c.d_fpinfo.p);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t cb = std::min(chunk, batch - b0);
+        if (cb == 1) {   // (the last chunk; nothing below uses this call's scratch any more)
+            single(b0);
+            break;
+        }
+        const u64 *in = ct + b0 * ct_words;
+        u64 *o = out + b0 * ct_words;
+        if (nbk) modup(c, t, t_mod_up, in + ql_n, scheme, tmp, s, (uint32_t)cb, ct_words, nullptr, false);
+        k.cc = in; k.n_ct = (uint32_t)cb;
+        for (size_t g0 = 0; g0 < G;) {
+            const size_t left = G - g0;
+            k.g0 = (uint32_t)g0;
+            with_beta<4>(t.beta, [&](auto Bt) {   // (beta <= 4: checked above)
+                constexpr int BETA = decltype(Bt)::value;
+                auto launch = [&](auto Ng) {
+                    constexpr int NG = decltype(Ng)::value, CB = hoist_bsgs_batched_cb(BETA, NG);
+                    const dim3 grid((unsigned)(n / 256), t.size_qlp, (unsigned)((cb + CB - 1) / CB));
+                    hipLaunchKernelGGL((hoist_bsgs_batched_kernel<NG, CB, BETA>), grid, dim3(256), 0, s, k);
+                    g0 += NG;
+                };
+                if (left >= 16) launch(std::integral_constant<int, 16>{});
+                else if (left >= 8) launch(std::integral_constant<int, 8>{});
+                else if (left >= 4) launch(std::integral_constant<int, 4>{});
+                else if (left >= 2) launch(std::integral_constant<int, 2>{});
+                else launch(std::integral_constant<int, 1>{});
+            });
+            check_launch();
+        }
+        moddown_from_ntt(c, t, B, ql_n, acc, qlp_n, (uint32_t)(2 * G * cb), scheme, false, tmp, s);
+        hipLaunchKernelGGL(bsgs_combine_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql, (unsigned)cb), dim3(256), 0, s, o, g1, B,
+                           reinterpret_cast<const uint32_t *const *>(p_gtab), reinterpret_cast<const uint32_t *>(p_rank), (uint32_t)ng,
+                           (uint32_t)nk, c.d_mod.p, (uint32_t)n, ql_n);
+        check_launch();
+        if (nk) {
+            modup(c, t, mu_g, g1, scheme, tmp, s, (uint32_t)(cb * nk));
+            MultiInnerArgs m{cxg, mu_g, d_gkeys, c.d_mod.p, t.d_qlp_prime.p, (uint32_t)n, t.beta, (uint32_t)nk, qlp_n, (size_t)c.size_qp * n};
+            hipLaunchKernelGGL(inner_prod_multi_kernel, dim3((unsigned)(n / 512), t.size_qlp, (unsigned)cb), dim3(256), 0, s, m);
+            check_launch();
+            moddown_from_ntt(c, t, o, ql_n, cxg, qlp_n, (uint32_t)(2 * cb), scheme, true, tmp, s);
+        }
     }
 }
 
@@ -870,6 +1025,20 @@ int pha_hoisting_weighted_bsgs(pha_context_t ctx, size_t size_Ql, uint64_t *ct, 
     Context &c = ctx->c;
     check_level(c, size_Ql, true);
     bsgs_core(c, c.tool((uint32_t)size_Ql), ct, 1, baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights, ct, scheme, stream);
+    PHA_API_END
+}
+
+int pha_hoisting_weighted_bsgs_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t batch, const uint32_t *baby_elts,
+                                       size_t n_baby, const uint64_t *const *const *baby_glk, const uint32_t *giant_elts, size_t n_giant,
+                                       const uint64_t *const *const *giant_glk, const uint64_t *const *weights, int scheme, uint64_t *out,
+                                       size_t chunk, void *stream) {
+    PHA_CTX_BEGIN(ctx)
+    need(ct); need(baby_elts); need(baby_glk); need(giant_elts); need(giant_glk); need(weights); need(out);
+    if (n_baby == 0 || n_giant == 0) throw std::invalid_argument("steps must not be empty");
+    if (!ntt_domain_scheme(scheme)) throw std::invalid_argument("weighted hoisting takes NTT-form ciphertexts (ckks / bgv)");
+    if (batch == 0) return 0;
+    bsgs_batched_core(ctx->c, size_Ql, ct, batch, baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights, scheme, out, chunk,
+                      stream);
     PHA_API_END
 }
 

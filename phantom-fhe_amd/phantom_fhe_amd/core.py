@@ -663,6 +663,27 @@ class PhantomContext:
                                                          int(scheme), _ptr(out), chunk, _stream()))
         return out
 
+    def hoisting_weighted_bsgs_batched(self, size_Ql, ct, baby_elts, baby_keys, giant_elts, giant_keys, weights, scheme, out=None, chunk=0):
+        """pha_hoisting_weighted_bsgs_batched: the baby-step / giant-step form for a batch ct [B][2][Ql][N] that shares the keys and
+        the weights [n_giant][n_baby] (as hoisting_weighted_bsgs takes them); every out[b] is word for word what
+        hoisting_weighted_bsgs() makes of ct[b].  out=None allocates, out=ct works in place; `chunk` ciphertexts go through one set
+        of launches (0: the library's default, 4).  Returns out."""
+        if out is None:
+            out = torch.empty_like(ct)
+        if ct.shape[0] == 0:             # (an empty tensor has no device pointer to hand over)
+            return out
+        be = (C.c_uint32 * len(baby_elts))(*[int(e) for e in baby_elts])
+        ge = (C.c_uint32 * len(giant_elts))(*[int(e) for e in giant_elts])
+        bk = (C.c_void_p * len(baby_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in baby_keys])
+        gk = (C.c_void_p * len(giant_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in giant_keys])
+        flat = [w for row in weights for w in row]
+        if len(flat) != len(baby_elts) * len(giant_elts):
+            raise ValueError("weights must be [n_giant][n_baby]")
+        ws = (C.c_void_p * len(flat))(*[_ptr(w) for w in flat])
+        _lib.check(self._L.pha_hoisting_weighted_bsgs_batched(self._h, size_Ql, _ptr(ct), ct.shape[0], be, len(baby_elts), bk, ge,
+                                                              len(giant_elts), gk, ws, int(scheme), _ptr(out), chunk, _stream()))
+        return out
+
     def divide_and_round_q_last_ntt(self, size_Ql, src, cipher_size, dst):
         _lib.check(self._L.pha_divide_and_round_q_last_ntt(self._h, size_Ql, _ptr(src), cipher_size, _ptr(dst),
                                                            _stream()))

@@ -124,6 +124,8 @@ _SIGS = {
     "pha_hoisting_weighted": [vp, sz, vp, C.POINTER(C.c_uint32), sz, C.POINTER(vp), C.POINTER(vp), C.c_int, vp],
     "pha_hoisting_weighted_bsgs": [vp, sz, vp, C.POINTER(C.c_uint32), sz, C.POINTER(vp), C.POINTER(C.c_uint32), sz, C.POINTER(vp),
                                    C.POINTER(vp), C.c_int, vp],
+    "pha_hoisting_weighted_bsgs_batched": [vp, sz, vp, sz, C.POINTER(C.c_uint32), sz, C.POINTER(vp), C.POINTER(C.c_uint32), sz, C.POINTER(vp),
+                                           C.POINTER(vp), C.c_int, vp, sz, vp],
     "pha_hoisting_weighted_bsgs_blocks": [vp, sz, vp, sz, C.POINTER(C.c_uint32), sz, C.POINTER(vp), C.POINTER(C.c_uint32), sz, C.POINTER(vp),
                                           C.POINTER(vp), vp, C.c_int, vp],
     "pha_hoisting_batched": [vp, sz, vp, sz, C.POINTER(C.c_uint32), sz, C.POINTER(vp), C.c_int, vp, sz, vp],

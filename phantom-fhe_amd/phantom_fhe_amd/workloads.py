@@ -92,6 +92,14 @@ def diag_matvec_bsgs(ctx, size_Ql, ct, baby_elts, baby_keys, giant_elts, giant_k
     return out
 
 
+def diag_matvec_bsgs_batch(ctx, size_Ql, cts, baby_elts, baby_keys, giant_elts, giant_keys, diagonals, scheme, chunk=0):
+    """The baby-step / giant-step block applied to a batch of encrypted vectors cts [B][2][Ql][N]
+    (pha_hoisting_weighted_bsgs_batched): the baby keys and the diagonals are read once per group of ciphertexts instead of once per
+    vector.  `chunk` vectors go through one set of launches (0: the library's default).  Returns [B][2][Ql][N]; every result equals
+    diag_matvec_bsgs of that vector."""
+    return ctx.hoisting_weighted_bsgs_batched(size_Ql, cts, baby_elts, baby_keys, giant_elts, giant_keys, diagonals, scheme, chunk=chunk)
+
+
 def diag_matvec_bsgs_blocks(ctx, size_Ql, ct, baby_elts, baby_keys, giant_elts, giant_keys, blocks, scheme, per_call=0):
     """Several row blocks of the matrix against ONE encrypted vector (pha_hoisting_weighted_bsgs_blocks): blocks[r][i][j] as in
     diag_matvec_bsgs.  `per_call` blocks go through one call (0: as many as make 16 (block, giant step) accumulators, the width of
