@@ -3,14 +3,22 @@
 // a batch of ciphertexts that share the keys (pha_hoisting_batched, pha_hoisting_weighted_batched), and the baby-step / giant-step
 // form for such a batch (pha_hoisting_weighted_bsgs_batched).
 //
+// Two host drivers stand behind the seven entries.  hoist_batched_core() runs the plain and the weighted form: the single entries are
+// a batch of one, in place, and a chunk of one ciphertext takes the one-ciphertext kernels.  The three BSGS entries build one BsgsCall
+// (the plan of pha_hoist_plan.h: refusals, counts, host tables; the scratch claim; the upload) and run bsgs_baby_steps() and
+// bsgs_giant_side() per set of row blocks or per chunk of ciphertexts.  Every entry claims its scratch once and no driver calls
+// another.
+//
 // Reference: src/evaluate.cu:1670-1866.  The mod-up, the mod-down and the Galois launchers these entries call live in pha_rns.hip
 // (declared in pha_internal.h).
 #include "../../include/phantom_amd.h"
 #include "pha_internal.h"
 #include "pha_hoist_batched.h"
 #include "pha_hoist_bsgs_batched.h"
+#include "pha_hoist_plan.h"
 #include <algorithm>
 #include <cstddef>
+#include <cstring>
 
 namespace pha {
 // ---- hoisted rotations (src/evaluate.cu:1670-1866): for every output coefficient, sum over the Galois
@@ -389,27 +397,31 @@ static size_t acc_capacity(const Context &c) {
     return qbits >= 64 ? 1 : ((size_t)1 << std::min(20, 128 - 2 * qbits)) - 1;
 }
 
-// All rotations' inner products in one kernel per `per_call` Galois elements; a later launch adds to what cx holds.
-// d_w != null: the weighted form.
-static void launch_hoist_inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const u64 *const *const *d_keys,
-                                    const uint32_t *const *d_tabs, const u64 *const *d_w, size_t n_elts, size_t per_call,
-                                    hipStream_t s) {
-    const dim3 grid((unsigned)(c.n / 512), t.size_qlp), block(256);
-    for (size_t e0 = 0; e0 < n_elts; e0 += per_call) {
-        HoistWArgs k{};
-        k.cx = cx; k.t_mod_up = t_mod_up; k.keys = d_keys + e0; k.tables = d_tabs + e0; k.mod = c.d_mod.p;
-        k.qlp_prime = t.d_qlp_prime.p; k.n = (uint32_t)c.n; k.beta = t.beta;
-        k.n_elts = (uint32_t)std::min(per_call, n_elts - e0); k.accumulate = e0 ? 1 : 0;
-        k.qlp_n = (size_t)t.size_qlp * c.n; k.qp_n = (size_t)c.size_qp * c.n;
-        k.weights = d_w ? d_w + e0 : nullptr;
-        with_beta<0>(t.beta, [&](auto B) {
-            constexpr int BETA = decltype(B)::value;
-            if (d_w) hipLaunchKernelGGL((hoist_inner_prod_kernel<BETA, true>), grid, block, 0, s, k);
-            else hipLaunchKernelGGL((hoist_inner_prod_kernel<BETA, false>), grid, block, 0, s, static_cast<const HoistArgs &>(k));
-        });
-        check_launch();
+// The pointer tables of a call: host lists gathered into one buffer that upload() copies to `dev` (scratch words) in one go; add()
+// hands back the typed device address the list will have there.
+class PtrTable {
+    std::vector<u64> host;
+    u64 *dev;
+
+public:
+    explicit PtrTable(u64 *d) : dev(d) {}
+    template <class T>
+    const T *add(const std::vector<const void *> &list) {
+        const T *at = reinterpret_cast<const T *>(dev + host.size());
+        for (const void *p : list) host.push_back((u64)(uintptr_t)p);
+        return at;
     }
-}
+    const uint32_t *add(const std::vector<uint32_t> &list) {   // two entries per word
+        const uint32_t *at = reinterpret_cast<const uint32_t *>(dev + host.size());
+        host.resize(host.size() + (list.size() + 1) / 2);
+        std::memcpy(host.data() + host.size() - (list.size() + 1) / 2, list.data(), list.size() * sizeof(uint32_t));
+        return at;
+    }
+    size_t words() const { return host.size(); }
+    void upload(hipStream_t s) const {
+        if (!host.empty()) PHA_HIP(hipMemcpyAsync(dev, host.data(), host.size() * sizeof(u64), hipMemcpyHostToDevice, s));
+    }
+};
 
 // ---- hoisted rotations of a batch of ciphertexts that share keys, tables and weights (pha_hoisting_batched,
 //      pha_hoisting_weighted_batched).  The thread program is pha_hoist_batched.h (replayed on the CPU by tests/emu): one thread
@@ -483,33 +495,72 @@ __global__ __launch_bounds__(256) void hoist_weighted_c_batched_kernel(u64 *dst,
         if (j < cnt) dst[(size_t)(first + j) * dst_stride + p * poly_stride + id] = barrett128(lo[j], hi[j], m);
 }
 
-// The gather + inner products of `n_ct` >= 2 ciphertexts (t_mod_up [n_ct][beta][QlP][N] -> cx [n_ct][2][QlP][N]), `per_call` Galois
-// elements per launch as launch_hoist_inner_prod.
-static void launch_hoist_inner_prod_batched(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const u64 *const *const *d_keys,
-                                            const uint32_t *const *d_tabs, const u64 *const *d_w, size_t n_elts, size_t per_call,
-                                            size_t n_ct, hipStream_t s) {
+// All rotations' gather + inner products of n_ct ciphertexts (t_mod_up [n_ct][beta][QlP][N] -> cx [n_ct][2][QlP][N]) in one kernel per
+// `per_call` Galois elements; a later launch adds to what cx holds.  d_w != null: the weighted form.  One ciphertext takes the
+// one-ciphertext kernel, more take the batched one over groups of CB.
+static void launch_hoist_inner_prod(Context &c, Tool &t, u64 *cx, const u64 *t_mod_up, const u64 *const *const *d_keys,
+                                    const uint32_t *const *d_tabs, const u64 *const *d_w, size_t n_elts, size_t per_call, size_t n_ct,
+                                    hipStream_t s) {
+    const unsigned gx = (unsigned)(c.n / 512);
     for (size_t e0 = 0; e0 < n_elts; e0 += per_call) {
-        HoistBArgs k{};
-        k.cx = cx; k.t_mod_up = t_mod_up; k.keys = d_keys + e0; k.tables = d_tabs + e0; k.weights = d_w ? d_w + e0 : nullptr;
-        k.mod = c.d_mod.p; k.qlp_prime = t.d_qlp_prime.p; k.n = (uint32_t)c.n; k.beta = t.beta;
-        k.n_elts = (uint32_t)std::min(per_call, n_elts - e0); k.accumulate = e0 ? 1 : 0; k.n_ct = (uint32_t)n_ct;
-        k.qlp_n = (size_t)t.size_qlp * c.n; k.qp_n = (size_t)c.size_qp * c.n;
-        with_beta<0>(t.beta, [&](auto B) {
-            constexpr int BETA = decltype(B)::value;
-            constexpr int CBP = hoist_batched_cb(BETA, false), CBW = hoist_batched_cb(BETA, true);
-            const unsigned cb = d_w ? CBW : CBP;
-            const dim3 grid((unsigned)(c.n / 512), t.size_qlp, (unsigned)((n_ct + cb - 1) / cb)), block(256);
-            if (d_w) hipLaunchKernelGGL((hoist_inner_prod_batched_kernel<BETA, CBW, true>), grid, block, 0, s, k);
-            else hipLaunchKernelGGL((hoist_inner_prod_batched_kernel<BETA, CBP, false>), grid, block, 0, s, k);
-        });
+        HoistWArgs k{};
+        HoistBArgs kb{};
+        auto fill = [&](auto &x) {
+            x.cx = cx; x.t_mod_up = t_mod_up; x.keys = d_keys + e0; x.tables = d_tabs + e0; x.weights = d_w ? d_w + e0 : nullptr;
+            x.mod = c.d_mod.p; x.qlp_prime = t.d_qlp_prime.p; x.n = (uint32_t)c.n; x.beta = t.beta;
+            x.n_elts = (uint32_t)std::min(per_call, n_elts - e0); x.accumulate = e0 ? 1 : 0;
+            x.qlp_n = (size_t)t.size_qlp * c.n; x.qp_n = (size_t)c.size_qp * c.n;
+        };
+        fill(k);
+        fill(kb);
+        kb.n_ct = (uint32_t)n_ct;
+        if (n_ct == 1)
+            with_beta<0>(t.beta, [&](auto B) {
+                constexpr int BETA = decltype(B)::value;
+                const dim3 grid(gx, t.size_qlp), block(256);
+                if (d_w) hipLaunchKernelGGL((hoist_inner_prod_kernel<BETA, true>), grid, block, 0, s, k);
+                else hipLaunchKernelGGL((hoist_inner_prod_kernel<BETA, false>), grid, block, 0, s, static_cast<const HoistArgs &>(k));
+            });
+        else
+            with_beta<0>(t.beta, [&](auto B) {
+                constexpr int BETA = decltype(B)::value;
+                constexpr int CBP = hoist_batched_cb(BETA, false), CBW = hoist_batched_cb(BETA, true);
+                const unsigned cb = d_w ? CBW : CBP;
+                const dim3 grid(gx, t.size_qlp, (unsigned)((n_ct + cb - 1) / cb)), block(256);
+                if (d_w) hipLaunchKernelGGL((hoist_inner_prod_batched_kernel<BETA, CBW, true>), grid, block, 0, s, kb);
+                else hipLaunchKernelGGL((hoist_inner_prod_batched_kernel<BETA, CBP, false>), grid, block, 0, s, kb);
+            });
         check_launch();
     }
 }
 
-// Driver of both batched entries (weights == null: the plain form).  Per chunk of cb ciphertexts: one mod-up of beta * cb digits (the
-// digits' own limbs copied into t_mod_up -- the gather reads them through the permutation, so modup's own_in_place is off here whatever
-// the key switch's own_in_place_ok() says), the inner-product launches, the c0 / (c0, c1) sums into out, one mod-down of 2 * cb
-// polynomials added to them.  A chunk of one ciphertext runs the single entries' launches.
+// The sums over c0 (d_w == null, NTT form: dst c0 = sum_e galois_e(c0), dst c1 = 0) or over (c0, c1) with the weights, for n_ct
+// ciphertexts at dst + b * [2][Ql][N], read from src + b * src_stride: the one-ciphertext kernels for n_ct = 1, their batched twins else.
+static void launch_hoist_c_sums(Context &c, size_t size_Ql, u64 *dst, const u64 *src, size_t src_stride, const uint32_t *const *d_tabs,
+                                const u64 *const *d_w, size_t n_elts, size_t n_ks, size_t n_ct, hipStream_t s) {
+    const uint32_t n = (uint32_t)c.n;
+    const size_t ql_n = size_Ql * n;
+    const unsigned gx = n / 256, gy = (unsigned)size_Ql, groups = (unsigned)((n_ct + kHoistCGroup - 1) / kHoistCGroup);
+    if (d_w && n_ct == 1)
+        hipLaunchKernelGGL(hoist_weighted_c_kernel, dim3(gx, gy, 2), dim3(256), 0, s, dst, src, d_tabs, d_w, (uint32_t)n_elts, (uint32_t)n_ks,
+                           c.d_mod.p, n, ql_n);
+    else if (d_w)
+        hipLaunchKernelGGL(hoist_weighted_c_batched_kernel, dim3(gx, gy, 2 * groups), dim3(256), 0, s, dst, 2 * ql_n, src, src_stride, d_tabs,
+                           d_w, (uint32_t)n_elts, (uint32_t)n_ks, c.d_mod.p, n, (uint32_t)n_ct, ql_n);
+    else if (n_ct == 1)
+        hipLaunchKernelGGL(hoist_c0_kernel, dim3(gx, gy), dim3(256), 0, s, dst, src, d_tabs, (uint32_t)n_elts, c.d_mod.p, n);
+    else
+        hipLaunchKernelGGL(hoist_c0_batched_kernel, dim3(gx, gy, groups), dim3(256), 0, s, dst, 2 * ql_n, src, src_stride, d_tabs,
+                           (uint32_t)n_elts, c.d_mod.p, n, (uint32_t)n_ct, ql_n);
+    check_launch();
+    if (!d_w && n_ct == 1) PHA_HIP(hipMemsetAsync(dst + ql_n, 0, ql_n * sizeof(u64), s));   // (the batched twin writes c1 = 0 itself)
+}
+
+// Driver of the plain and the weighted form (weights == null: plain), single entries (a batch of one, in place) and batched ones.  Per
+// chunk of cb ciphertexts: one mod-up of beta * cb digits (the digits' own limbs copied into t_mod_up -- the gather reads them through
+// the permutation, so modup's own_in_place is off here whatever the key switch's own_in_place_ok() says), the inner-product launches,
+// the c0 / (c0, c1) sums into out, one mod-down of 2 * cb polynomials added to them.  A chunk of one ciphertext takes the
+// one-ciphertext kernels.
 // Scratch: KsScratch of `chunk` ciphertexts | copy of the chunk's c0 [chunk][Ql][N] (plain; in place or bfv) resp. (c0, c1)
 // [chunk][2][Ql][N] (weighted, in place) | pointer tables.
 static void hoist_batched_core(Context &c, size_t size_Ql, const u64 *ct, size_t batch, const uint32_t *galois_elts, size_t n_elts,
@@ -555,17 +606,17 @@ static void hoist_batched_core(Context &c, size_t size_Ql, const u64 *ct, size_t
             }
         }
     const size_t copy_polys = weighted ? (in_place ? 2 : 0) : ((in_place || !ntt_dom) ? 1 : 0);
-    const size_t ks_words = KsScratch::words(c, t, chunk), ptr_words = 3 * n_elts;
-    u64 *base = c.scratch(stream, ks_words + chunk * copy_polys * ql_n + ptr_words);
+    const size_t ks_words = KsScratch::words(c, t, chunk), copy_words = chunk * copy_polys * ql_n;
+    u64 *base = c.scratch(stream, ks_words + copy_words + tabs.size() + w_all.size() + keys.size());
     const KsScratch k(base, c, t, chunk);
-    u64 *cc = base + ks_words, *d_ptrs = cc + chunk * copy_polys * ql_n;
-    PHA_HIP(hipMemcpyAsync(d_ptrs, tabs.data(), n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
-    if (weighted) PHA_HIP(hipMemcpyAsync(d_ptrs + n_elts, w_all.data(), n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
-    if (n_ks) PHA_HIP(hipMemcpyAsync(d_ptrs + 2 * n_elts, keys.data(), n_ks * sizeof(void *), hipMemcpyHostToDevice, s));
-    const uint32_t *const *d_tabs = reinterpret_cast<const uint32_t *const *>(d_ptrs);
-    const u64 *const *d_w = weighted ? reinterpret_cast<const u64 *const *>(d_ptrs + n_elts) : nullptr;
-    const u64 *const *const *d_keys = reinterpret_cast<const u64 *const *const *>(d_ptrs + 2 * n_elts);
-    // plain: acc_capacity / beta elements per launch; weighted: 63, whatever the primes (pha_hoisting_weighted)
+    u64 *cc = base + ks_words;
+    PtrTable ptrs(cc + copy_words);
+    const uint32_t *const *d_tabs = ptrs.add<const uint32_t *>(tabs);
+    const u64 *const *d_w = weighted ? ptrs.add<const u64 *>(w_all) : nullptr;
+    const u64 *const *const *d_keys = ptrs.add<const u64 *const *>(keys);
+    ptrs.upload(s);
+    // plain: acc_capacity / beta elements per launch.  Weighted: 63, whatever the primes: an element adds ONE reduced sum times a
+    // weight, below 2^122 for the 61-bit primes the context accepts at most, so 63 of them fit (acc_capacity() / beta would split earlier)
     const size_t per_call = weighted ? 63 : std::max<size_t>(1, acc_capacity(c) / t.beta);
 
     for (size_t b0 = 0; b0 < batch; b0 += chunk) {
@@ -579,37 +630,17 @@ static void hoist_batched_core(Context &c, size_t size_Ql, const u64 *ct, size_t
             PHA_HIP(hipMemcpyAsync(cc, in, cb * ct_words * sizeof(u64), hipMemcpyDeviceToDevice, s));
             src = cc;
         } else if (copy_polys == 1) {
-            PHA_HIP(hipMemcpy2DAsync(cc, ql_n * sizeof(u64), in, ct_words * sizeof(u64), ql_n * sizeof(u64), cb, hipMemcpyDeviceToDevice, s));
+            if (cb == 1) PHA_HIP(hipMemcpyAsync(cc, in, ql_n * sizeof(u64), hipMemcpyDeviceToDevice, s));
+            else PHA_HIP(hipMemcpy2DAsync(cc, ql_n * sizeof(u64), in, ct_words * sizeof(u64), ql_n * sizeof(u64), cb, hipMemcpyDeviceToDevice, s));
             src = cc;
             src_stride = ql_n;
         }
         if (n_ks) {
             modup(c, t, k.t_mod_up, in + ql_n, scheme, k.tmp, s, (uint32_t)cb, ct_words, nullptr, false);
-            if (cb == 1) launch_hoist_inner_prod(c, t, k.cx, k.t_mod_up, d_keys, d_tabs, d_w, n_ks, per_call, s);
-            else launch_hoist_inner_prod_batched(c, t, k.cx, k.t_mod_up, d_keys, d_tabs, d_w, n_ks, per_call, cb, s);
+            launch_hoist_inner_prod(c, t, k.cx, k.t_mod_up, d_keys, d_tabs, d_w, n_ks, per_call, cb, s);
         }
-        if (weighted) {
-            if (cb == 1)
-                hipLaunchKernelGGL(hoist_weighted_c_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql, 2), dim3(256), 0, s, o, src, d_tabs,
-                                   d_w, (uint32_t)n_elts, (uint32_t)n_ks, c.d_mod.p, (uint32_t)n, ql_n);
-            else
-                hipLaunchKernelGGL(hoist_weighted_c_batched_kernel,
-                                   dim3((unsigned)(n / 256), (unsigned)size_Ql, (unsigned)(2 * ((cb + kHoistCGroup - 1) / kHoistCGroup))),
-                                   dim3(256), 0, s, o, ct_words, src, src_stride, d_tabs, d_w, (uint32_t)n_elts, (uint32_t)n_ks, c.d_mod.p,
-                                   (uint32_t)n, (uint32_t)cb, ql_n);
-            check_launch();
-        } else if (ntt_dom) {
-            if (cb == 1) {
-                hipLaunchKernelGGL(hoist_c0_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql), dim3(256), 0, s, o, src, d_tabs,
-                                   (uint32_t)n_elts, c.d_mod.p, (uint32_t)n);
-                check_launch();
-                PHA_HIP(hipMemsetAsync(o + ql_n, 0, ql_n * sizeof(u64), s));
-            } else {
-                hipLaunchKernelGGL(hoist_c0_batched_kernel,
-                                   dim3((unsigned)(n / 256), (unsigned)size_Ql, (unsigned)((cb + kHoistCGroup - 1) / kHoistCGroup)), dim3(256),
-                                   0, s, o, ct_words, src, src_stride, d_tabs, (uint32_t)n_elts, c.d_mod.p, (uint32_t)n, (uint32_t)cb, ql_n);
-                check_launch();
-            }
+        if (ntt_dom) {
+            launch_hoist_c_sums(c, size_Ql, o, src, src_stride, d_tabs, d_w, n_elts, n_ks, cb, s);
         } else {
             // coefficient-domain automorphism (src/galois.cu:20-39) of the chunk's dense c0 copy, one launch per element, and the adds
             PHA_HIP(hipMemsetAsync(o, 0, cb * ct_words * sizeof(u64), s));
@@ -634,269 +665,162 @@ __global__ __launch_bounds__(256) void hoist_bsgs_batched_kernel(const BsgsBArgs
     hoist_bsgs_batched_thread<NG, CB, BETA>(k, blockIdx.x * 256 + threadIdx.x, blockIdx.y, blockIdx.z);
 }
 
+// ---- host side of the BSGS entries.  Block r (or ciphertext r) with weights w[i][j] gives out[r] = sum_i rot_{G_i}(sum_j w[i][j] (.)
+//      rot_{B_j}(ct)).  The fused baby-step kernels treat the (unit, giant step) pairs as one list of accumulators, so the baby keys,
+//      the gathered digits and the per-baby reductions are paid once for up to 16 of them; everything after them is batched over the
+//      units.  Every unit's result is bit-identical to a call of its own. ----
+
+// The plan of one API call (pha_hoist_plan.h): every refusal, then the strict-mode walk over n_ct ciphertexts, before the first launch
+static BsgsPlan bsgs_plan(Context &c, Tool &t, const u64 *ct, size_t n_ct, const BsgsSteps &a, size_t lists, size_t units,
+                          const char *unit_name, hipStream_t s) {
+    BsgsPlan p(c.n, t.beta, acc_capacity(c), a, lists, units, unit_name, [&](uint32_t elt) { return c.galois_table(elt); });
+    if (strict_mode()) {
+        strict_operand(c, "hoisting ct", ct, rows_plain(0, t.size_ql), (uint32_t)(2 * n_ct), (size_t)t.size_ql * c.n, s);
+        for (size_t j = 0; j < a.nb; j++)
+            if (a.baby_glk[j]) strict_keys(c, "baby-step Galois key", a.baby_glk[j], t.beta, t.size_ql, s);
+        for (size_t i = 0; i < a.ng; i++)
+            if (a.giant_glk[i]) strict_keys(c, "giant-step Galois key", a.giant_glk[i], t.beta, t.size_ql, s);
+        for (size_t i = 0; i < lists * a.nb; i++)
+            if (a.weights[i]) strict_operand(c, "BSGS weight", a.weights[i], rows_qlp(t.size_ql, c.size_q, c.size_p), 1, 0, s);
+    }
+    return p;
+}
+
+// One API call on the device: the call's one scratch claim -- `units` row blocks of one ciphertext (cts = 1) or a chunk of `units`
+// ciphertexts (cts = units) -- with the plan's tables uploaded into its pointer region.
+struct BsgsCall {
+    Context &c;
+    Tool &t;
+    const BsgsPlan &p;
+    const int scheme;
+    const hipStream_t s;
+    const size_t n, ql_n, qlp_n;
+    const BsgsScratch::Dims dims;
+    const BsgsScratch m;
+    const uint32_t *const *d_btab, *const *d_gtab, *d_rank;
+    const u64 *const *const *d_bkeys, *const *const *d_gkeys;
+    const u64 *const *d_w;
+
+    BsgsCall(Context &c_, Tool &t_, const BsgsPlan &p_, size_t units, size_t cts, int scheme_, void *stream)
+        : c(c_), t(t_), p(p_), scheme(scheme_), s(as_stream(stream)), n(c_.n), ql_n((size_t)t_.size_ql * n), qlp_n((size_t)t_.size_qlp * n),
+          dims{ql_n, qlp_n, t_.beta, units, cts, p_.nb, p_.ng, p_.nk, p_.lists, p_.any_null},
+          m(c_.scratch(stream, BsgsScratch::words(dims)), dims) {
+        std::vector<const void *> w = p.weights;
+        if (p.any_null) {   // missing weights point at a zero plane
+            PHA_HIP(hipMemsetAsync(m.zero, 0, qlp_n * sizeof(u64), s));
+            for (auto &x : w)
+                if (!x) x = m.zero;
+        }
+        PtrTable ptrs(m.ptrs);
+        d_btab = ptrs.add<const uint32_t *>(p.btab);
+        d_bkeys = ptrs.add<const u64 *const *>(p.bkeys);
+        d_w = ptrs.add<const u64 *>(w);
+        d_gtab = ptrs.add<const uint32_t *>(p.gtab);
+        d_gkeys = ptrs.add<const u64 *const *>(p.gkeys);
+        d_rank = ptrs.add(p.rank);
+        if (ptrs.words() > BsgsScratch::ptr_words(dims)) throw std::logic_error("BSGS pointer tables do not fit their region");
+        ptrs.upload(s);
+    }
+};
+
+// Baby steps of `cts` ciphertexts at `in`: one mod-up of their c1 polynomials (the digits' own limbs copied -- the gather reads them
+// through the permutation), then every accumulator list's weighted sum of the hoisted inner products (and of the c0 / c1 terms,
+// pre-multiplied by P) into acc, in one pass over the baby keys per NG lists: the one-ciphertext kernel over the plan's lists (the
+// (row block, giant step) pairs), or the batched kernel over groups of CB ciphertexts with ng lists each (pha_hoist_bsgs_batched.h).
+static void bsgs_baby_steps(const BsgsCall &b, const u64 *in, size_t cts) {
+    Context &c = b.c;
+    Tool &t = b.t;
+    const BsgsPlan &p = b.p;
+    const size_t n = b.n;
+    if (p.nbk) modup(c, t, b.m.t_mod_up, in + b.ql_n, b.scheme, b.m.tmp, b.s, (uint32_t)cts, 2 * b.ql_n, nullptr, false);
+    BsgsArgs k{};     // the one-ciphertext kernel's arguments and the batched kernel's: the same fields, the batch's on top
+    BsgsBArgs kb{};
+    auto fill = [&](auto &x) {
+        x.acc = b.m.acc; x.t_mod_up = b.m.t_mod_up; x.keys = b.d_bkeys; x.tables = b.d_btab; x.weights = b.d_w; x.mod = c.d_mod.p;
+        x.qlp_prime = t.d_qlp_prime.p; x.n = (uint32_t)n; x.beta = t.beta; x.nb = (uint32_t)p.nb; x.qlp_n = b.qlp_n;
+        x.qp_n = (size_t)c.size_qp * n; x.cc = in; x.p_mod_q = t.p_mod_q2.p; x.ql = t.size_ql; x.ql_n = b.ql_n;
+    };
+    fill(k);
+    fill(kb);
+    k.fpinfo = c.d_fpinfo.p;
+    kb.fpinfo = reinterpret_cast<const BsgsBFp *>(c.d_fpinfo.p);
+    kb.g_total = (uint32_t)p.lists; kb.cc_stride = 2 * b.ql_n; kb.n_ct = (uint32_t)cts;
+    // NG lists per launch, from list g0 on: launch(BETA, NG) issues one kernel
+    auto ladder = [&](auto &&launch) {
+        for (size_t g0 = 0; g0 < p.lists;) {
+            k.g0 = kb.g0 = (uint32_t)g0;
+            with_beta<4>(t.beta, [&](auto Bt) {   // (beta <= 4: the plan refuses anything else)
+                g0 += with_ng(p.lists - g0, [&](auto Ng) { launch(Bt, Ng); });
+            });
+            check_launch();
+        }
+    };
+    if (cts == 1)
+        ladder([&](auto Bt, auto Ng) {
+            constexpr int BETA = decltype(Bt)::value, NG = decltype(Ng)::value;
+            hipLaunchKernelGGL((hoist_bsgs_inner_prod_kernel<NG, BETA>), dim3((unsigned)(n / 256), t.size_qlp), dim3(256), 0, b.s, k);
+        });
+    else
+        ladder([&](auto Bt, auto Ng) {
+            constexpr int BETA = decltype(Bt)::value, NG = decltype(Ng)::value, CB = hoist_bsgs_batched_cb(BETA, NG);
+            hipLaunchKernelGGL((hoist_bsgs_batched_kernel<NG, CB, BETA>),
+                               dim3((unsigned)(n / 256), t.size_qlp, (unsigned)((cts + CB - 1) / CB)), dim3(256), 0, b.s, kb);
+        });
+}
+
+// Giant steps of `units` row blocks or ciphertexts, ng accumulator lists each: B = moddown(acc) in one batched launch set, the
+// permutations (every unit in one launch: the first write to `out`), then per unit ONE mod-down for the sum of its key-switch inner
+// products, added to out.
+static void bsgs_giant_side(const BsgsCall &b, size_t units, u64 *out) {
+    Context &c = b.c;
+    Tool &t = b.t;
+    const BsgsPlan &p = b.p;
+    const BsgsScratch &m = b.m;
+    const size_t n = b.n;
+    moddown_from_ntt(c, t, m.B, b.ql_n, m.acc, b.qlp_n, (uint32_t)(2 * p.ng * units), b.scheme, false, m.tmp, b.s);
+    hipLaunchKernelGGL(bsgs_combine_kernel, dim3((unsigned)(n / 256), t.size_ql, (unsigned)units), dim3(256), 0, b.s, out, m.g1, m.B, b.d_gtab,
+                       b.d_rank, (uint32_t)p.ng, (uint32_t)p.nk, c.d_mod.p, (uint32_t)n, b.ql_n);
+    check_launch();
+    if (p.nk) {
+        modup(c, t, m.mu_g, m.g1, b.scheme, m.tmp, b.s, (uint32_t)(units * p.nk));
+        MultiInnerArgs k{m.cx, m.mu_g, b.d_gkeys, c.d_mod.p, t.d_qlp_prime.p, (uint32_t)n, t.beta, (uint32_t)p.nk, b.qlp_n, (size_t)c.size_qp * n};
+        hipLaunchKernelGGL(inner_prod_multi_kernel, dim3((unsigned)(n / 512), t.size_qlp, (unsigned)units), dim3(256), 0, b.s, k);
+        check_launch();
+        moddown_from_ntt(c, t, out, b.ql_n, m.cx, b.qlp_n, (uint32_t)(2 * units), b.scheme, true, m.tmp, b.s);
+    }
+}
+
+// pha_hoisting_weighted_bsgs (one block, in place) and ..._blocks: `blocks` row blocks that share the input ciphertext and every Galois
+// key, blocks * ng accumulator lists on the one-ciphertext kernel
+static void bsgs_blocks(Context &c, size_t size_Ql, const u64 *ct, size_t blocks, const BsgsSteps &a, u64 *out, int scheme, void *stream) {
+    Tool &t = c.tool((uint32_t)size_Ql);
+    const BsgsPlan p = bsgs_plan(c, t, ct, 1, a, blocks * a.ng, blocks, "row blocks", as_stream(stream));
+    const BsgsCall b(c, t, p, blocks, 1, scheme, stream);
+    bsgs_baby_steps(b, ct, 1);
+    bsgs_giant_side(b, blocks, out);
+}
+
+// pha_hoisting_weighted_bsgs_batched: `batch` ciphertexts that share every key, table and weight, `chunk` of them per set of launches
+// (scratch per call: BsgsScratch of `chunk` ciphertexts).  A chunk of one ciphertext -- chunk = 1, or a tail of one -- takes the
+// one-ciphertext baby-step kernel.
+static void bsgs_batched(Context &c, size_t size_Ql, const u64 *ct, size_t batch, const BsgsSteps &a, int scheme, u64 *out, size_t chunk,
+                         void *stream) {
+    Tool &t = c.tool((uint32_t)size_Ql);
+    const size_t ct_words = 2 * size_Ql * c.n;
+    const BsgsPlan p = bsgs_plan(c, t, ct, batch, a, a.ng, 1, "giant steps", as_stream(stream));
+    if (!chunk) chunk = 4;
+    chunk = std::min(std::min(chunk, batch), std::min((size_t)65535 / (2 * a.ng), (size_t)65535 / std::max<size_t>(1, p.nk * t.beta)));
+    const BsgsCall b(c, t, p, chunk, chunk, scheme, stream);
+    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
+        const size_t cb = std::min(chunk, batch - b0);
+        bsgs_baby_steps(b, ct + b0 * ct_words, cb);
+        bsgs_giant_side(b, cb, out + b0 * ct_words);
+    }
+}
+
 }  // namespace pha
 
 using namespace pha;
-
-// Core of the baby-step / giant-step entries: `blocks` row blocks that share the input ciphertext and every Galois key.  Block r
-// with weights w[r][i][j] gives out[r] = sum_i rot_{G_i}(sum_j w[r][i][j] (.) rot_{B_j}(ct)).  The fused baby-step kernel treats
-// the (block, giant step) pairs as one list of accumulators, so the baby keys, the gathered digits and the per-baby reductions are
-// paid once for up to 8 of them; everything after it is batched over the blocks.  Every block's result is bit-identical to a
-// one-block call.
-static void bsgs_core(Context &c, Tool &t, const u64 *ct_in, size_t blocks, const uint32_t *baby_elts, size_t nb,
-                      const uint64_t *const *const *baby_glk, const uint32_t *giant_elts, size_t ng,
-                      const uint64_t *const *const *giant_glk, const uint64_t *const *weights, u64 *out, int scheme, void *stream) {
-    hipStream_t s = as_stream(stream);
-    const size_t n = c.n, size_Ql = t.size_ql, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n, G = blocks * ng;
-    if (strict_mode()) {
-        strict_operand(c, "hoisting ct", ct_in, rows_plain(0, size_Ql), 2, ql_n, s);
-        for (size_t j = 0; j < nb; j++)
-            if (baby_glk[j]) strict_keys(c, "baby-step Galois key", baby_glk[j], t.beta, (uint32_t)size_Ql, s);
-        for (size_t i = 0; i < ng; i++)
-            if (giant_glk[i]) strict_keys(c, "giant-step Galois key", giant_glk[i], t.beta, (uint32_t)size_Ql, s);
-        for (size_t i = 0; i < G * nb; i++)
-            if (weights[i]) strict_operand(c, "BSGS weight", weights[i], rows_qlp(t.size_ql, c.size_q, c.size_p), 1, 0, s);
-    }
-    // 128-bit accumulators: every weighted term is below 2^122 (61-bit primes), 63 of them fit; the giant inner products are
-    // plain products (2^120 each for 60-bit primes)
-    size_t nbk = 0, nk = 0;
-    for (size_t j = 0; j < nb; j++) {
-        if (baby_elts[j] != 1 && !baby_glk[j]) throw std::logic_error("Galois key not present in hoisting");
-        nbk += baby_elts[j] != 1;
-    }
-    for (size_t i = 0; i < ng; i++) {
-        if (giant_elts[i] != 1 && !giant_glk[i]) throw std::logic_error("Galois key not present in hoisting");
-        nk += giant_elts[i] != 1;
-    }
-    // what the unreduced 128-bit accumulators of the fused baby-step kernel hold: one s * w product per baby ENTRY (identity entries and
-    // repeated elements included) plus the P-scaled c0 / c1 term, each below q_max^2; the giant steps' key products likewise
-    const size_t max_terms = acc_capacity(c);
-    if (nb + 1 > max_terms || nk * t.beta > max_terms || nbk > 255)
-        throw std::invalid_argument("too many steps for one call: the 128-bit accumulators hold floor(2^128 / q_max^2) - 1 products (at most "
-                                    "254 baby entries for primes up to 60 bits, 62 for 61-bit primes)");
-    if (2 * G > 65535 || blocks * nk * t.beta > 65535) throw std::invalid_argument("too many row blocks for one call");
-    if (t.beta > 4) throw std::invalid_argument("more than 4 key-switch digits are not supported by the baby-step / giant-step form");
-    bool any_null = false;
-    for (size_t i = 0; i < G * nb; i++) any_null = any_null || !weights[i];
-    std::vector<const void *> h_btab(nb), h_bkeys(nb), h_gtab(ng), h_gkeys;
-    std::vector<uint32_t> h_rank(ng);
-    for (size_t j = 0; j < nb; j++) {
-        h_btab[j] = c.galois_table(baby_elts[j]);
-        h_bkeys[j] = baby_elts[j] == 1 ? nullptr : baby_glk[j];
-    }
-    for (size_t i = 0; i < ng; i++) {
-        h_gtab[i] = c.galois_table(giant_elts[i]);
-        h_rank[i] = giant_elts[i] == 1 ? 0xffffffffu : (uint32_t)h_gkeys.size();
-        if (giant_elts[i] != 1) h_gkeys.push_back(giant_glk[i]);
-    }
-    // scratch: cc [2][Ql][N] | tmp [max(2 G, blocks nk, 2 blocks)][Ql][N] | mod-up [beta][QlP][N] | acc [G][2][QlP][N] |
-    //          B [G][2][Ql][N] | g1 [blocks][nk][Ql][N] | giant mod-up [blocks][nk][beta][QlP][N] | cx [blocks][2][QlP][N] | tables
-    const size_t n_tmp = std::max<size_t>(2 * G, std::max<size_t>(blocks * nk, 2 * blocks));
-    const size_t ptr_words = 2 * nb + G * nb + 2 * ng + nk + (any_null ? qlp_n : 0);   // (+ a zero plane for the missing weights)
-    u64 *base = c.scratch(stream, 2 * ql_n + n_tmp * ql_n + (size_t)t.beta * qlp_n + G * 2 * qlp_n + G * 2 * ql_n + blocks * nk * ql_n +
-                                      blocks * nk * (size_t)t.beta * qlp_n + blocks * 2 * qlp_n + ptr_words);
-    u64 *cc = base, *tmp = cc + 2 * ql_n, *t_mod_up = tmp + n_tmp * ql_n, *acc = t_mod_up + (size_t)t.beta * qlp_n,
-        *B = acc + G * 2 * qlp_n, *g1 = B + G * 2 * ql_n, *mu_g = g1 + blocks * nk * ql_n,
-        *cxg = mu_g + blocks * nk * (size_t)t.beta * qlp_n, *d_ptrs = cxg + blocks * 2 * qlp_n;
-    u64 *p_btab = d_ptrs, *p_bkeys = p_btab + nb, *p_w = p_bkeys + nb, *p_gtab = p_w + G * nb, *p_rank = p_gtab + ng, *p_gkeys = p_rank + ng;
-    PHA_HIP(hipMemcpyAsync(p_btab, h_btab.data(), nb * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(p_bkeys, h_bkeys.data(), nb * sizeof(void *), hipMemcpyHostToDevice, s));
-    std::vector<const void *> h_w(weights, weights + G * nb);
-    if (any_null) {
-        u64 *zero = p_gkeys + nk;
-        PHA_HIP(hipMemsetAsync(zero, 0, qlp_n * sizeof(u64), s));
-        for (auto &w : h_w)
-            if (!w) w = zero;
-    }
-    PHA_HIP(hipMemcpyAsync(p_w, h_w.data(), G * nb * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(p_gtab, h_gtab.data(), ng * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(p_rank, h_rank.data(), ng * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    if (nk) PHA_HIP(hipMemcpyAsync(p_gkeys, h_gkeys.data(), nk * sizeof(void *), hipMemcpyHostToDevice, s));
-    const uint32_t *const *d_btab = reinterpret_cast<const uint32_t *const *>(p_btab);
-    const u64 *const *const *d_bkeys = reinterpret_cast<const u64 *const *const *>(p_bkeys);
-    const u64 *const *d_w = reinterpret_cast<const u64 *const *>(p_w);
-    const uint32_t *const *d_gtab = reinterpret_cast<const uint32_t *const *>(p_gtab);
-    const u64 *const *const *d_gkeys = reinterpret_cast<const u64 *const *const *>(p_gkeys);
-
-    PHA_HIP(hipMemcpyAsync(cc, ct_in, 2 * ql_n * sizeof(u64), hipMemcpyDeviceToDevice, s));   // (out may be ct_in: one-block in-place form)
-    // baby steps: one mod-up of c1, then every (block, giant step)'s weighted sum of the hoisted inner products (and of the c0 / c1
-    // terms, pre-multiplied by P) in one pass over the baby keys per 8 accumulators; B = moddown(acc), one batched launch set
-    if (nbk) modup(c, t, t_mod_up, cc + ql_n, scheme, tmp, s);
-    {
-        BsgsArgs k{};
-        k.acc = acc; k.t_mod_up = t_mod_up; k.keys = d_bkeys; k.tables = d_btab; k.weights = d_w; k.mod = c.d_mod.p;
-        k.qlp_prime = t.d_qlp_prime.p; k.n = (uint32_t)n; k.beta = t.beta; k.nb = (uint32_t)nb;
-        k.qlp_n = qlp_n; k.qp_n = (size_t)c.size_qp * n;
-        k.cc = cc; k.p_mod_q = t.p_mod_q2.p; k.ql = (uint32_t)size_Ql; k.ql_n = ql_n;
-        k.fpinfo = c.d_fpinfo.p;
-        const dim3 grid((unsigned)(n / 256), t.size_qlp), block(256);
-        for (size_t g0 = 0; g0 < G;) {
-            const size_t left = G - g0;
-            k.g0 = (uint32_t)g0;
-            with_beta<4>(t.beta, [&](auto B) {   // (beta <= 4: checked above)
-                constexpr int BETA = decltype(B)::value;
-                if (left >= 16) { hipLaunchKernelGGL((hoist_bsgs_inner_prod_kernel<16, BETA>), grid, block, 0, s, k); g0 += 16; }
-                else if (left >= 8) { hipLaunchKernelGGL((hoist_bsgs_inner_prod_kernel<8, BETA>), grid, block, 0, s, k); g0 += 8; }
-                else if (left >= 4) { hipLaunchKernelGGL((hoist_bsgs_inner_prod_kernel<4, BETA>), grid, block, 0, s, k); g0 += 4; }
-                else if (left >= 2) { hipLaunchKernelGGL((hoist_bsgs_inner_prod_kernel<2, BETA>), grid, block, 0, s, k); g0 += 2; }
-                else { hipLaunchKernelGGL((hoist_bsgs_inner_prod_kernel<1, BETA>), grid, block, 0, s, k); g0 += 1; }
-            });
-            check_launch();
-        }
-    }
-    moddown_from_ntt(c, t, B, ql_n, acc, qlp_n, (uint32_t)(2 * G), scheme, false, tmp, s);
-    // giant steps: permutations (every block in one launch), then per block ONE mod-down for the sum of its key-switch inner products
-    hipLaunchKernelGGL(bsgs_combine_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql, (unsigned)blocks), dim3(256), 0, s, out, g1, B,
-                       d_gtab, reinterpret_cast<const uint32_t *>(p_rank), (uint32_t)ng, (uint32_t)nk, c.d_mod.p, (uint32_t)n, ql_n);
-    check_launch();
-    if (nk) {
-        modup(c, t, mu_g, g1, scheme, tmp, s, (uint32_t)(blocks * nk));
-        MultiInnerArgs k{cxg, mu_g, d_gkeys, c.d_mod.p, t.d_qlp_prime.p, (uint32_t)n, t.beta, (uint32_t)nk, qlp_n, (size_t)c.size_qp * n};
-        hipLaunchKernelGGL(inner_prod_multi_kernel, dim3((unsigned)(n / 512), t.size_qlp, (unsigned)blocks), dim3(256), 0, s, k);
-        check_launch();
-        moddown_from_ntt(c, t, out, ql_n, cxg, qlp_n, (uint32_t)(2 * blocks), scheme, true, tmp, s);
-    }
-}
-
-// Driver of pha_hoisting_weighted_bsgs_batched: `batch` ciphertexts that share every key, table and weight, `chunk` of them per set of
-// launches.  Per chunk of cb >= 2 ciphertexts: one mod-up of the cb c1 polynomials (the digits' own limbs copied -- the gather reads
-// them through the permutation), the fused baby-step kernel over groups of CB ciphertexts (pha_hoist_bsgs_batched.h), one mod-down of
-// 2 G cb polynomials, and the giant-step side on bsgs_core's kernels with the ciphertext where they have the row block.  A chunk of
-// one ciphertext is bsgs_core with one block.
-// No copy of the ciphertexts, in place included: the first write to out[b] is the combine kernel's, after the last read of ct[b] (by
-// the mod-up and the baby-step kernel of the same chunk, earlier on the stream); a later chunk reads only its own ciphertexts.
-// Scratch per call: chunk * (4 G |Ql| + (beta + 2 G + nk beta + 2) |QlP| + nk |Ql|) * N words + the pointer tables:
-//   tmp [2 G chunk][Ql][N] | mod-up [chunk][beta][QlP][N] | acc [chunk][G][2][QlP][N] | B [chunk][G][2][Ql][N] | g1 [chunk][nk][Ql][N] |
-//   giant mod-up [chunk][nk][beta][QlP][N] | cx [chunk][2][QlP][N] | tables (| a zero plane [QlP][N] for the missing weights)
-static void bsgs_batched_core(Context &c, size_t size_Ql, const u64 *ct, size_t batch, const uint32_t *baby_elts, size_t nb,
-                              const uint64_t *const *const *baby_glk, const uint32_t *giant_elts, size_t ng,
-                              const uint64_t *const *const *giant_glk, const uint64_t *const *weights, int scheme, u64 *out, size_t chunk,
-                              void *stream) {
-    check_level(c, size_Ql, true);
-    Tool &t = c.tool((uint32_t)size_Ql);
-    hipStream_t s = as_stream(stream);
-    const size_t n = c.n, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n, ct_words = 2 * ql_n, G = ng;
-    if (out != ct && overlaps(out, batch * ct_words, ct, batch * ct_words))
-        throw std::invalid_argument("out must be ct itself (in place) or must not overlap it");
-    // every refusal of bsgs_core, before the first launch
-    for (size_t j = 0; j < nb; j++) check_galois_elt(c, baby_elts[j]);
-    for (size_t i = 0; i < ng; i++) check_galois_elt(c, giant_elts[i]);
-    size_t nbk = 0, nk = 0;
-    for (size_t j = 0; j < nb; j++) {
-        if (baby_elts[j] != 1 && !baby_glk[j]) throw std::logic_error("Galois key not present in hoisting");
-        nbk += baby_elts[j] != 1;
-    }
-    for (size_t i = 0; i < ng; i++) {
-        if (giant_elts[i] != 1 && !giant_glk[i]) throw std::logic_error("Galois key not present in hoisting");
-        nk += giant_elts[i] != 1;
-    }
-    const size_t max_terms = acc_capacity(c);
-    if (nb + 1 > max_terms || nk * t.beta > max_terms || nbk > 255)
-        throw std::invalid_argument("too many steps for one call: the 128-bit accumulators hold floor(2^128 / q_max^2) - 1 products (at most "
-                                    "254 baby entries for primes up to 60 bits, 62 for 61-bit primes)");
-    if (2 * G > 65535 || nk * t.beta > 65535) throw std::invalid_argument("too many giant steps for one call");
-    if (t.beta > 4) throw std::invalid_argument("more than 4 key-switch digits are not supported by the baby-step / giant-step form");
-    if (strict_mode()) {
-        strict_operand(c, "hoisting ct", ct, rows_plain(0, size_Ql), (uint32_t)(2 * batch), ql_n, s);
-        for (size_t j = 0; j < nb; j++)
-            if (baby_glk[j]) strict_keys(c, "baby-step Galois key", baby_glk[j], t.beta, (uint32_t)size_Ql, s);
-        for (size_t i = 0; i < ng; i++)
-            if (giant_glk[i]) strict_keys(c, "giant-step Galois key", giant_glk[i], t.beta, (uint32_t)size_Ql, s);
-        for (size_t i = 0; i < G * nb; i++)
-            if (weights[i]) strict_operand(c, "BSGS weight", weights[i], rows_qlp(t.size_ql, c.size_q, c.size_p), 1, 0, s);
-    }
-    if (!chunk) chunk = 4;
-    chunk = std::min(std::min(chunk, batch), std::min((size_t)65535 / (2 * G), (size_t)65535 / std::max<size_t>(1, nk * t.beta)));
-    auto single = [&](size_t b) {
-        bsgs_core(c, t, ct + b * ct_words, 1, baby_elts, nb, baby_glk, giant_elts, ng, giant_glk, weights, out + b * ct_words, scheme, stream);
-    };
-    if (chunk == 1) {
-        for (size_t b = 0; b < batch; b++) single(b);
-        return;
-    }
-    bool any_null = false;
-    for (size_t i = 0; i < G * nb; i++) any_null = any_null || !weights[i];
-    std::vector<const void *> h_btab(nb), h_bkeys(nb), h_gtab(ng), h_gkeys;
-    std::vector<uint32_t> h_rank(ng);
-    for (size_t j = 0; j < nb; j++) {
-        h_btab[j] = c.galois_table(baby_elts[j]);
-        h_bkeys[j] = baby_elts[j] == 1 ? nullptr : baby_glk[j];
-    }
-    for (size_t i = 0; i < ng; i++) {
-        h_gtab[i] = c.galois_table(giant_elts[i]);
-        h_rank[i] = giant_elts[i] == 1 ? 0xffffffffu : (uint32_t)h_gkeys.size();
-        if (giant_elts[i] != 1) h_gkeys.push_back(giant_glk[i]);
-    }
-    const size_t ptr_words = 2 * nb + G * nb + 2 * ng + nk + (any_null ? qlp_n : 0);
-    u64 *base = c.scratch(stream, chunk * (4 * G * ql_n + ((size_t)t.beta + 2 * G + nk * t.beta + 2) * qlp_n + nk * ql_n) + ptr_words);
-    u64 *tmp = base, *t_mod_up = tmp + chunk * 2 * G * ql_n, *acc = t_mod_up + chunk * t.beta * qlp_n, *B = acc + chunk * G * 2 * qlp_n,
-        *g1 = B + chunk * G * 2 * ql_n, *mu_g = g1 + chunk * nk * ql_n, *cxg = mu_g + chunk * nk * t.beta * qlp_n,
-        *d_ptrs = cxg + chunk * 2 * qlp_n;
-    u64 *p_btab = d_ptrs, *p_bkeys = p_btab + nb, *p_w = p_bkeys + nb, *p_gtab = p_w + G * nb, *p_rank = p_gtab + ng, *p_gkeys = p_rank + ng;
-    PHA_HIP(hipMemcpyAsync(p_btab, h_btab.data(), nb * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(p_bkeys, h_bkeys.data(), nb * sizeof(void *), hipMemcpyHostToDevice, s));
-    std::vector<const void *> h_w(weights, weights + G * nb);
-    if (any_null) {
-        u64 *zero = p_gkeys + nk;
-        PHA_HIP(hipMemsetAsync(zero, 0, qlp_n * sizeof(u64), s));
-        for (auto &w : h_w)
-            if (!w) w = zero;
-    }
-    PHA_HIP(hipMemcpyAsync(p_w, h_w.data(), G * nb * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(p_gtab, h_gtab.data(), ng * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(p_rank, h_rank.data(), ng * sizeof(uint32_t), hipMemcpyHostToDevice, s));
-    if (nk) PHA_HIP(hipMemcpyAsync(p_gkeys, h_gkeys.data(), nk * sizeof(void *), hipMemcpyHostToDevice, s));
-    const u64 *const *const *d_gkeys = reinterpret_cast<const u64 *const *const *>(p_gkeys);
-
-    BsgsBArgs k{};
-    k.acc = acc; k.t_mod_up = t_mod_up; k.keys = reinterpret_cast<const u64 *const *const *>(p_bkeys);
-    k.tables = reinterpret_cast<const uint32_t *const *>(p_btab); k.weights = reinterpret_cast<const u64 *const *>(p_w);
-    k.mod = c.d_mod.p; k.qlp_prime = t.d_qlp_prime.p; k.n = (uint32_t)n; k.beta = t.beta; k.nb = (uint32_t)nb; k.g_total = (uint32_t)G;
-    k.qlp_n = qlp_n; k.qp_n = (size_t)c.size_qp * n; k.cc_stride = ct_words; k.p_mod_q = t.p_mod_q2.p; k.ql = (uint32_t)size_Ql;
-    k.ql_n = ql_n; k.fpinfo = reinterpret_cast<const BsgsBFp *>(c.d_fpinfo.p);
-    for (size_t b0 = 0; b0 < batch; b0 += chunk) {
-        const size_t cb = std::min(chunk, batch - b0);
-        if (cb == 1) {   // (the last chunk; nothing below uses this call's scratch any more)
-            single(b0);
-            break;
-        }
-        const u64 *in = ct + b0 * ct_words;
-        u64 *o = out + b0 * ct_words;
-        if (nbk) modup(c, t, t_mod_up, in + ql_n, scheme, tmp, s, (uint32_t)cb, ct_words, nullptr, false);
-        k.cc = in; k.n_ct = (uint32_t)cb;
-        for (size_t g0 = 0; g0 < G;) {
-            const size_t left = G - g0;
-            k.g0 = (uint32_t)g0;
-            with_beta<4>(t.beta, [&](auto Bt) {   // (beta <= 4: checked above)
-                constexpr int BETA = decltype(Bt)::value;
-                auto launch = [&](auto Ng) {
-                    constexpr int NG = decltype(Ng)::value, CB = hoist_bsgs_batched_cb(BETA, NG);
-                    const dim3 grid((unsigned)(n / 256), t.size_qlp, (unsigned)((cb + CB - 1) / CB));
-                    hipLaunchKernelGGL((hoist_bsgs_batched_kernel<NG, CB, BETA>), grid, dim3(256), 0, s, k);
-                    g0 += NG;
-                };
-                if (left >= 16) launch(std::integral_constant<int, 16>{});
-                else if (left >= 8) launch(std::integral_constant<int, 8>{});
-                else if (left >= 4) launch(std::integral_constant<int, 4>{});
-                else if (left >= 2) launch(std::integral_constant<int, 2>{});
-                else launch(std::integral_constant<int, 1>{});
-            });
-            check_launch();
-        }
-        moddown_from_ntt(c, t, B, ql_n, acc, qlp_n, (uint32_t)(2 * G * cb), scheme, false, tmp, s);
-        hipLaunchKernelGGL(bsgs_combine_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql, (unsigned)cb), dim3(256), 0, s, o, g1, B,
-                           reinterpret_cast<const uint32_t *const *>(p_gtab), reinterpret_cast<const uint32_t *>(p_rank), (uint32_t)ng,
-                           (uint32_t)nk, c.d_mod.p, (uint32_t)n, ql_n);
-        check_launch();
-        if (nk) {
-            modup(c, t, mu_g, g1, scheme, tmp, s, (uint32_t)(cb * nk));
-            MultiInnerArgs m{cxg, mu_g, d_gkeys, c.d_mod.p, t.d_qlp_prime.p, (uint32_t)n, t.beta, (uint32_t)nk, qlp_n, (size_t)c.size_qp * n};
-            hipLaunchKernelGGL(inner_prod_multi_kernel, dim3((unsigned)(n / 512), t.size_qlp, (unsigned)cb), dim3(256), 0, s, m);
-            check_launch();
-            moddown_from_ntt(c, t, o, ql_n, cxg, qlp_n, (uint32_t)(2 * cb), scheme, true, tmp, s);
-        }
-    }
-}
 
 extern "C" {
 
@@ -905,51 +829,7 @@ int pha_hoisting(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const uint32_t
     PHA_CTX_BEGIN(ctx)
     need(ct); need(galois_elts); need(glk);
     if (n_elts == 0) throw std::invalid_argument("steps must not be empty");
-    Context &c = ctx->c;
-    check_level(c, size_Ql, true);
-    Tool &t = c.tool((uint32_t)size_Ql);
-    hipStream_t s = as_stream(stream);
-    if (strict_mode()) {
-        strict_operand(c, "hoisting ct", ct, rows_plain(0, size_Ql), 2, size_Ql * c.n, s);
-        for (size_t e = 0; e < n_elts; e++)
-            if (glk[e]) strict_keys(c, "hoisting Galois key", glk[e], t.beta, (uint32_t)size_Ql, s);
-    }
-    const size_t n = c.n, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n;
-    const bool ntt_dom = ntt_domain_scheme(scheme);
-    // per-element device tables: permutation tables and key pointer tables
-    std::vector<const uint32_t *> h_tabs(n_elts);
-    for (size_t e = 0; e < n_elts; e++) {
-        if (!glk[e]) throw std::logic_error("Galois key not present in hoisting");
-        h_tabs[e] = c.galois_table(galois_elts[e]);
-    }
-    // scratch: c0 copy [Ql][N] | tmp / delta [2][Ql][N] | mod-up [beta][QlP][N] | acc_cx [2][QlP][N] | pointer tables
-    const size_t ptr_words = 2 * n_elts;
-    u64 *base = c.scratch(stream, 3 * ql_n + (size_t)t.beta * qlp_n + 2 * qlp_n + ptr_words);
-    u64 *c0 = base, *tmp = c0 + ql_n, *t_mod_up = tmp + 2 * ql_n, *acc_cx = t_mod_up + (size_t)t.beta * qlp_n;
-    u64 *d_ptrs = acc_cx + 2 * qlp_n;
-    PHA_HIP(hipMemcpyAsync(d_ptrs, h_tabs.data(), n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(d_ptrs + n_elts, glk, n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
-    const uint32_t *const *d_tabs = reinterpret_cast<const uint32_t *const *>(d_ptrs);
-    const u64 *const *const *d_keys = reinterpret_cast<const u64 *const *const *>(d_ptrs + n_elts);
-
-    PHA_HIP(hipMemcpyAsync(c0, ct, ql_n * sizeof(u64), hipMemcpyDeviceToDevice, s));
-    // one mod-up of c1 shared by every rotation (evaluate.cu:1758-1760)
-    modup(c, t, t_mod_up, ct + ql_n, scheme, tmp, s);
-    launch_hoist_inner_prod(c, t, acc_cx, t_mod_up, d_keys, d_tabs, nullptr, n_elts, std::max<size_t>(1, acc_capacity(c) / t.beta), s);
-    // ct0 <- sum_e galois_e(c0) ; ct1 <- 0 ; then both += moddown(acc_cx) (fused into the NTT epilogue)
-    if (ntt_dom) {
-        hipLaunchKernelGGL(hoist_c0_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql), dim3(256), 0, s, ct, c0,
-                           d_tabs, (uint32_t)n_elts, c.d_mod.p, (uint32_t)n);
-        check_launch();
-    } else {
-        PHA_HIP(hipMemsetAsync(ct, 0, ql_n * sizeof(u64), s));
-        for (size_t e = 0; e < n_elts; e++) {  // coefficient-domain automorphism (src/galois.cu:20-39)
-            launch_galois_coeff(c, tmp, c0, galois_elts[e], size_Ql, 0, 1, s);
-            launch_add(c, ct, tmp, ct, size_Ql, 0, s);
-        }
-    }
-    PHA_HIP(hipMemsetAsync(ct + ql_n, 0, ql_n * sizeof(u64), s));
-    moddown_from_ntt(c, t, ct, ql_n, acc_cx, qlp_n, 2, scheme, true, tmp, s);
+    hoist_batched_core(ctx->c, size_Ql, ct, 1, galois_elts, n_elts, glk, nullptr, scheme, ct, 1, stream);
     PHA_API_END
 }
 
@@ -959,59 +839,7 @@ int pha_hoisting_weighted(pha_context_t ctx, size_t size_Ql, uint64_t *ct, const
     need(ct); need(galois_elts); need(glk); need(weights);
     if (n_elts == 0) throw std::invalid_argument("steps must not be empty");
     if (!ntt_domain_scheme(scheme)) throw std::invalid_argument("weighted hoisting takes NTT-form ciphertexts (ckks / bgv)");
-    Context &c = ctx->c;
-    check_level(c, size_Ql, true);
-    Tool &t = c.tool((uint32_t)size_Ql);
-    hipStream_t s = as_stream(stream);
-    if (strict_mode()) {
-        strict_operand(c, "hoisting ct", ct, rows_plain(0, size_Ql), 2, size_Ql * c.n, s);
-        for (size_t e = 0; e < n_elts; e++) {
-            if (glk[e]) strict_keys(c, "hoisting Galois key", glk[e], t.beta, (uint32_t)size_Ql, s);
-            if (weights[e]) strict_operand(c, "hoisting weight", weights[e], rows_qlp(t.size_ql, c.size_q, c.size_p), 1, 0, s);
-        }
-    }
-    const size_t n = c.n, ql_n = size_Ql * n, qlp_n = (size_t)t.size_qlp * n;
-    // order the elements: key-switched ones first, main-diagonal ones (element 1, no key) last
-    std::vector<const void *> tabs, keys, w_ks, w_all;
-    std::vector<size_t> order;
-    for (int pass = 0; pass < 2; pass++)
-        for (size_t e = 0; e < n_elts; e++) {
-            if (!weights[e]) throw std::invalid_argument("null weight");
-            if ((galois_elts[e] == 1) == (pass == 1)) order.push_back(e);
-        }
-    size_t n_ks = 0;
-    for (size_t e : order) {
-        tabs.push_back(c.galois_table(galois_elts[e]));
-        w_all.push_back(weights[e]);
-        if (galois_elts[e] != 1) {
-            if (!glk[e]) throw std::logic_error("Galois key not present in hoisting");
-            keys.push_back(glk[e]);
-            n_ks++;
-        }
-    }
-    // scratch: (c0, c1) copy [2][Ql][N] | tmp / delta [2][Ql][N] | mod-up [beta][QlP][N] | acc_cx [2][QlP][N] | pointers
-    const size_t ptr_words = 3 * n_elts;
-    u64 *base = c.scratch(stream, 4 * ql_n + (size_t)t.beta * qlp_n + 2 * qlp_n + ptr_words);
-    u64 *cc = base, *tmp = cc + 2 * ql_n, *t_mod_up = tmp + 2 * ql_n, *acc_cx = t_mod_up + (size_t)t.beta * qlp_n;
-    u64 *d_ptrs = acc_cx + 2 * qlp_n;
-    PHA_HIP(hipMemcpyAsync(d_ptrs, tabs.data(), n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
-    PHA_HIP(hipMemcpyAsync(d_ptrs + n_elts, w_all.data(), n_elts * sizeof(void *), hipMemcpyHostToDevice, s));
-    if (n_ks) PHA_HIP(hipMemcpyAsync(d_ptrs + 2 * n_elts, keys.data(), n_ks * sizeof(void *), hipMemcpyHostToDevice, s));
-    const uint32_t *const *d_tabs = reinterpret_cast<const uint32_t *const *>(d_ptrs);
-    const u64 *const *d_w = reinterpret_cast<const u64 *const *>(d_ptrs + n_elts);
-    const u64 *const *const *d_keys = reinterpret_cast<const u64 *const *const *>(d_ptrs + 2 * n_elts);
-    PHA_HIP(hipMemcpyAsync(cc, ct, 2 * ql_n * sizeof(u64), hipMemcpyDeviceToDevice, s));
-    if (n_ks) {
-        modup(c, t, t_mod_up, ct + ql_n, scheme, tmp, s);
-        // 63 elements per launch, whatever the primes: an element adds ONE reduced sum times a weight, below 2^122 for the 61-bit
-        // primes the context accepts at most, so 63 of them fit (acc_capacity() / beta of the unweighted form would split earlier)
-        launch_hoist_inner_prod(c, t, acc_cx, t_mod_up, d_keys, d_tabs, d_w, n_ks, 63, s);
-    }
-    // ct0 <- sum_e w_e galois_e(c0), ct1 <- sum over the main-diagonal elements of w_e c1; then both += moddown(acc_cx)
-    hipLaunchKernelGGL(hoist_weighted_c_kernel, dim3((unsigned)(n / 256), (unsigned)size_Ql, 2), dim3(256), 0, s, ct, cc,
-                       d_tabs, d_w, (uint32_t)n_elts, (uint32_t)n_ks, c.d_mod.p, (uint32_t)n, ql_n);
-    check_launch();
-    if (n_ks) moddown_from_ntt(c, t, ct, ql_n, acc_cx, qlp_n, 2, scheme, true, tmp, s);
+    hoist_batched_core(ctx->c, size_Ql, ct, 1, galois_elts, n_elts, glk, weights, scheme, ct, 1, stream);
     PHA_API_END
 }
 
@@ -1024,7 +852,7 @@ int pha_hoisting_weighted_bsgs(pha_context_t ctx, size_t size_Ql, uint64_t *ct, 
     if (!ntt_domain_scheme(scheme)) throw std::invalid_argument("weighted hoisting takes NTT-form ciphertexts (ckks / bgv)");
     Context &c = ctx->c;
     check_level(c, size_Ql, true);
-    bsgs_core(c, c.tool((uint32_t)size_Ql), ct, 1, baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights, ct, scheme, stream);
+    bsgs_blocks(c, size_Ql, ct, 1, {baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights}, ct, scheme, stream);
     PHA_API_END
 }
 
@@ -1037,8 +865,11 @@ int pha_hoisting_weighted_bsgs_batched(pha_context_t ctx, size_t size_Ql, const 
     if (n_baby == 0 || n_giant == 0) throw std::invalid_argument("steps must not be empty");
     if (!ntt_domain_scheme(scheme)) throw std::invalid_argument("weighted hoisting takes NTT-form ciphertexts (ckks / bgv)");
     if (batch == 0) return 0;
-    bsgs_batched_core(ctx->c, size_Ql, ct, batch, baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights, scheme, out, chunk,
-                      stream);
+    Context &c = ctx->c;
+    check_level(c, size_Ql, true);
+    const size_t words = batch * 2 * size_Ql * c.n;
+    if (out != ct && overlaps(out, words, ct, words)) throw std::invalid_argument("out must be ct itself (in place) or must not overlap it");
+    bsgs_batched(c, size_Ql, ct, batch, {baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights}, scheme, out, chunk, stream);
     PHA_API_END
 }
 
@@ -1055,8 +886,7 @@ int pha_hoisting_weighted_bsgs_blocks(pha_context_t ctx, size_t size_Ql, const u
     check_level(c, size_Ql, true);
     const size_t ql_n = size_Ql * c.n;
     if (overlaps(out, n_blocks * 2 * ql_n, ct, 2 * ql_n)) throw std::invalid_argument("out must not overlap ct");
-    bsgs_core(c, c.tool((uint32_t)size_Ql), ct, n_blocks, baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights, out, scheme,
-              stream);
+    bsgs_blocks(c, size_Ql, ct, n_blocks, {baby_elts, n_baby, baby_glk, giant_elts, n_giant, giant_glk, weights}, out, scheme, stream);
     PHA_API_END
 }
 

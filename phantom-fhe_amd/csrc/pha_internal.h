@@ -500,6 +500,16 @@ inline void with_beta(uint32_t beta, F &&fn) {
         default: fn(std::integral_constant<int, FALLBACK>{}); break;
     }
 }
+// calls fn(std::integral_constant<int, NG>{}) with NG = the largest accumulator count the baby-step kernels of pha_hoist.hip are
+// instantiated for (16, 8, 4, 2, 1) that `left` >= 1 accumulator lists still fill, and returns NG
+template <class F>
+inline size_t with_ng(size_t left, F &&fn) {
+    if (left >= 16) return fn(std::integral_constant<int, 16>{}), 16;
+    if (left >= 8) return fn(std::integral_constant<int, 8>{}), 8;
+    if (left >= 4) return fn(std::integral_constant<int, 4>{}), 4;
+    if (left >= 2) return fn(std::integral_constant<int, 2>{}), 2;
+    return fn(std::integral_constant<int, 1>{}), 1;
+}
 // calls fn(std::integral_constant<int, P>{}) with P = the register-resident input count (ISZ_PAD) the base-conversion kernels are
 // instantiated for: the ladder 2, 4, 8, 15 (exactly fifteen inputs: no padded sixteenth term), 16, 32, with steps below MIN taken
 // as MIN.  Returns false and calls nothing above MAX (the caller has another kernel, or has ruled such a base out).

@@ -46,6 +46,20 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _elts_keys(elts, keys, optional=True):
+    """Galois elements and the key tables of their PhantomRelinKeys as the hoisting entries take them; optional: a key may be None
+    (element 1 needs none)."""
+    tabs = [None if optional and k is None else k.public_keys_ptr.data_ptr() for k in keys]
+    return (C.c_uint32 * len(elts))(*[int(e) for e in elts]), (C.c_void_p * len(keys))(*tabs)
+
+
+def _weight_ptrs(flat, count=None, shape=None):
+    """The device pointers of a flat list of weights (None: no such term); count: how many there must be, of `shape`."""
+    if count is not None and len(flat) != count:
+        raise ValueError(f"weights must be {shape}")
+    return (C.c_void_p * len(flat))(*[_ptr(w) for w in flat])
+
+
 def stream_copy_rate(dst, src, iters=10):
     """bytes per second (read + write) of the library's own 16-byte-per-lane device-to-device copy (phantom_amd_bench.h)."""
     rate = C.c_double()
@@ -593,16 +607,14 @@ class PhantomContext:
     def hoisting(self, size_Ql, ct, galois_elts, galois_keys, scheme):
         """hoisting_inplace (src/evaluate.cu:1670-1866): ct <- sum_e rotate_e(ct); galois_keys[e] is the
         PhantomRelinKey of Galois element galois_elts[e]."""
-        elts = (C.c_uint32 * len(galois_elts))(*[int(e) for e in galois_elts])
-        tabs = (C.c_void_p * len(galois_keys))(*[k.public_keys_ptr.data_ptr() for k in galois_keys])
+        elts, tabs = _elts_keys(galois_elts, galois_keys, optional=False)
         _lib.check(self._L.pha_hoisting(self._h, size_Ql, _ptr(ct), elts, len(galois_elts), tabs, int(scheme), _stream()))
 
     def hoisting_weighted(self, size_Ql, ct, galois_elts, galois_keys, weights, scheme):
         """Build-defined (BASELINE config 5): ct <- sum_e weights[e] (.) rotate_e(ct); weights[e] is a device
         tensor [Ql + size_P][N] (the plaintext over [Q_l || P], NTT form); galois_keys[e] may be None for element 1."""
-        elts = (C.c_uint32 * len(galois_elts))(*[int(e) for e in galois_elts])
-        tabs = (C.c_void_p * len(galois_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in galois_keys])
-        ws = (C.c_void_p * len(weights))(*[_ptr(w) for w in weights])
+        elts, tabs = _elts_keys(galois_elts, galois_keys)
+        ws = _weight_ptrs(weights)
         _lib.check(self._L.pha_hoisting_weighted(self._h, size_Ql, _ptr(ct), elts, len(galois_elts), tabs, ws, int(scheme),
                                                  _stream()))
 
@@ -610,28 +622,19 @@ class PhantomContext:
         """Baby-step / giant-step form (pha_hoisting_weighted_bsgs): ct <- sum_i rot_{giant_elts[i]}(sum_j weights[i][j] (.)
         rot_{baby_elts[j]}(ct)); weights is a list (per giant step) of lists (per baby step) of device tensors [Ql + size_P][N] or
         None; keys may be None for element 1."""
-        be = (C.c_uint32 * len(baby_elts))(*[int(e) for e in baby_elts])
-        ge = (C.c_uint32 * len(giant_elts))(*[int(e) for e in giant_elts])
-        bk = (C.c_void_p * len(baby_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in baby_keys])
-        gk = (C.c_void_p * len(giant_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in giant_keys])
-        flat = [w for row in weights for w in row]
-        if len(flat) != len(baby_elts) * len(giant_elts):
-            raise ValueError("weights must be [n_giant][n_baby]")
-        ws = (C.c_void_p * len(flat))(*[_ptr(w) for w in flat])
+        be, bk = _elts_keys(baby_elts, baby_keys)
+        ge, gk = _elts_keys(giant_elts, giant_keys)
+        ws = _weight_ptrs([w for row in weights for w in row], len(baby_elts) * len(giant_elts), "[n_giant][n_baby]")
         _lib.check(self._L.pha_hoisting_weighted_bsgs(self._h, size_Ql, _ptr(ct), be, len(baby_elts), bk, ge, len(giant_elts), gk, ws,
                                                       int(scheme), _stream()))
 
     def hoisting_weighted_bsgs_blocks(self, size_Ql, ct, baby_elts, baby_keys, giant_elts, giant_keys, weights, out, scheme):
         """Several row blocks that share ct and the keys (pha_hoisting_weighted_bsgs_blocks): weights[block][giant][baby] device
         tensors or None, out [blocks][2][Ql][N]; ct is only read."""
-        be = (C.c_uint32 * len(baby_elts))(*[int(e) for e in baby_elts])
-        ge = (C.c_uint32 * len(giant_elts))(*[int(e) for e in giant_elts])
-        bk = (C.c_void_p * len(baby_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in baby_keys])
-        gk = (C.c_void_p * len(giant_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in giant_keys])
-        flat = [w for blk in weights for row in blk for w in row]
-        if len(flat) != len(weights) * len(baby_elts) * len(giant_elts):
-            raise ValueError("weights must be [n_blocks][n_giant][n_baby]")
-        ws = (C.c_void_p * len(flat))(*[_ptr(w) for w in flat])
+        be, bk = _elts_keys(baby_elts, baby_keys)
+        ge, gk = _elts_keys(giant_elts, giant_keys)
+        ws = _weight_ptrs([w for blk in weights for row in blk for w in row], len(weights) * len(baby_elts) * len(giant_elts),
+                          "[n_blocks][n_giant][n_baby]")
         _lib.check(self._L.pha_hoisting_weighted_bsgs_blocks(self._h, size_Ql, _ptr(ct), len(weights), be, len(baby_elts), bk, ge,
                                                              len(giant_elts), gk, ws, _ptr(out), int(scheme), _stream()))
 
@@ -643,8 +646,7 @@ class PhantomContext:
             out = torch.empty_like(ct)
         if ct.shape[0] == 0:             # (an empty tensor has no device pointer to hand over)
             return out
-        elts = (C.c_uint32 * len(galois_elts))(*[int(e) for e in galois_elts])
-        tabs = (C.c_void_p * len(galois_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in galois_keys])
+        elts, tabs = _elts_keys(galois_elts, galois_keys)
         _lib.check(self._L.pha_hoisting_batched(self._h, size_Ql, _ptr(ct), ct.shape[0], elts, len(galois_elts), tabs, int(scheme),
                                                 _ptr(out), chunk, _stream()))
         return out
@@ -656,9 +658,8 @@ class PhantomContext:
             out = torch.empty_like(ct)
         if ct.shape[0] == 0:             # (an empty tensor has no device pointer to hand over)
             return out
-        elts = (C.c_uint32 * len(galois_elts))(*[int(e) for e in galois_elts])
-        tabs = (C.c_void_p * len(galois_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in galois_keys])
-        ws = (C.c_void_p * len(weights))(*[_ptr(w) for w in weights])
+        elts, tabs = _elts_keys(galois_elts, galois_keys)
+        ws = _weight_ptrs(weights)
         _lib.check(self._L.pha_hoisting_weighted_batched(self._h, size_Ql, _ptr(ct), ct.shape[0], elts, len(galois_elts), tabs, ws,
                                                          int(scheme), _ptr(out), chunk, _stream()))
         return out
@@ -672,14 +673,9 @@ class PhantomContext:
             out = torch.empty_like(ct)
         if ct.shape[0] == 0:             # (an empty tensor has no device pointer to hand over)
             return out
-        be = (C.c_uint32 * len(baby_elts))(*[int(e) for e in baby_elts])
-        ge = (C.c_uint32 * len(giant_elts))(*[int(e) for e in giant_elts])
-        bk = (C.c_void_p * len(baby_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in baby_keys])
-        gk = (C.c_void_p * len(giant_keys))(*[k.public_keys_ptr.data_ptr() if k is not None else None for k in giant_keys])
-        flat = [w for row in weights for w in row]
-        if len(flat) != len(baby_elts) * len(giant_elts):
-            raise ValueError("weights must be [n_giant][n_baby]")
-        ws = (C.c_void_p * len(flat))(*[_ptr(w) for w in flat])
+        be, bk = _elts_keys(baby_elts, baby_keys)
+        ge, gk = _elts_keys(giant_elts, giant_keys)
+        ws = _weight_ptrs([w for row in weights for w in row], len(baby_elts) * len(giant_elts), "[n_giant][n_baby]")
         _lib.check(self._L.pha_hoisting_weighted_bsgs_batched(self._h, size_Ql, _ptr(ct), ct.shape[0], be, len(baby_elts), bk, ge,
                                                               len(giant_elts), gk, ws, int(scheme), _ptr(out), chunk, _stream()))
         return out

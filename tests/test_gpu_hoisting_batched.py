@@ -329,3 +329,50 @@ def test_diag_matvec_batch_equals_diag_matvec_per_vector(gpu):
     for b in range(3):
         one = W.diag_matvec(s.ctx, s.ql, d_cts[b], elts, [None] + d_rot, d_w, s.scheme)
         assert np.array_equal(s.P.to_host(out[b]), s.P.to_host(one)), f"vector {b}"
+
+
+# ---- J. refusals of the single entries ------------------------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def single_refusals(gpu):
+    """hyb12_a2, level 6: one ciphertext, two rotation keys and three weights -- made once."""
+    s = Setup("hyb12_a2", O.CKKS, 6, gpu)
+    r = rng_for(9950)
+    _, d_rot, _ = s.keys(r, 2)
+    return s, d_rot, s.weights(r, 3)[1], s.cts(r, 1)[0]
+
+
+SINGLE_REFUSALS = [
+    ("plain", "even", ValueError), ("plain", "beyond_2n", ValueError), ("plain", "missing_key", ArithmeticError),
+    ("weighted", "even", ValueError), ("weighted", "beyond_2n", ValueError), ("weighted", "missing_key", ArithmeticError),
+    ("weighted", "null_weight", ValueError),
+]
+
+
+@pytest.mark.parametrize("form,defect,exc", SINGLE_REFUSALS, ids=[f"{f}-{d}" for f, d, _ in SINGLE_REFUSALS])
+def test_single_entry_refusals_leave_ct_untouched(form, defect, exc, single_refusals, gpu):
+    """pha_hoisting / pha_hoisting_weighted with exactly one defect per call: the exception class, and ct keeps its words."""
+    import torch
+    from phantom_fhe_amd import lib as plib
+    s, d_rot, d_w, ct = single_refusals
+    weighted = form == "weighted"
+    elts = ([1] if weighted else []) + [5, 25]
+    keys = ([None] if weighted else []) + list(d_rot)
+    w = list(d_w)
+    if defect == "even":
+        elts[-1] = 4
+    elif defect == "beyond_2n":
+        elts[-1] = 2 * s.n + 5
+    elif defect == "missing_key":
+        keys[-1] = None
+    else:
+        w[1] = None
+    d_ct = s.P.to_device(ct, gpu)
+    with pytest.raises(exc):
+        if weighted:
+            s.ctx.hoisting_weighted(s.ql, d_ct, elts, keys, w, s.scheme)
+        else:   # (the wrapper takes no None key: the raw entry with a null key table)
+            e = (C.c_uint32 * 2)(*elts)
+            k = (C.c_void_p * 2)(*[None if x is None else x.public_keys_ptr.data_ptr() for x in keys])
+            plib.check(plib.load().pha_hoisting(s.ctx._h, s.ql, d_ct.data_ptr(), e, 2, k, int(s.scheme), torch.cuda.current_stream().cuda_stream))
+    torch.cuda.synchronize()
+    assert np.array_equal(s.P.to_host(d_ct), ct), "a refused call wrote to ct"

@@ -311,3 +311,91 @@ def test_n16_both_sides_of_the_fused_conversion_threshold(batch, n16, gpu):
     got = s.P.to_host(s.batched(s.P.to_device(cts[:batch], gpu), chunk=batch))
     assert np.array_equal(got[0], oracle0), "ciphertext 0 differs from the oracle"
     assert np.array_equal(got, singles[:batch]), "differs from single pha_hoisting_weighted_bsgs calls"
+
+
+# ---- I. refusals of the single and the row-block entry --------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def single_refusals(gpu):
+    """hyb12_a2, level 6, 3 x 2 steps with the identity first, one ciphertext -- made once."""
+    s = Setup("hyb12_a2", O.CKKS, 6, gpu)
+    r = rng_for(6800)
+    s.split(r, 3, 2, True)
+    return s, s.cts(r, 1)[0]
+
+
+@pytest.mark.parametrize("defect,exc", [("even", ValueError), ("beyond_2n", ValueError), ("missing_key", ArithmeticError)])
+@pytest.mark.parametrize("side", ["baby", "giant"])
+def test_single_entry_refusals_leave_ct_untouched(side, defect, exc, single_refusals, gpu):
+    """pha_hoisting_weighted_bsgs with exactly one defect per call: the exception class, and ct keeps its words."""
+    import torch
+    s, ct = single_refusals
+    baby, giant, bk, gk = list(s.baby), list(s.giant), list(s.d_bk), list(s.d_gk)
+    elts, keys = (baby, bk) if side == "baby" else (giant, gk)
+    if defect == "even":
+        elts[-1] = 4
+    elif defect == "beyond_2n":
+        elts[-1] = 2 * s.n + 5
+    else:
+        keys[-1] = None
+    d_ct = s.P.to_device(ct, gpu)
+    with pytest.raises(exc):
+        s.ctx.hoisting_weighted_bsgs(s.ql, d_ct, baby, bk, giant, gk, s.d_w, s.scheme)
+    torch.cuda.synchronize()
+    assert np.array_equal(s.P.to_host(d_ct), ct), "a refused call wrote to ct"
+
+
+def test_single_entry_refuses_five_digits(gpu):
+    """beta = 5 (hyb13_b5, level 10): pha_hoisting_weighted_bsgs refuses, ct keeps its words."""
+    import torch
+    s = Setup("hyb13_b5", O.CKKS, 10, gpu)
+    assert s.tool.beta == 5
+    r = rng_for(6850)
+    s.split(r, 2, 2, True, pool=1)
+    ct = s.cts(r, 1)[0]
+    d_ct = s.P.to_device(ct, gpu)
+    with pytest.raises(ValueError):
+        s.ctx.hoisting_weighted_bsgs(s.ql, d_ct, s.baby, s.d_bk, s.giant, s.d_gk, s.d_w, s.scheme)
+    torch.cuda.synchronize()
+    assert np.array_equal(s.P.to_host(d_ct), ct), "a refused call wrote to ct"
+
+
+def test_blocks_entry_refuses_out_overlapping_ct(single_refusals, gpu):
+    """pha_hoisting_weighted_bsgs_blocks, one block whose out starts at ct's second polynomial: refused, nothing written."""
+    import torch
+    s, ct = single_refusals
+    polys = np.concatenate([ct, np.full((1, s.ql, s.n), CANARY, dtype=np.uint64)])
+    buf = s.P.to_device(polys, gpu)
+    with pytest.raises(ValueError):
+        s.ctx.hoisting_weighted_bsgs_blocks(s.ql, buf[:2], s.baby, s.d_bk, s.giant, s.d_gk, [s.d_w], buf[1:].view(1, 2, s.ql, s.n), s.scheme)
+    torch.cuda.synchronize()
+    assert np.array_equal(s.P.to_host(buf), polys), "a refused call wrote to the overlapping buffers"
+
+
+# ---- J. one scratch claim per call ----------------------------------------------------------------------------------------------
+def test_tail_of_one_on_a_fresh_and_on_a_warm_context(five, gpu):
+    """Five ciphertexts at the default chunk (a group of four and a tail of one) as the FIRST hoisting call of a new context, whose
+    scratch arena therefore grows inside this call, then the same call again on the warm context: both equal five single calls."""
+    s, cts, ref = five
+    fresh = s.P.PhantomContext(s.log_n, list(s.primes), s.size_p, device=gpu)
+    d_ct = s.P.to_device(cts, gpu)
+    for state in ("fresh", "warm"):
+        got = fresh.hoisting_weighted_bsgs_batched(s.ql, d_ct, s.baby, s.d_bk, s.giant, s.d_gk, s.d_w, s.scheme)
+        assert np.array_equal(s.P.to_host(got), ref), f"{state} context: differs from five calls of pha_hoisting_weighted_bsgs"
+    assert np.array_equal(s.P.to_host(d_ct), cts), "ct is only read"
+
+
+# ---- K. one row block ------------------------------------------------------------------------------------------------------------
+def test_one_row_block_equals_the_single_entry_and_the_oracle(gpu):
+    """pha_hoisting_weighted_bsgs_blocks at n_blocks = 1 with nine giant steps (the NG ladder runs 8 + 1): word for word
+    pha_hoisting_weighted_bsgs on a copy, and the oracle."""
+    s = Setup("hyb13_a3", O.CKKS, 9, gpu)
+    r = rng_for(6900)
+    s.split(r, 2, 9, True, pool=3)
+    ct = s.cts(r, 1)[0]
+    d_ct = s.P.to_device(ct, gpu)
+    out = s.P.to_device(np.full((1,) + ct.shape, CANARY, dtype=np.uint64), gpu)
+    s.ctx.hoisting_weighted_bsgs_blocks(s.ql, d_ct, s.baby, s.d_bk, s.giant, s.d_gk, [s.d_w], out, s.scheme)
+    got = s.P.to_host(out)[0]
+    assert np.array_equal(s.P.to_host(d_ct), ct), "ct is only read"
+    assert np.array_equal(got, s.singles(ct[None])[0]), "differs from pha_hoisting_weighted_bsgs"
+    assert np.array_equal(got, s.oracle(ct)), "differs from the oracle"
