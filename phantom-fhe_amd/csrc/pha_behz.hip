@@ -508,13 +508,11 @@ extern "C" int pha_keyswitch_inplace_bfv_leveled(pha_context_t ctx, size_t size_
 constexpr size_t kBfvBatchChunk = 8;
 constexpr size_t kBfvMaxChunk = 1024;   // 3 * chunk polynomials ride in grid z / y (limit 65535)
 
-static bool bfv_overlaps(const u64 *a, size_t na, const u64 *b, size_t nb) { return a < b + nb && b < a + na; }
-
 // refusals and strict checks shared by every multiply entry (`name`: the entry, for the strict message); returns the pairs per chunk
 static size_t bfv_batched_begin(Context &c, const char *name, const u64 *ct1, const u64 *ct2, const u64 *dst, size_t batch,
                                 size_t chunk, hipStream_t s) {
     const size_t qn = (size_t)c.size_q * c.n;
-    if (bfv_overlaps(dst, batch * 3 * qn, ct1, batch * 2 * qn) || bfv_overlaps(dst, batch * 3 * qn, ct2, batch * 2 * qn))
+    if (overlaps(dst, batch * 3 * qn, ct1, batch * 2 * qn) || overlaps(dst, batch * 3 * qn, ct2, batch * 2 * qn))
         throw std::invalid_argument("dst must not overlap ct1 or ct2");
     if (strict_mode()) {   // large batches in pieces of at most 65534 polynomials (grid z); never skipped
         const std::string n1 = std::string(name) + " ct1", n2 = std::string(name) + " ct2";

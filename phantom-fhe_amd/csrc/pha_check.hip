@@ -144,6 +144,15 @@ void strict_plain(Context &c, const char *what, const u64 *data, u64 t, size_t p
         throw std::invalid_argument(std::string("PHA_STRICT: ") + what + " holds " + std::to_string(host) +
                                     " word(s) >= the plain modulus (a bfv plaintext's words are below t; include/phantom_amd.h)");
 }
+void strict_sum_operand(Context &c, const char *what, const SumOperand &op, size_t cms, size_t terms, size_t batch, bool raw, hipStream_t s) {
+    if (!strict_mode() || !op.p) return;
+    auto run = [&](const u64 *base, size_t polys, size_t stride) {
+        if (raw) strict_plain(c, what, base, c.plain_t, polys, stride, s);
+        else strict_operand(c, what, base, rows_plain(0, cms), (uint32_t)polys, stride, s);
+    };
+    if (raw) op.strict_runs(terms, batch, run, SIZE_MAX);   // strict_plain cuts a group's terms into counts itself and reports their sum
+    else op.strict_runs(terms, batch, run);
+}
 void strict_keys(Context &c, const char *what, const u64 *const *keys, uint32_t n_keys, uint32_t size_Ql, hipStream_t s) {
     if (!strict_mode() || !keys) return;
     const u64 bad = count_noncanonical_keys(c, keys, n_keys, size_Ql, s);

@@ -16,6 +16,7 @@
 
 #include "pha_arith.h"
 #include "pha_rns_tables.h"
+#include "pha_sum_operand.h"   // overlaps(), SumOperand
 
 namespace pha {
 
@@ -356,6 +357,9 @@ u64 count_noncanonical_keys(Context &c, const u64 *const *keys, uint32_t n_keys,
 void strict_operand(Context &c, const char *what, const u64 *data, const RowMap &rows, uint32_t polys, size_t poly_stride, hipStream_t s);
 void strict_keys(Context &c, const char *what, const u64 *const *keys, uint32_t n_keys, uint32_t size_Ql, hipStream_t s);
 void strict_plain(Context &c, const char *what, const u64 *data, u64 t, size_t polys, size_t stride, hipStream_t s);   // raw bfv plaintexts: words below t
+// every distinct polynomial of a summed-product operand over rows [0, cms), in the runs of SumOperand::strict_runs; raw: the
+// elements are raw bfv plaintexts (words below t), a group's terms in one strict_plain call.  An absent operand is skipped
+void strict_sum_operand(Context &c, const char *what, const SumOperand &op, size_t cms, size_t terms, size_t batch, bool raw, hipStream_t s);
 
 // NTT drivers (pha_ntt.hip): pass 1 reads `in` and writes `mid`, pass 2 reads `mid` and writes `out`
 struct NttExtra {
@@ -457,7 +461,6 @@ struct KsScratch {
 
 bool ntt_domain_scheme(int scheme);   // ckks / bgv: true, bfv: false; throws on anything else
 void check_level(Context &c, size_t size_Ql, bool need_p);
-bool overlaps(const u64 *a, size_t na, const u64 *b, size_t nb);
 // argument checks shared by the entry points
 inline void need(const void *p) {
     if (!p) throw std::invalid_argument("null device pointer");
@@ -582,13 +585,19 @@ void launch_tensor(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs,
 void launch_tensor_batched(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, uint32_t remap_from, uint32_t remap_add,
                            bool square, size_t batch, hipStream_t s);
 void launch_add(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, size_t mod_start, hipStream_t s);
-// plain_sum_kernel (pha_poly.hip), launch only: res[g] = acc[g] + sum_k plain[g][k] (.) ct[g][k]; strides as pha_multiply_plain_sum_batched
-void launch_plain_sum(Context &c, const u64 *plain, const u64 *ct, const u64 *acc, u64 *res, size_t cms, size_t terms, size_t batch,
-                      size_t tp, size_t bp, size_t tc, size_t bc, size_t ba, hipStream_t s);
-// does out [out_words] touch any of the operand's buffers (op_words each at op + g * bs + k * ts)?
-bool touches_operand(const u64 *out, size_t out_words, const u64 *op, size_t terms, size_t batch, size_t ts, size_t bs, size_t op_words);
-// strict mode: every distinct [2][L][N] ciphertext of an operand (pha_poly.hip)
-void sum_strict(Context &c, const char *what, const u64 *op, size_t cms, size_t terms, size_t batch, size_t ts, size_t bs, hipStream_t s);
+// plain_sum_kernel (pha_poly.hip), launch only: res[g] = acc[g] + sum_k plain[g][k] (.) ct[g][k]; acc may be absent (a null view)
+void launch_plain_sum(Context &c, const SumOperand &plain, const SumOperand &ct, const SumOperand &acc, u64 *res, size_t cms, size_t terms,
+                      size_t batch, hipStream_t s);
+// the views of the summed-product entries (pha_sum_operand.h) over `ln` = L * N words per polynomial: a ciphertext per term, a
+// polynomial per term, one ciphertext per group (an addend, or a work buffer's partial sums)
+inline SumOperand sum_ct(const u64 *p, size_t ts, size_t bs, size_t ln, const char *crowded) { return SumOperand{p, ts, bs, 2 * ln, 2, crowded}; }
+inline SumOperand sum_poly(const u64 *p, size_t ts, size_t bs, size_t words, const char *crowded) { return SumOperand{p, ts, bs, words, 1, crowded}; }
+inline SumOperand sum_acc(const u64 *p, size_t bs, size_t ln) { return SumOperand{p, 0, bs, 2 * ln, 2, nullptr}; }
+// the four wordings of "term stride below the element size" (SumOperand::crowded)
+constexpr const char *kSumCrowded = "term stride below 2 * L * N: the terms of an operand overlap";
+constexpr const char *kPlainCrowded = "plain term stride below L * N: the terms of plain overlap";
+constexpr const char *kRawPlainCrowded = "plain term stride below N: the terms of plain overlap";
+constexpr const char *kCtCrowded = "ct term stride below 2 * L * N: the terms of ct overlap";
 
 void register_context(Context *c, bool alive);   // live-context list walked by the per-thread arena reaper
 

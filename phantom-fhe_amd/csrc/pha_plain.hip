@@ -58,45 +58,27 @@ constexpr size_t kBfvSumSlab = 4;
 // pha_bfv_plain_inner_product_batched (raw == true: [N] words below t).  Slabs of terms outside, chunks of groups inside, so that
 // an operand shared between the groups is transformed once per slab for ALL groups; the NTT-form partial sums live in res
 // (plain_sum_kernel's acc == res mode) and a chunk is taken back to coefficient form right behind its last slab.
-static void bfv_plain_sum(Context &c, size_t size_Ql, const u64 *plain, bool raw, const u64 *ct, const u64 *acc, u64 *res, size_t terms,
-                          size_t batch, size_t tp, size_t bp, size_t tc, size_t bc, size_t ba, size_t chunk, size_t slab, void *stream) {
-    need(plain); need(ct); need(res);
+static void bfv_plain_sum(Context &c, size_t size_Ql, const SumOperand &plain, bool raw, const SumOperand &ct, const SumOperand &acc,
+                          u64 *res, size_t terms, size_t batch, size_t chunk, size_t slab, void *stream) {
+    need(plain.p); need(ct.p); need(res);
     bfv_sum_level(c, size_Ql);
-    const size_t ln = size_Ql * c.n, pn = raw ? c.n : ln;   // words of one plaintext operand
-    if (terms == 0) throw std::invalid_argument("terms must be at least 1");
-    if (terms > 0xffffffffull) throw std::invalid_argument("terms out of range");
-    if ((tp | bp | tc | bc | ba) & 1) throw std::invalid_argument("strides must be even (16-byte loads)");
-    if ((reinterpret_cast<uintptr_t>(plain) | reinterpret_cast<uintptr_t>(ct) | reinterpret_cast<uintptr_t>(acc) |
-         reinterpret_cast<uintptr_t>(res)) & 15)
-        throw std::invalid_argument("buffers must be 16-byte aligned");
-    if (terms > 1 && tp < pn)
-        throw std::invalid_argument(raw ? "plain term stride below N: the terms of plain overlap"
-                                        : "plain term stride below L * N: the terms of plain overlap");
-    if (terms > 1 && tc < 2 * ln) throw std::invalid_argument("ct term stride below 2 * L * N: the terms of ct overlap");
-    if (batch == 0) return;
+    const size_t ln = size_Ql * c.n;
+    sum_check_terms(terms);
+    sum_check_layout({plain, ct, acc}, terms, res);
     const size_t res_words = batch * 2 * ln;
-    if (touches_operand(res, res_words, plain, terms, batch, tp, bp, pn))
-        throw std::invalid_argument("res must not overlap a plaintext operand");
-    if (touches_operand(res, res_words, ct, terms, batch, tc, bc, 2 * ln))
-        throw std::invalid_argument("res must not overlap an operand ciphertext");
-    if (acc && touches_operand(res, res_words, acc, 1, batch, 0, ba, 2 * ln)) throw std::invalid_argument("res must not overlap acc");
+    if (plain.touches(res, res_words, terms, batch)) throw std::invalid_argument("res must not overlap a plaintext operand");
+    if (ct.touches(res, res_words, terms, batch)) throw std::invalid_argument("res must not overlap an operand ciphertext");
+    if (acc.p && acc.touches(res, res_words, 1, batch)) throw std::invalid_argument("res must not overlap acc");
+    if (batch == 0) return;
     hipStream_t s = as_stream(stream);
-    if (strict_mode()) {
-        for (size_t g = 0; g < (bp ? batch : 1); g++) {
-            if (raw) strict_plain(c, "bfv_plain_inner_product plain", plain + g * bp, c.plain_t, terms, tp, s);
-            else
-                for (size_t k0 = 0; k0 < terms; k0 += 65535)
-                    strict_operand(c, "bfv_multiply_plain_sum plain", plain + g * bp + k0 * tp, rows_plain(0, size_Ql),
-                                   (uint32_t)std::min<size_t>(65535, terms - k0), tp, s);
-        }
-        const char *entry = raw ? "bfv_plain_inner_product" : "bfv_multiply_plain_sum";
-        sum_strict(c, (std::string(entry) + " ct").c_str(), ct, size_Ql, terms, batch, tc, bc, s);
-        if (acc) sum_strict(c, (std::string(entry) + " acc").c_str(), acc, size_Ql, 1, batch, 0, ba, s);
-    }
+    strict_sum_operand(c, raw ? "bfv_plain_inner_product plain" : "bfv_multiply_plain_sum plain", plain, size_Ql, terms, batch, raw, s);
+    strict_sum_operand(c, raw ? "bfv_plain_inner_product ct" : "bfv_multiply_plain_sum ct", ct, size_Ql, terms, batch, false, s);
+    strict_sum_operand(c, raw ? "bfv_plain_inner_product acc" : "bfv_multiply_plain_sum acc", acc, size_Ql, 1, batch, false, s);
+    const size_t tp = plain.ts, tc = ct.ts;
     // 2 * chunk polynomials per inverse and 2 * slab per forward launch: both within a launch's grid
     const size_t C = std::min<size_t>(std::min(chunk ? chunk : kBfvSumChunk, batch), 32767);
     const size_t S = std::min<size_t>(std::min(slab ? slab : kBfvSumSlab, terms), 32767);
-    const bool ct_shared = bc == 0, pl_shared = bp == 0;
+    const bool ct_shared = ct.bs == 0, pl_shared = plain.bs == 0;
     const size_t wct_words = (ct_shared ? 1 : C) * S * 2 * ln, wpl_words = raw ? (pl_shared ? 1 : C) * S * ln : 0;
     u64 *wct = c.scratch_outer(stream, wct_words + wpl_words), *wpl = wct + wct_words;
     const LimbSel sel = plain_sel(0, size_Ql);
@@ -115,28 +97,30 @@ static void bfv_plain_sum(Context &c, size_t size_Ql, const u64 *plain, bool raw
     for (size_t k0 = 0; k0 < terms; k0 += S) {
         const size_t K = std::min(S, terms - k0);
         const bool first = k0 == 0, last = k0 + K == terms;
-        if (ct_shared) forward_ct(ct + k0 * tc, K, wct);
-        if (raw && pl_shared) launch_bfv_lift(c, size_Ql, plain + k0 * tp, K, tp, wpl, ln, s);
+        if (ct_shared) forward_ct(ct.at(0, k0), K, wct);
+        if (raw && pl_shared) launch_bfv_lift(c, size_Ql, plain.at(0, k0), K, tp, wpl, ln, s);
         for (size_t b0 = 0; b0 < batch; b0 += C) {
             const size_t B = std::min(C, batch - b0);
             for (size_t g = 0; g < B; g++) {
-                if (!ct_shared) forward_ct(ct + (b0 + g) * bc + k0 * tc, K, wct + g * S * 2 * ln);
-                if (raw && !pl_shared) launch_bfv_lift(c, size_Ql, plain + (b0 + g) * bp + k0 * tp, K, tp, wpl + g * S * ln, ln, s);
+                if (!ct_shared) forward_ct(ct.at(b0 + g, k0), K, wct + g * S * 2 * ln);
+                if (raw && !pl_shared) launch_bfv_lift(c, size_Ql, plain.at(b0 + g, k0), K, tp, wpl + g * S * ln, ln, s);
             }
             u64 *r = res + b0 * 2 * ln;
-            const u64 *pl = raw ? wpl : plain + b0 * bp + k0 * tp;
-            launch_plain_sum(c, pl, wct, first ? nullptr : r, r, size_Ql, K, B, raw ? ln : tp, raw ? (pl_shared ? 0 : S * ln) : bp, 2 * ln,
-                             ct_shared ? 0 : S * 2 * ln, 2 * ln, s);
+            // the work buffers hold a group's slab densely: [S] lifted plaintexts, [S] ciphertexts; the partial sums are res itself
+            const SumOperand w_plain = raw ? sum_poly(wpl, ln, pl_shared ? 0 : S * ln, ln, nullptr) : plain.advanced(b0, k0),
+                             w_ct = sum_ct(wct, 2 * ln, ct_shared ? 0 : S * 2 * ln, ln, nullptr),
+                             partial = sum_acc(first ? nullptr : r, 2 * ln, ln);
+            launch_plain_sum(c, w_plain, w_ct, partial, r, size_Ql, K, B, s);
             if (!last) continue;
             NttExtra x;   // the chunk's 2 B polynomials back to coefficient form, in place; group g adds acc (g) in the final store
             x.batch = (uint32_t)(2 * B);
             x.poly_stride = ln;
-            if (acc) {
-                x.aux = acc + b0 * ba;
+            if (acc.p) {
+                x.aux = acc.at(b0, 0);
                 x.aux_stride = ln;
-                x.aux_pair_stride = ba;
+                x.aux_pair_stride = acc.bs;
             }
-            ntt_inverse(c, r, r, r, sel, acc ? EPI_INV_CANON_ADD : EPI_INV_CANON, x, s);
+            ntt_inverse(c, r, r, r, sel, acc.p ? EPI_INV_CANON_ADD : EPI_INV_CANON, x, s);
         }
     }
 }
@@ -209,7 +193,7 @@ int pha_bfv_lift_plain_batched(pha_context_t ctx, size_t size_Ql, const uint64_t
         throw std::invalid_argument("buffers must be 16-byte aligned");
     if (count > 1 && out_stride < ln) throw std::invalid_argument("out stride below L * N: the lifted plaintexts overlap");
     if (count == 0) return 0;
-    if (touches_operand(out, (count - 1) * out_stride + ln, plain, count, 1, plain_stride, 0, c.n))
+    if (sum_poly(plain, plain_stride, 0, c.n, nullptr).touches(out, (count - 1) * out_stride + ln, count, 1))
         throw std::invalid_argument("out must not overlap a plaintext operand");
     hipStream_t s = as_stream(stream);
     strict_plain(c, "bfv_lift_plain plain", plain, c.plain_t, count > 1 && plain_stride == 0 ? 1 : count, plain_stride, s);
@@ -222,8 +206,10 @@ int pha_bfv_multiply_plain_sum_batched(pha_context_t ctx, size_t size_Ql, const 
                                        size_t plain_batch_stride, size_t ct_term_stride, size_t ct_batch_stride,
                                        size_t acc_batch_stride, size_t chunk, size_t slab, void *stream) {
     PHA_CTX_BEGIN(ctx)
-    bfv_plain_sum(ctx->c, size_Ql, plain_ntt, false, ct, acc, res, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride,
-                  ct_batch_stride, acc_batch_stride, chunk, slab, stream);
+    const size_t ln = size_Ql * ctx->c.n;
+    bfv_plain_sum(ctx->c, size_Ql, sum_poly(plain_ntt, plain_term_stride, plain_batch_stride, ln, kPlainCrowded), false,
+                  sum_ct(ct, ct_term_stride, ct_batch_stride, ln, kCtCrowded), sum_acc(acc, acc_batch_stride, ln), res, terms, batch, chunk,
+                  slab, stream);
     PHA_API_END
 }
 
@@ -232,8 +218,10 @@ int pha_bfv_plain_inner_product_batched(pha_context_t ctx, size_t size_Ql, const
                                         size_t plain_batch_stride, size_t ct_term_stride, size_t ct_batch_stride,
                                         size_t acc_batch_stride, size_t chunk, size_t slab, void *stream) {
     PHA_CTX_BEGIN(ctx)
-    bfv_plain_sum(ctx->c, size_Ql, plain, true, ct, acc, res, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride,
-                  ct_batch_stride, acc_batch_stride, chunk, slab, stream);
+    const size_t ln = size_Ql * ctx->c.n;
+    bfv_plain_sum(ctx->c, size_Ql, sum_poly(plain, plain_term_stride, plain_batch_stride, ctx->c.n, kRawPlainCrowded), true,
+                  sum_ct(ct, ct_term_stride, ct_batch_stride, ln, kCtCrowded), sum_acc(acc, acc_batch_stride, ln), res, terms, batch, chunk,
+                  slab, stream);
     PHA_API_END
 }
 

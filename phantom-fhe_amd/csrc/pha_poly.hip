@@ -332,11 +332,11 @@ __global__ __launch_bounds__(kEwThreads) void tensor_sum_kernel(const SumArgs k)
 constexpr size_t kSumCachedResultBytes = (size_t)128 << 20;
 
 // launch only: the callers have validated (sum_check below)
-static void launch_tensor_sum(Context &c, const u64 *op1, const u64 *op2, u64 *res01, u64 *res2, size_t cms, size_t terms, size_t batch,
-                              size_t t1, size_t b1, size_t t2, size_t b2, hipStream_t s) {
-    SumArgs k{op1, op2, res01, res2, c.d_mod.p, c.d_fpinfo.p, (uint32_t)c.n, (uint32_t)cms, (uint32_t)terms, t1, b1, t2, b2};
+static void launch_tensor_sum(Context &c, const SumOperand &a, const SumOperand &b, u64 *res01, u64 *res2, size_t cms, size_t terms,
+                              size_t batch, hipStream_t s) {
+    SumArgs k{a.p, b.p, res01, res2, c.d_mod.p, c.d_fpinfo.p, (uint32_t)c.n, (uint32_t)cms, (uint32_t)terms, a.ts, a.bs, b.ts, b.bs};
     const dim3 grid((unsigned)(c.n / (kEwThreads * kEwPerThread)), (unsigned)cms, (unsigned)batch), block(kEwThreads);
-    const bool st_nt = batch * 3 * cms * c.n * sizeof(u64) > kSumCachedResultBytes, b_nt = !(b2 == 0 && batch > 1);
+    const bool st_nt = batch * 3 * cms * c.n * sizeof(u64) > kSumCachedResultBytes, b_nt = !b.shared(batch);
     if (b_nt && st_nt) hipLaunchKernelGGL((tensor_sum_kernel<true, true>), grid, block, 0, s, k);
     else if (b_nt) hipLaunchKernelGGL((tensor_sum_kernel<true, false>), grid, block, 0, s, k);
     else if (st_nt) hipLaunchKernelGGL((tensor_sum_kernel<false, true>), grid, block, 0, s, k);
@@ -406,13 +406,14 @@ __global__ __launch_bounds__(kEwThreads, 8) void plain_sum_kernel(const PlainSum
     st2<ST_NT>(r + rc, r1);
 }
 
-// launch only: the callers have validated (plain_sum_check below)
-void launch_plain_sum(Context &c, const u64 *plain, const u64 *ct, const u64 *acc, u64 *res, size_t cms, size_t terms,
-                             size_t batch, size_t tp, size_t bp, size_t tc, size_t bc, size_t ba, hipStream_t s) {
-    PlainSumArgs k{plain, ct, acc, res, c.d_mod.p, c.d_fpinfo.p, (uint32_t)c.n, (uint32_t)cms, (uint32_t)terms, tp, bp, tc, bc, ba};
+// launch only: the callers have validated (sum_check below)
+void launch_plain_sum(Context &c, const SumOperand &plain, const SumOperand &ct, const SumOperand &acc, u64 *res, size_t cms, size_t terms,
+                      size_t batch, hipStream_t s) {
+    PlainSumArgs k{plain.p,  ct.p,     acc.p, res,   c.d_mod.p, c.d_fpinfo.p, (uint32_t)c.n, (uint32_t)cms, (uint32_t)terms,
+                   plain.ts, plain.bs, ct.ts, ct.bs, acc.bs};
     const dim3 grid((unsigned)(c.n / (kEwThreads * kEwPerThread)), (unsigned)cms, (unsigned)batch), block(kEwThreads);
     const bool st_nt = batch * 2 * cms * c.n * sizeof(u64) > kSumCachedResultBytes;
-    const bool pl_nt = !(bp == 0 && batch > 1), ct_nt = !(bc == 0 && batch > 1);
+    const bool pl_nt = !plain.shared(batch), ct_nt = !ct.shared(batch);
 #define PHA_PLAIN_SUM_LAUNCH(P, C, S) hipLaunchKernelGGL((plain_sum_kernel<P, C, S>), grid, block, 0, s, k)
     if (pl_nt && ct_nt) { if (st_nt) PHA_PLAIN_SUM_LAUNCH(true, true, true); else PHA_PLAIN_SUM_LAUNCH(true, true, false); }
     else if (pl_nt) { if (st_nt) PHA_PLAIN_SUM_LAUNCH(true, false, true); else PHA_PLAIN_SUM_LAUNCH(true, false, false); }
@@ -433,65 +434,34 @@ void launch_add(Context &c, const u64 *a, const u64 *b, u64 *r, size_t limbs, si
 
 using namespace pha;
 
-// ---- summed tensor product and the inner-product entries (extension) ------------------------------------------------------------
-static bool ranges_overlap(const u64 *a, size_t na, const u64 *b, size_t nb) { return a < b + nb && b < a + na; }
+// ---- the summed-product entries (extension): what they share on the host --------------------------------------------------------
+// Every strided operand is a SumOperand view (pha_sum_operand.h: the address arithmetic, the layout refusals, the output-overlap
+// walk and the strict-mode runs); the entries add what is theirs: the limb count, the batch one launch takes, their outputs.
 
-// does out [out_words] touch any operand ciphertext (2 L N words at op + g * bs + k * ts)?  The span of all of them first: the
-// usual call is answered by one comparison
-bool pha::touches_operand(const u64 *out, size_t out_words, const u64 *op, size_t terms, size_t batch, size_t ts, size_t bs,
-                            size_t ct_words) {
-    const size_t groups = bs ? batch : 1;
-    if (!ranges_overlap(out, out_words, op, (groups - 1) * bs + (terms - 1) * ts + ct_words)) return false;
-    for (size_t g = 0; g < groups; g++)
-        for (size_t k = 0; k < terms; k++)
-            if (ranges_overlap(out, out_words, op + g * bs + k * ts, ct_words)) return true;
-    return false;
-}
-
-// the refusals the three entries share (everything but their outputs)
-static void sum_check(Context &c, const u64 *op1, const u64 *op2, size_t cms, size_t terms, size_t batch, size_t t1, size_t b1,
-                      size_t t2, size_t b2) {
-    if (terms == 0) throw std::invalid_argument("terms must be at least 1");
-    if (terms > 0xffffffffull) throw std::invalid_argument("terms out of range");
+// the refusals about everything but the outputs: terms, limb count, batch (the group is blockIdx.z of ONE launch), layout
+static void sum_check(Context &c, std::initializer_list<SumOperand> ops, size_t cms, size_t terms, size_t batch) {
+    sum_check_terms(terms);
     if (cms == 0 || cms > c.rows) throw std::invalid_argument("coeff_mod_size out of range");
     if (batch > 65535) throw std::invalid_argument("batch out of range");
-    if ((t1 | b1 | t2 | b2) & 1) throw std::invalid_argument("strides must be even (16-byte loads)");
-    if ((reinterpret_cast<uintptr_t>(op1) | reinterpret_cast<uintptr_t>(op2)) & 15)
-        throw std::invalid_argument("buffers must be 16-byte aligned");
-    if (terms > 1 && (t1 < 2 * cms * c.n || t2 < 2 * cms * c.n))
-        throw std::invalid_argument("term stride below 2 * L * N: the terms of an operand overlap");
+    sum_check_layout(ops, terms);
 }
 
-static void sum_check_output(Context &c, const char *name, const u64 *out, size_t out_words, const u64 *op1, const u64 *op2, size_t cms,
-                             size_t terms, size_t batch, size_t t1, size_t b1, size_t t2, size_t b2) {
+// an output is aligned and touches no operand; the refusal calls operand i `what` (an absent operand is skipped)
+struct SumInput {
+    SumOperand op;
+    const char *what;
+};
+static void sum_check_output(const char *name, const u64 *out, size_t out_words, std::initializer_list<SumInput> ins, size_t terms,
+                             size_t batch) {
     if (reinterpret_cast<uintptr_t>(out) & 15) throw std::invalid_argument("buffers must be 16-byte aligned");
-    const size_t ct_words = 2 * cms * c.n;
-    if (batch && (touches_operand(out, out_words, op1, terms, batch, t1, b1, ct_words) ||
-                  touches_operand(out, out_words, op2, terms, batch, t2, b2, ct_words)))
-        throw std::invalid_argument(std::string(name) + " must not overlap an operand ciphertext");
-}
-
-// strict mode: every distinct operand ciphertext, in runs of at most 65534 polynomials per count (grid z); never skipped
-void pha::sum_strict(Context &c, const char *what, const u64 *op, size_t cms, size_t terms, size_t batch, size_t ts, size_t bs,
-                       hipStream_t s) {
-    if (!strict_mode()) return;
-    const size_t ln = cms * c.n, groups = bs ? batch : 1;
-    for (size_t g = 0; g < groups; g++) {
-        const u64 *base = op + g * bs;
-        if (terms == 1 || ts == 2 * ln) {   // dense terms: [terms][2] polynomials in a row
-            for (size_t k0 = 0; k0 < terms; k0 += 32767)
-                strict_operand(c, what, base + k0 * 2 * ln, rows_plain(0, cms), (uint32_t)(2 * std::min<size_t>(32767, terms - k0)), ln, s);
-        } else {                            // c0 of every term, then c1 of every term
-            for (size_t half = 0; half < 2; half++)
-                for (size_t k0 = 0; k0 < terms; k0 += 65535)
-                    strict_operand(c, what, base + half * ln + k0 * ts, rows_plain(0, cms), (uint32_t)std::min<size_t>(65535, terms - k0), ts, s);
-        }
-    }
+    for (const SumInput &in : ins)
+        if (in.op.p && in.op.touches(out, out_words, terms, batch))
+            throw std::invalid_argument(std::string(name) + " must not overlap " + in.what);
 }
 
 constexpr size_t kInnerProductChunk = 8;   // groups per set of launches, as the batched BFV multiplies (pha_behz.hip: kBfvBatchChunk)
 
-// groups per set of launches of the two whole-operation entries: what the batched key switch takes in one call
+// groups per set of launches of the whole-operation entries: what the batched key switch takes in one call
 static size_t inner_product_chunk(Context &c, size_t size_Ql, size_t chunk, size_t batch) {
     if (chunk == 0) chunk = kInnerProductChunk;
     chunk = std::min<size_t>(std::min(chunk, batch), 1024);
@@ -500,47 +470,63 @@ static size_t inner_product_chunk(Context &c, size_t size_Ql, size_t chunk, size
     return chunk;
 }
 
+// The whole operations: the summed tensor product of a chunk of groups, then ONE batched key switch for the chunk (the key
+// switch is linear: relinearizing the sum is relinearizing every product, at 1 / terms of the cost).  The working buffers are the
+// call's own (ONE scratch_outer claim: the key switch uses the stream's arena) and sized by the chunk; nothing is copied.
+// What differs between the three entries, apart from the preconditions each checks itself, is the closing call:
+enum class InnerProductClose {
+    Rescale,     // pha_keyswitch_rescale_batched: the sums in scratch, dst [batch][2][Ql - 1][N]
+    InPlace,     // pha_keyswitch_inplace_batched: (c0, c1) summed straight into dst [batch][2][Ql][N], which it completes in place
+    ModSwitch,   // pha_keyswitch_mod_switch_batched (bgv): as Rescale
+};
+static int inner_product(pha_context_t ctx, InnerProductClose close, size_t size_Ql, const SumOperand &op1, const SumOperand &op2,
+                         size_t terms, size_t batch, const u64 *const *rlk, int scheme, u64 *dst, size_t chunk, void *stream) {
+    Context &c = ctx->c;
+    const bool in_dst = close == InnerProductClose::InPlace;
+    sum_check(c, {op1, op2}, size_Ql, terms, batch);
+    const size_t ql_n = size_Ql * c.n, out_n = in_dst ? ql_n : ql_n - c.n;
+    sum_check_output("dst", dst, batch * 2 * out_n, {{op1, "an operand ciphertext"}, {op2, "an operand ciphertext"}}, terms, batch);
+    if (batch == 0) return 0;
+    hipStream_t s = as_stream(stream);
+    strict_sum_operand(c, "tensor_prod_2x2_sum operand1", op1, size_Ql, terms, batch, false, s);
+    strict_sum_operand(c, "tensor_prod_2x2_sum operand2", op2, size_Ql, terms, batch, false, s);
+    const size_t C = inner_product_chunk(c, size_Ql, chunk, batch);
+    // the sums of a chunk: [C][2][Ql][N] | [C][Ql][N], or c2 alone
+    u64 *work = c.scratch_outer(stream, C * (in_dst ? 1 : 3) * ql_n), *s2 = in_dst ? work : work + C * 2 * ql_n;
+    for (size_t b0 = 0; b0 < batch; b0 += C) {
+        const size_t B = std::min(C, batch - b0);
+        u64 *out = dst + b0 * 2 * out_n, *s01 = in_dst ? out : work;
+        launch_tensor_sum(c, op1.advanced(b0, 0), op2.advanced(b0, 0), s01, s2, size_Ql, terms, B, s);
+        int rc = 0;
+        switch (close) {
+            case InnerProductClose::Rescale: rc = pha_keyswitch_rescale_batched(ctx, size_Ql, s01, s2, B, rlk, out, stream); break;
+            case InnerProductClose::InPlace: rc = pha_keyswitch_inplace_batched(ctx, size_Ql, out, s2, B, rlk, scheme, stream); break;
+            case InnerProductClose::ModSwitch: rc = pha_keyswitch_mod_switch_batched(ctx, size_Ql, s01, s2, B, rlk, out, stream); break;
+        }
+        if (rc != 0) return rc;   // (its message is the last error)
+    }
+    return 0;
+}
+
 // ---- plaintext-weighted sums (extension) -----------------------------------------------------------------------------------------
-// the refusals the two entries share (everything but their outputs); plaintext (g, k) is L N words at plain + g * bp + k * tp,
-// ciphertext (g, k) 2 L N words at ct + g * bc + k * tc, acc (g) 2 L N words at acc + g * ba
-static void plain_sum_check(Context &c, const u64 *plain, const u64 *ct, const u64 *acc, size_t cms, size_t terms, size_t batch,
-                            size_t tp, size_t bp, size_t tc, size_t bc, size_t ba) {
-    if (terms == 0) throw std::invalid_argument("terms must be at least 1");
-    if (terms > 0xffffffffull) throw std::invalid_argument("terms out of range");
-    if (cms == 0 || cms > c.rows) throw std::invalid_argument("coeff_mod_size out of range");
-    if (batch > 65535) throw std::invalid_argument("batch out of range");
-    if ((tp | bp | tc | bc | ba) & 1) throw std::invalid_argument("strides must be even (16-byte loads)");
-    if ((reinterpret_cast<uintptr_t>(plain) | reinterpret_cast<uintptr_t>(ct) | reinterpret_cast<uintptr_t>(acc)) & 15)
-        throw std::invalid_argument("buffers must be 16-byte aligned");
-    if (terms > 1 && tp < cms * c.n) throw std::invalid_argument("plain term stride below L * N: the terms of plain overlap");
-    if (terms > 1 && tc < 2 * cms * c.n) throw std::invalid_argument("ct term stride below 2 * L * N: the terms of ct overlap");
+// The views of both entries: plaintext (g, k) is L N words at plain + g * bp + k * tp (sum_poly), ciphertext (g, k) 2 L N words at
+// ct + g * bc + k * tc (sum_ct), acc (g) 2 L N words at acc + g * ba (sum_acc; absent when acc is null).
+// An output may not touch a plaintext, a ciphertext or an addend (handed over as absent where out IS acc in acc's own layout, which
+// the kernel allows)
+static void plain_sum_check_output(const char *name, const u64 *out, size_t out_words, const SumOperand &plain, const SumOperand &ct,
+                                   const SumOperand &acc, size_t terms, size_t batch) {
+    sum_check_output(name, out, out_words,
+                     {{plain, "a plaintext operand"},
+                      {ct, "an operand ciphertext"},
+                      {acc, "acc (other than res == acc with a stride of 2 * L * N)"}},
+                     terms, batch);
 }
-
-// an output may not touch a plaintext, a ciphertext or an addend; `inplace`: out IS acc (same layout), which the kernel allows
-static void plain_sum_check_output(Context &c, const char *name, const u64 *out, size_t out_words, const u64 *plain, const u64 *ct,
-                                   const u64 *acc, bool inplace, size_t cms, size_t terms, size_t batch, size_t tp, size_t bp,
-                                   size_t tc, size_t bc, size_t ba) {
-    if (reinterpret_cast<uintptr_t>(out) & 15) throw std::invalid_argument("buffers must be 16-byte aligned");
-    if (batch == 0) return;
-    const size_t ln = cms * c.n;
-    if (touches_operand(out, out_words, plain, terms, batch, tp, bp, ln))
-        throw std::invalid_argument(std::string(name) + " must not overlap a plaintext operand");
-    if (touches_operand(out, out_words, ct, terms, batch, tc, bc, 2 * ln))
-        throw std::invalid_argument(std::string(name) + " must not overlap an operand ciphertext");
-    if (acc && !inplace && touches_operand(out, out_words, acc, 1, batch, 0, ba, 2 * ln))
-        throw std::invalid_argument(std::string(name) + " must not overlap acc (other than res == acc with a stride of 2 * L * N)");
-}
-
-// strict mode: every distinct buffer of the three operands, in pieces of at most 65535 polynomials per count (grid z); never skipped
-static void plain_sum_strict(Context &c, const u64 *plain, const u64 *ct, const u64 *acc, size_t cms, size_t terms, size_t batch,
-                             size_t tp, size_t bp, size_t tc, size_t bc, size_t ba, hipStream_t s) {
-    if (!strict_mode()) return;
-    for (size_t g = 0; g < (bp ? batch : 1); g++)
-        for (size_t k0 = 0; k0 < terms; k0 += 65535)
-            strict_operand(c, "multiply_plain_sum plain", plain + g * bp + k0 * tp, rows_plain(0, cms),
-                           (uint32_t)std::min<size_t>(65535, terms - k0), tp, s);
-    sum_strict(c, "multiply_plain_sum ct", ct, cms, terms, batch, tc, bc, s);
-    if (acc) sum_strict(c, "multiply_plain_sum acc", acc, cms, 1, batch, 0, ba, s);
+// strict mode: every distinct buffer of the three operands; never skipped
+static void plain_sum_strict(Context &c, const SumOperand &plain, const SumOperand &ct, const SumOperand &acc, size_t cms, size_t terms,
+                             size_t batch, hipStream_t s) {
+    strict_sum_operand(c, "multiply_plain_sum plain", plain, cms, terms, batch, false, s);
+    strict_sum_operand(c, "multiply_plain_sum ct", ct, cms, terms, batch, false, s);
+    strict_sum_operand(c, "multiply_plain_sum acc", acc, cms, 1, batch, false, s);
 }
 
 constexpr size_t kPlainSumChunk = 8;   // groups per set of launches of the rescale entry, as kInnerProductChunk
@@ -647,23 +633,21 @@ int pha_tensor_prod_2x2_sum_batched(pha_context_t ctx, const uint64_t *op1, cons
     PHA_CTX_BEGIN(ctx)
     need(op1); need(op2); need(res01); need(res2);
     Context &c = ctx->c;
-    sum_check(c, op1, op2, cms, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride);
     const size_t ln = cms * c.n;
-    sum_check_output(c, "res01", res01, batch * 2 * ln, op1, op2, cms, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride,
-                     op2_batch_stride);
-    sum_check_output(c, "res2", res2, batch * ln, op1, op2, cms, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride,
-                     op2_batch_stride);
+    const SumOperand a = sum_ct(op1, op1_term_stride, op1_batch_stride, ln, kSumCrowded),
+                     b = sum_ct(op2, op2_term_stride, op2_batch_stride, ln, kSumCrowded);
+    sum_check(c, {a, b}, cms, terms, batch);
+    sum_check_output("res01", res01, batch * 2 * ln, {{a, "an operand ciphertext"}, {b, "an operand ciphertext"}}, terms, batch);
+    sum_check_output("res2", res2, batch * ln, {{a, "an operand ciphertext"}, {b, "an operand ciphertext"}}, terms, batch);
     if (batch == 0) return 0;
-    sum_strict(c, "tensor_prod_2x2_sum operand1", op1, cms, terms, batch, op1_term_stride, op1_batch_stride, as_stream(stream));
-    sum_strict(c, "tensor_prod_2x2_sum operand2", op2, cms, terms, batch, op2_term_stride, op2_batch_stride, as_stream(stream));
-    launch_tensor_sum(c, op1, op2, res01, res2, cms, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride,
-                      as_stream(stream));
+    strict_sum_operand(c, "tensor_prod_2x2_sum operand1", a, cms, terms, batch, false, as_stream(stream));
+    strict_sum_operand(c, "tensor_prod_2x2_sum operand2", b, cms, terms, batch, false, as_stream(stream));
+    launch_tensor_sum(c, a, b, res01, res2, cms, terms, batch, as_stream(stream));
     PHA_API_END
 }
 
-// The two whole operations: the summed tensor product of a chunk of groups, then ONE batched key switch for the chunk (the key
-// switch is linear: relinearizing the sum is relinearizing every product, at 1 / terms of the cost).  The working buffers are this
-// call's own (scratch_outer: the key switch uses the stream's arena) and sized by the chunk; nothing is copied.
+// The three whole operations on encrypted operands: each checks what is its own (scheme, level, special modulus, plain modulus) and
+// names its form; inner_product() above does the rest.
 int pha_inner_product_relin_rescale_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *op1, const uint64_t *op2, size_t terms,
                                             size_t batch, size_t op1_term_stride, size_t op1_batch_stride, size_t op2_term_stride,
                                             size_t op2_batch_stride, const uint64_t *const *rlk, uint64_t *dst, size_t chunk,
@@ -674,23 +658,9 @@ int pha_inner_product_relin_rescale_batched(pha_context_t ctx, size_t size_Ql, c
     if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("size_Ql out of range");
     if (c.size_p == 0) throw std::invalid_argument("context has no special modulus");
     if (size_Ql < 2) throw std::invalid_argument("cannot rescale the last remaining modulus");
-    sum_check(c, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride);
-    const size_t ql_n = size_Ql * c.n, out_n = (size_Ql - 1) * c.n;
-    sum_check_output(c, "dst", dst, batch * 2 * out_n, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride,
-                     op2_batch_stride);
-    if (batch == 0) return 0;
-    hipStream_t s = as_stream(stream);
-    sum_strict(c, "tensor_prod_2x2_sum operand1", op1, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, s);
-    sum_strict(c, "tensor_prod_2x2_sum operand2", op2, size_Ql, terms, batch, op2_term_stride, op2_batch_stride, s);
-    const size_t C = inner_product_chunk(c, size_Ql, chunk, batch);
-    u64 *s01 = c.scratch_outer(stream, C * 3 * ql_n), *s2 = s01 + C * 2 * ql_n;   // the sums of a chunk: [C][2][Ql][N] | [C][Ql][N]
-    for (size_t b0 = 0; b0 < batch; b0 += C) {
-        const size_t B = std::min(C, batch - b0);
-        launch_tensor_sum(c, op1 + b0 * op1_batch_stride, op2 + b0 * op2_batch_stride, s01, s2, size_Ql, terms, B, op1_term_stride,
-                          op1_batch_stride, op2_term_stride, op2_batch_stride, s);
-        const int rc = pha_keyswitch_rescale_batched(ctx, size_Ql, s01, s2, B, rlk, dst + b0 * 2 * out_n, stream);
-        if (rc != 0) return rc;   // (its message is the last error)
-    }
+    const size_t ln = size_Ql * c.n;
+    return inner_product(ctx, InnerProductClose::Rescale, size_Ql, sum_ct(op1, op1_term_stride, op1_batch_stride, ln, kSumCrowded),
+                         sum_ct(op2, op2_term_stride, op2_batch_stride, ln, kSumCrowded), terms, batch, rlk, 0, dst, chunk, stream);
     PHA_API_END
 }
 
@@ -708,23 +678,9 @@ int pha_inner_product_relin_batched(pha_context_t ctx, size_t size_Ql, const uin
     if (c.size_p == 0) throw std::invalid_argument("context has no special modulus");
     if (scheme == PHA_SCHEME_BGV && !c.tool((uint32_t)size_Ql).bgv_ready)
         throw std::invalid_argument("bgv needs a plain modulus (pha_context_set_plain_modulus)");
-    sum_check(c, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride);
-    const size_t ql_n = size_Ql * c.n;
-    sum_check_output(c, "dst", dst, batch * 2 * ql_n, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride,
-                     op2_batch_stride);
-    if (batch == 0) return 0;
-    hipStream_t s = as_stream(stream);
-    sum_strict(c, "tensor_prod_2x2_sum operand1", op1, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, s);
-    sum_strict(c, "tensor_prod_2x2_sum operand2", op2, size_Ql, terms, batch, op2_term_stride, op2_batch_stride, s);
-    const size_t C = inner_product_chunk(c, size_Ql, chunk, batch);
-    u64 *s2 = c.scratch_outer(stream, C * ql_n);   // c2 of a chunk's sums; (c0, c1) go straight into dst, which the key switch completes in place
-    for (size_t b0 = 0; b0 < batch; b0 += C) {
-        const size_t B = std::min(C, batch - b0);
-        launch_tensor_sum(c, op1 + b0 * op1_batch_stride, op2 + b0 * op2_batch_stride, dst + b0 * 2 * ql_n, s2, size_Ql, terms, B,
-                          op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride, s);
-        const int rc = pha_keyswitch_inplace_batched(ctx, size_Ql, dst + b0 * 2 * ql_n, s2, B, rlk, scheme, stream);
-        if (rc != 0) return rc;   // (its message is the last error)
-    }
+    const size_t ln = size_Ql * c.n;
+    return inner_product(ctx, InnerProductClose::InPlace, size_Ql, sum_ct(op1, op1_term_stride, op1_batch_stride, ln, kSumCrowded),
+                         sum_ct(op2, op2_term_stride, op2_batch_stride, ln, kSumCrowded), terms, batch, rlk, scheme, dst, chunk, stream);
     PHA_API_END
 }
 // bgv: the sums of a chunk, then ONE fused key switch + mod_switch_to_next for the chunk (pha_keyswitch_mod_switch_batched)
@@ -739,23 +695,9 @@ int pha_inner_product_relin_mod_switch_batched(pha_context_t ctx, size_t size_Ql
     if (c.size_p == 0) throw std::invalid_argument("context has no special modulus");
     if (size_Ql < 2) throw std::invalid_argument("cannot switch down the last remaining modulus");
     if (!c.tool((uint32_t)size_Ql).bgv_ready) throw std::invalid_argument("bgv needs a plain modulus (pha_context_set_plain_modulus)");
-    sum_check(c, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride, op2_batch_stride);
-    const size_t ql_n = size_Ql * c.n, out_n = (size_Ql - 1) * c.n;
-    sum_check_output(c, "dst", dst, batch * 2 * out_n, op1, op2, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, op2_term_stride,
-                     op2_batch_stride);
-    if (batch == 0) return 0;
-    hipStream_t s = as_stream(stream);
-    sum_strict(c, "tensor_prod_2x2_sum operand1", op1, size_Ql, terms, batch, op1_term_stride, op1_batch_stride, s);
-    sum_strict(c, "tensor_prod_2x2_sum operand2", op2, size_Ql, terms, batch, op2_term_stride, op2_batch_stride, s);
-    const size_t C = inner_product_chunk(c, size_Ql, chunk, batch);
-    u64 *s01 = c.scratch_outer(stream, C * 3 * ql_n), *s2 = s01 + C * 2 * ql_n;   // the sums of a chunk: [C][2][Ql][N] | [C][Ql][N]
-    for (size_t b0 = 0; b0 < batch; b0 += C) {
-        const size_t B = std::min(C, batch - b0);
-        launch_tensor_sum(c, op1 + b0 * op1_batch_stride, op2 + b0 * op2_batch_stride, s01, s2, size_Ql, terms, B, op1_term_stride,
-                          op1_batch_stride, op2_term_stride, op2_batch_stride, s);
-        const int rc = pha_keyswitch_mod_switch_batched(ctx, size_Ql, s01, s2, B, rlk, dst + b0 * 2 * out_n, stream);
-        if (rc != 0) return rc;   // (its message is the last error)
-    }
+    const size_t ln = size_Ql * c.n;
+    return inner_product(ctx, InnerProductClose::ModSwitch, size_Ql, sum_ct(op1, op1_term_stride, op1_batch_stride, ln, kSumCrowded),
+                         sum_ct(op2, op2_term_stride, op2_batch_stride, ln, kSumCrowded), terms, batch, rlk, 0, dst, chunk, stream);
     PHA_API_END
 }
 
@@ -765,18 +707,16 @@ int pha_multiply_plain_sum_batched(pha_context_t ctx, const uint64_t *plain, con
     PHA_CTX_BEGIN(ctx)
     need(plain); need(ct); need(res);
     Context &c = ctx->c;
-    plain_sum_check(c, plain, ct, acc, cms, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride,
-                    acc_batch_stride);
     const size_t ln = cms * c.n;
+    const SumOperand pl = sum_poly(plain, plain_term_stride, plain_batch_stride, ln, kPlainCrowded),
+                     cts = sum_ct(ct, ct_term_stride, ct_batch_stride, ln, kCtCrowded), addend = sum_acc(acc, acc_batch_stride, ln);
+    sum_check(c, {pl, cts, addend}, cms, terms, batch);
     const bool inplace = acc && res == acc && acc_batch_stride == 2 * ln;
-    plain_sum_check_output(c, "res", res, batch * 2 * ln, plain, ct, acc, inplace, cms, terms, batch, plain_term_stride,
-                           plain_batch_stride, ct_term_stride, ct_batch_stride, acc_batch_stride);
+    plain_sum_check_output("res", res, batch * 2 * ln, pl, cts, inplace ? SumOperand{} : addend, terms, batch);
     if (batch == 0) return 0;
     hipStream_t s = as_stream(stream);
-    plain_sum_strict(c, plain, ct, acc, cms, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride,
-                     acc_batch_stride, s);
-    launch_plain_sum(c, plain, ct, acc, res, cms, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride,
-                     acc_batch_stride, s);
+    plain_sum_strict(c, pl, cts, addend, cms, terms, batch, s);
+    launch_plain_sum(c, pl, cts, addend, res, cms, terms, batch, s);
     PHA_API_END
 }
 
@@ -797,21 +737,19 @@ int pha_plain_inner_product_rescale_batched(pha_context_t ctx, size_t size_Ql, c
     if (size_Ql < 2) throw std::invalid_argument("cannot rescale the last remaining modulus");
     if (scheme == PHA_SCHEME_BGV && !c.tool((uint32_t)size_Ql).bgv_ready)
         throw std::invalid_argument("bgv needs a plain modulus (pha_context_set_plain_modulus)");
-    plain_sum_check(c, plain, ct, acc, size_Ql, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride,
-                    acc_batch_stride);
     const size_t ql_n = size_Ql * c.n, out_n = (size_Ql - 1) * c.n;
-    plain_sum_check_output(c, "dst", dst, batch * 2 * out_n, plain, ct, acc, false, size_Ql, terms, batch, plain_term_stride,
-                           plain_batch_stride, ct_term_stride, ct_batch_stride, acc_batch_stride);
+    const SumOperand pl = sum_poly(plain, plain_term_stride, plain_batch_stride, ql_n, kPlainCrowded),
+                     cts = sum_ct(ct, ct_term_stride, ct_batch_stride, ql_n, kCtCrowded), addend = sum_acc(acc, acc_batch_stride, ql_n);
+    sum_check(c, {pl, cts, addend}, size_Ql, terms, batch);
+    plain_sum_check_output("dst", dst, batch * 2 * out_n, pl, cts, addend, terms, batch);
     if (batch == 0) return 0;
     hipStream_t s = as_stream(stream);
-    plain_sum_strict(c, plain, ct, acc, size_Ql, terms, batch, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride,
-                     acc_batch_stride, s);
+    plain_sum_strict(c, pl, cts, addend, size_Ql, terms, batch, s);
     const size_t C = std::min<size_t>(std::min(chunk ? chunk : kPlainSumChunk, batch), 32767);   // 2 C polynomials per level drop
     u64 *work = c.scratch_outer(stream, C * 2 * ql_n);   // the sums of a chunk: [C][2][Ql][N]
     for (size_t b0 = 0; b0 < batch; b0 += C) {
         const size_t B = std::min(C, batch - b0);
-        launch_plain_sum(c, plain + b0 * plain_batch_stride, ct + b0 * ct_batch_stride, acc ? acc + b0 * acc_batch_stride : nullptr, work,
-                         size_Ql, terms, B, plain_term_stride, plain_batch_stride, ct_term_stride, ct_batch_stride, acc_batch_stride, s);
+        launch_plain_sum(c, pl.advanced(b0, 0), cts.advanced(b0, 0), addend.advanced(b0, 0), work, size_Ql, terms, B, s);
         const int rc = scheme == PHA_SCHEME_CKKS
                            ? pha_divide_and_round_q_last_ntt(ctx, size_Ql, work, 2 * B, dst + b0 * 2 * out_n, stream)
                            : pha_mod_t_and_divide_q_last_ntt(ctx, size_Ql, work, 2 * B, dst + b0 * 2 * out_n, stream);

@@ -1255,8 +1255,6 @@ void check_level(Context &c, size_t size_Ql, bool need_p) {
     if (need_p && c.size_p == 0) throw std::invalid_argument("context has no special modulus");
 }
 
-bool overlaps(const u64 *a, size_t na, const u64 *b, size_t nb) { return a < b + nb && b < a + na; }
-
 }  // namespace pha
 
 using namespace pha;

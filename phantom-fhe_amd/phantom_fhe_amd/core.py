@@ -16,6 +16,11 @@ import torch
 from . import lib as _lib
 
 
+# which operands a summed-product entry takes (PhantomContext._strides): two ciphertexts per term (op1 dense only), or a plaintext
+# [L][N] / a raw bfv plaintext [N] and a ciphertext per term, plus acc
+_CT_CT, _PLAIN_CT, _RAW_CT = 0, 1, 2
+
+
 class scheme_type(IntEnum):  # include/host/encryptionparams.h:19-27
     none = 0
     bfv = 1
@@ -362,29 +367,45 @@ class PhantomContext:
         _lib.check(self._L.pha_tensor_prod_2x2_batched(self._h, _ptr(op1), _ptr(op2), _ptr(res01), _ptr(res2), cms,
                                                        batch, _stream()))
 
-    def _sum_strides(self, op1, op2, cms, terms, batch, strides):
-        """(op1 term, op1 batch, op2 term, op2 batch) strides in 64-bit words.  None: the dense layout, op1 [batch][terms][2][L][N]
-        and op2 the same or, with one dimension fewer, [terms][2][L][N] shared by all groups (batch stride 0)."""
+    def _strides(self, a, b, cms, terms, batch, strides, kind):
+        """The strides of a summed-product entry in 64-bit words: (a term, a batch, b term, b batch) and, for the plaintext kinds,
+        acc's batch stride.  strides None: each operand is dense ([batch][terms] + its element shape) or, with one dimension fewer
+        ([terms] + ...), shared by all groups (batch stride 0; not op1 of _CT_CT).  Explicit strides pass through: the operands
+        may then be views into larger buffers."""
         if strides is not None:
-            t1, b1, t2, b2 = (int(v) for v in strides)
-            return t1, b1, t2, b2
-        ct = 2 * cms * self.n
-        dense = (batch, terms, 2, cms, self.n)
-        if op1 is None or op2 is None:          # the library refuses the null pointer
-            return ct, terms * ct, ct, terms * ct
-        if tuple(op1.shape) != dense:
-            raise ValueError("op1 must be [batch][terms][2][L][N] (or pass strides)")
-        if tuple(op2.shape) == dense:
-            return ct, terms * ct, ct, terms * ct
-        if tuple(op2.shape) == dense[1:]:
-            return ct, terms * ct, ct, 0
-        raise ValueError("op2 must be [batch][terms][2][L][N] or, shared by all groups, [terms][2][L][N] (or pass strides)")
+            if kind == _CT_CT:
+                t1, b1, t2, b2 = (int(v) for v in strides)
+                return t1, b1, t2, b2
+            tp, bp, tc, bc, ba = (int(v) for v in strides)
+            return tp, bp, tc, bc, ba
+        n = self.n
+        cw = 2 * cms * n
+        aw = cw if kind == _CT_CT else n if kind == _RAW_CT else cms * n
+        ab, bb = terms * aw, terms * cw
+        if a is not None and b is not None:     # (the library refuses the null pointer)
+            dense_b = (batch, terms, 2, cms, n)
+            dense_a = dense_b if kind == _CT_CT else (batch, terms, n) if kind == _RAW_CT else (batch, terms, cms, n)
+            shape = tuple(a.shape)
+            if shape != dense_a:
+                if kind == _CT_CT:
+                    raise ValueError("op1 must be [batch][terms][2][L][N] (or pass strides)")
+                if shape != dense_a[1:]:
+                    dims = "[N]" if kind == _RAW_CT else "[L][N]"
+                    raise ValueError("plain must be [batch][terms]%s or, shared by all groups, [terms]%s (or pass strides)" % (dims, dims))
+                ab = 0
+            shape = tuple(b.shape)
+            if shape != dense_b:
+                if shape != dense_b[1:]:
+                    raise ValueError("%s must be [batch][terms][2][L][N] or, shared by all groups, [terms][2][L][N] (or pass strides)" %
+                                     ("op2" if kind == _CT_CT else "ct"))
+                bb = 0
+        return (aw, ab, cw, bb) if kind == _CT_CT else (aw, ab, cw, bb, cw)
 
     def tensor_prod_2x2_sum_batched(self, op1, op2, res01, res2, cms, terms, batch, strides=None):
         """Extension: for every group g < batch, (res01[g], res2[g]) = sum over k < terms of tensor_prod_2x2(op1[g][k], op2[g][k]) in
         one launch, every word the canonical residue of the sum; res01 [batch][2][L][N], res2 [batch][L][N].  strides: see
-        _sum_strides (with explicit strides op1 / op2 may be views into larger buffers)."""
-        t1, b1, t2, b2 = self._sum_strides(op1, op2, cms, terms, batch, strides)
+        _strides (with explicit strides op1 / op2 may be views into larger buffers)."""
+        t1, b1, t2, b2 = self._strides(op1, op2, cms, terms, batch, strides, _CT_CT)
         _lib.check(self._L.pha_tensor_prod_2x2_sum_batched(self._h, _ptr(op1), _ptr(op2), _ptr(res01), _ptr(res2), cms, terms, batch,
                                                            t1, b1, t2, b2, _stream()))
 
@@ -392,53 +413,28 @@ class PhantomContext:
         """Extension (ckks): dst [batch][2][Ql-1][N] = rescale(relinearize(sum over k of op1[g][k] * op2[g][k])) with ONE key switch per
         sum; bit-identical to tensor_prod_2x2_sum_batched followed by keyswitch_rescale_batched.  `chunk` groups per set of launches
         (0: the library's default)."""
-        t1, b1, t2, b2 = self._sum_strides(op1, op2, size_Ql, terms, batch, strides)
+        t1, b1, t2, b2 = self._strides(op1, op2, size_Ql, terms, batch, strides, _CT_CT)
         _lib.check(self._L.pha_inner_product_relin_rescale_batched(self._h, size_Ql, _ptr(op1), _ptr(op2), terms, batch, t1, b1, t2, b2,
                                                                    _ptr(rlk_ptrs), _ptr(dst), chunk, _stream()))
 
     def inner_product_relin_batched(self, size_Ql, op1, op2, terms, batch, rlk_ptrs, scheme, dst, strides=None, chunk=0):
         """Extension (ckks / bgv), no rescale: dst [batch][2][Ql][N] = relinearize(sum over k of op1[g][k] * op2[g][k])."""
-        t1, b1, t2, b2 = self._sum_strides(op1, op2, size_Ql, terms, batch, strides)
+        t1, b1, t2, b2 = self._strides(op1, op2, size_Ql, terms, batch, strides, _CT_CT)
         _lib.check(self._L.pha_inner_product_relin_batched(self._h, size_Ql, _ptr(op1), _ptr(op2), terms, batch, t1, b1, t2, b2,
                                                            _ptr(rlk_ptrs), int(scheme), _ptr(dst), chunk, _stream()))
 
     def inner_product_relin_mod_switch_batched(self, size_Ql, op1, op2, terms, batch, rlk_ptrs, dst, strides=None, chunk=0):
         """Extension (bgv): dst [batch][2][Ql-1][N] = mod_switch(relinearize(sum over k of op1[g][k] * op2[g][k])) with ONE key switch
         per sum; bit-identical to tensor_prod_2x2_sum_batched followed by keyswitch_mod_switch_batched."""
-        t1, b1, t2, b2 = self._sum_strides(op1, op2, size_Ql, terms, batch, strides)
+        t1, b1, t2, b2 = self._strides(op1, op2, size_Ql, terms, batch, strides, _CT_CT)
         _lib.check(self._L.pha_inner_product_relin_mod_switch_batched(self._h, size_Ql, _ptr(op1), _ptr(op2), terms, batch, t1, b1, t2,
                                                                       b2, _ptr(rlk_ptrs), _ptr(dst), chunk, _stream()))
-
-    def _plain_sum_strides(self, plain, ct, cms, terms, batch, strides):
-        """(plain term, plain batch, ct term, ct batch, acc batch) strides in 64-bit words.  None: the dense layout, plain
-        [batch][terms][L][N], ct [batch][terms][2][L][N] and acc [batch][2][L][N]; plain or ct with one dimension fewer
-        ([terms]...) is shared by all groups (batch stride 0)."""
-        if strides is not None:
-            tp, bp, tc, bc, ba = (int(v) for v in strides)
-            return tp, bp, tc, bc, ba
-        ln = cms * self.n
-        if plain is None or ct is None:         # the library refuses the null pointer
-            return ln, terms * ln, 2 * ln, terms * 2 * ln, 2 * ln
-        dense_p, dense_c = (batch, terms, cms, self.n), (batch, terms, 2, cms, self.n)
-        if tuple(plain.shape) == dense_p:
-            bp = terms * ln
-        elif tuple(plain.shape) == dense_p[1:]:
-            bp = 0
-        else:
-            raise ValueError("plain must be [batch][terms][L][N] or, shared by all groups, [terms][L][N] (or pass strides)")
-        if tuple(ct.shape) == dense_c:
-            bc = terms * 2 * ln
-        elif tuple(ct.shape) == dense_c[1:]:
-            bc = 0
-        else:
-            raise ValueError("ct must be [batch][terms][2][L][N] or, shared by all groups, [terms][2][L][N] (or pass strides)")
-        return ln, bp, 2 * ln, bc, 2 * ln
 
     def multiply_plain_sum_batched(self, plain, ct, acc, res, cms, terms, batch, strides=None):
         """Extension: for every group g < batch, res[g] = acc[g] + sum over k < terms of plain[g][k] (.) ct[g][k] (both polynomials)
         in one launch, every word the canonical residue of the sum; acc may be None, res [batch][2][L][N] may be acc itself.
-        strides: see _plain_sum_strides (with explicit strides the operands may be views into larger buffers)."""
-        tp, bp, tc, bc, ba = self._plain_sum_strides(plain, ct, cms, terms, batch, strides)
+        strides: see _strides (with explicit strides the operands may be views into larger buffers)."""
+        tp, bp, tc, bc, ba = self._strides(plain, ct, cms, terms, batch, strides, _PLAIN_CT)
         _lib.check(self._L.pha_multiply_plain_sum_batched(self._h, _ptr(plain), _ptr(ct), _ptr(acc), _ptr(res), cms, terms, batch,
                                                           tp, bp, tc, bc, ba, _stream()))
 
@@ -446,7 +442,7 @@ class PhantomContext:
         """Extension (ckks / bgv): dst [batch][2][Ql-1][N] = the level drop (rescale / mod switch) of the sums above, ONE per sum;
         bit-identical to multiply_plain_sum_batched followed by divide_and_round_q_last_ntt / mod_t_and_divide_q_last_ntt over
         2 * batch polynomials.  `chunk` groups per set of launches (0: the library's default)."""
-        tp, bp, tc, bc, ba = self._plain_sum_strides(plain, ct, size_Ql, terms, batch, strides)
+        tp, bp, tc, bc, ba = self._strides(plain, ct, size_Ql, terms, batch, strides, _PLAIN_CT)
         _lib.check(self._L.pha_plain_inner_product_rescale_batched(self._h, size_Ql, _ptr(plain), _ptr(ct), _ptr(acc), terms, batch,
                                                                    tp, bp, tc, bc, ba, int(scheme), _ptr(dst), chunk, _stream()))
 
@@ -457,40 +453,13 @@ class PhantomContext:
         ps, os_ = (int(v) for v in strides) if strides is not None else (self.n, size_Ql * self.n)
         _lib.check(self._L.pha_bfv_lift_plain_batched(self._h, size_Ql, _ptr(plain), count, ps, _ptr(out), os_, _stream()))
 
-    def _bfv_plain_sum_strides(self, plain, ct, size_Ql, terms, batch, strides, raw):
-        """As _plain_sum_strides; raw: plain (g, k) is [N] (a bfv plaintext), so dense [batch][terms][N] or, shared by all
-        groups, [terms][N]."""
-        if strides is not None:
-            tp, bp, tc, bc, ba = (int(v) for v in strides)
-            return tp, bp, tc, bc, ba
-        ln = size_Ql * self.n
-        one = (self.n,) if raw else (size_Ql, self.n)
-        pn = self.n if raw else ln
-        if plain is None or ct is None:         # the library refuses the null pointer
-            return pn, terms * pn, 2 * ln, terms * 2 * ln, 2 * ln
-        dense_c = (batch, terms, 2, size_Ql, self.n)
-        if tuple(plain.shape) == (batch, terms) + one:
-            bp = terms * pn
-        elif tuple(plain.shape) == (terms,) + one:
-            bp = 0
-        else:
-            raise ValueError("plain must be [batch][terms]%s or, shared by all groups, [terms]%s (or pass strides)"
-                             % (("[N]", "[N]") if raw else ("[L][N]", "[L][N]")))
-        if tuple(ct.shape) == dense_c:
-            bc = terms * 2 * ln
-        elif tuple(ct.shape) == dense_c[1:]:
-            bc = 0
-        else:
-            raise ValueError("ct must be [batch][terms][2][L][N] or, shared by all groups, [terms][2][L][N] (or pass strides)")
-        return pn, bp, 2 * ln, bc, 2 * ln
-
     def bfv_multiply_plain_sum_batched(self, size_Ql, plain_ntt, ct, acc, res, terms, batch, strides=None, chunk=0, slab=0):
         """Extension (bfv): for every group g < batch, res[g] = acc[g] + sum over k < terms of plain[g][k] * ct[g][k] in the ring; ct,
         acc (may be None) and res [batch][2][L][N] in coefficient form, plain (g, k) [L][N] as bfv_lift_plain_batched writes it.
         One forward transform per term, one inverse per sum; word for word the loop of bfv_multiply_plain and add_rns_poly.
-        strides: see _plain_sum_strides; `chunk` groups per inverse transform and `slab` terms per sum launch (0: the library's
+        strides: see _strides; `chunk` groups per inverse transform and `slab` terms per sum launch (0: the library's
         defaults) size the work buffer and change no bit."""
-        tp, bp, tc, bc, ba = self._bfv_plain_sum_strides(plain_ntt, ct, size_Ql, terms, batch, strides, False)
+        tp, bp, tc, bc, ba = self._strides(plain_ntt, ct, size_Ql, terms, batch, strides, _PLAIN_CT)
         _lib.check(self._L.pha_bfv_multiply_plain_sum_batched(self._h, size_Ql, _ptr(plain_ntt), _ptr(ct), _ptr(acc), _ptr(res), terms,
                                                               batch, tp, bp, tc, bc, ba, chunk, slab, _stream()))
 
@@ -498,7 +467,7 @@ class PhantomContext:
         """Extension (bfv): bfv_multiply_plain_sum_batched on RAW plaintexts, plain (g, k) = [N] words below t (what a bfv
         PhantomPlaintext holds), lifted and transformed per slab; bit-identical to bfv_lift_plain_batched followed by
         bfv_multiply_plain_sum_batched."""
-        tp, bp, tc, bc, ba = self._bfv_plain_sum_strides(plain, ct, size_Ql, terms, batch, strides, True)
+        tp, bp, tc, bc, ba = self._strides(plain, ct, size_Ql, terms, batch, strides, _RAW_CT)
         _lib.check(self._L.pha_bfv_plain_inner_product_batched(self._h, size_Ql, _ptr(plain), _ptr(ct), _ptr(acc), _ptr(res), terms,
                                                                batch, tp, bp, tc, bc, ba, chunk, slab, _stream()))
 

@@ -480,6 +480,81 @@ def test_refusals_leave_everything_untouched(gpu):
     _release()
 
 
+def _refused_with(fn, text, *args, **kw):
+    with pytest.raises(ValueError) as e:
+        fn(*args, **kw)
+    assert str(e.value) == text, f"refused with {str(e.value)!r}, not with {text!r}"
+
+
+def test_every_refusal_and_their_order(gpu):
+    """The refusals of the three entries that test_refusals_leave_everything_untouched does not reach, the whole message compared,
+    and for several defects in one call the one that is reported: the level, the term count, odd strides, alignment (of res too),
+    overlapping terms of plain, of ct, and then what res lies on (plain, ct, acc).  These two entries bound neither the batch nor a
+    limb count of their own.  Nothing is launched."""
+    import torch
+    import phantom_fhe_amd as P
+    name = "hyb12_a2"
+    _, ctx, n, primes, ql = _setup(name, gpu)
+    batch, terms = 2, 3
+    ln = ql * n
+    rng = rng_for(11650)
+    m = _plains(rng, (batch, terms), n)
+    dm = P.to_device(m, gpu)
+    dp = _lifted(P, ctx, ql, n, m, gpu)
+    dc = P.to_device(_cts(rng, primes, (batch, terms, 2), n), gpu)
+    da = P.to_device(_cts(rng, primes, (batch, 2), n), gpu)
+    keep = [x.clone() for x in (dm, dp, dc, da)]
+    res, lifted = _poisoned((batch, 2, ql, n), gpu), _poisoned((batch * terms, ql, n), gpu)
+    even, aligned = "strides must be even (16-byte loads)", "buffers must be 16-byte aligned"
+    crowded_c = "ct term stride below 2 * L * N: the terms of ct overlap"
+    offc, offa, off_res, words = dc.view(-1)[1:], da.view(-1)[1:], res.view(-1)[1:], res.numel()
+    cases = ((ctx.bfv_multiply_plain_sum_batched, dp, ln, "plain term stride below L * N: the terms of plain overlap"),
+             (ctx.bfv_plain_inner_product_batched, dm, n, "plain term stride below N: the terms of plain overlap"))
+    for fn, pl, pn, crowded_p in cases:
+        st = (pn, terms * pn, 2 * ln, terms * 2 * ln, 2 * ln)
+        offp = pl.view(-1)[1:]                                     # 8 bytes past a 16-byte boundary
+        _refused_with(fn, "terms out of range", ql, pl, dc, da, res, 1 << 32, batch, strides=st)
+        for args in ((offp, dc, da, res), (pl, offc, da, res), (pl, dc, offa, res), (pl, dc, da, off_res), (pl, dc, None, off_res)):
+            _refused_with(fn, aligned, ql, *args, terms, batch, strides=st)
+        _refused_with(fn, crowded_p, ql, pl, dc, da, res, terms, batch, strides=(pn - 2,) + st[1:])
+        _refused_with(fn, crowded_c, ql, pl, dc, da, res, terms, batch, strides=st[:2] + (2 * ln - 2,) + st[3:])
+        _refused_with(fn, even, ql, pl, dc, None, res, terms, batch, strides=st[:4] + (2 * ln + 1,))   # acc's stride although there is no acc
+        _refused_with(fn, "res must not overlap an operand ciphertext", ql, pl, dc, da, dc.view(-1)[dc.numel() - words:], terms, batch, strides=st)
+        _refused_with(fn, "res must not overlap acc", ql, pl, dc, da, da, terms, batch, strides=st)
+        # every stride and alignment defect at once, then with the winner taken away each time
+        _refused_with(fn, even, ql, offp, offc, offa, off_res, terms, batch, strides=(pn - 1, 1, 2 * ln - 1, 3, 5))
+        _refused_with(fn, aligned, ql, offp, offc, offa, off_res, terms, batch, strides=(pn - 2, 0, 2 * ln - 2, 2, 4))
+        _refused_with(fn, aligned, ql, pl, dc, da, off_res, terms, batch, strides=(pn - 2, 0, 2 * ln - 2, 2, 4))   # res counts with the operands
+        _refused_with(fn, crowded_p, ql, pl, dc, da, res, terms, batch, strides=(pn - 2, 0, 2 * ln - 2, 2, 4))
+        _refused_with(fn, crowded_c, ql, pl, dc, da, res, terms, batch, strides=(pn, 0, 2 * ln - 2, 2, 4))
+        # the level and the term count come before the layout; no batch is too large to be looked at
+        _refused_with(fn, "RNSBase is invalid", 0, offp, dc, da, res, 0, batch, strides=(1, 1, 1, 1, 1))
+        _refused_with(fn, "terms must be at least 1", ql, offp, dc, da, res, 0, 65536, strides=(pn + 1,) + st[1:])
+        _refused_with(fn, "terms out of range", ql, offp, dc, da, res, 1 << 32, 65536, strides=(pn + 1,) + st[1:])
+        _refused_with(fn, even, ql, offp, dc, da, res, terms, 65536, strides=(pn + 1,) + st[1:])
+    f, h = cases[0][0], cases[1][0]
+    _refused_with(f, "res must not overlap a plaintext operand", ql, dp, dc, da, dp.view(-1)[:words], terms, batch)
+    both = torch.zeros((words + batch * terms * n,), dtype=torch.int64, device=gpu)
+    _refused_with(h, "res must not overlap a plaintext operand", ql, both[words - 2:], dc, da, both[:words], terms, batch,
+                  strides=(n, terms * n, 2 * ln, terms * 2 * ln, 2 * ln))
+    # the lift: alignment, and the order parity, alignment, out stride, overlap
+    lift, count = ctx.bfv_lift_plain_batched, batch * terms
+    offm, off_lifted = dm.view(-1)[1:], lifted.view(-1)[1:]
+    _refused_with(lift, aligned, ql, offm, count, lifted, strides=(n, ln))
+    _refused_with(lift, aligned, ql, dm, count, off_lifted, strides=(n, ln))
+    _refused_with(lift, "out stride below L * N: the lifted plaintexts overlap", ql, dm, count, lifted, strides=(n, ln - 2))
+    _refused_with(lift, "out must not overlap a plaintext operand", ql, dm, count, dm.view(-1)[:2], strides=(n, ln))
+    _refused_with(lift, even, ql, offm, count, off_lifted, strides=(n + 1, ln - 1))
+    _refused_with(lift, aligned, ql, offm, count, off_lifted, strides=(n, ln - 2))
+    _refused_with(lift, "out stride below L * N: the lifted plaintexts overlap", ql, dm, count, dm.view(-1)[:2], strides=(n, ln - 2))
+    _refused_with(lift, "RNSBase is invalid", 0, offm, count, off_lifted, strides=(n + 1, ln - 1))
+    torch.cuda.synchronize()
+    assert bool((res == POISON).all()) and bool((lifted == POISON).all()), "a refused call wrote to its output"
+    assert all(torch.equal(a, b) for a, b in zip((dm, dp, dc, da), keep)) and not bool(both.any()), "a refused call wrote to an operand"
+    del ctx
+    _release()
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # H: strict mode
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -23,7 +23,8 @@ F. (replaced by the composition in D at hyb13_a3, ckks, no rescale.)  The issue 
    key switch instead of once per sum.  Both results decrypt to the same message with slightly different noise, and their NTT-form
    words differ everywhere: in the CPU oracle at hyb13_a3 with three terms all 147456 output words of keyswitch(sum) differ from
    the sum of the key switches.  No other test was changed for this;
-G. refusals (status -1, the message, poisoned outputs untouched), and operands unchanged by successful calls;
+G. refusals (status -1, the message, poisoned outputs untouched), and operands unchanged by successful calls; every refusal of
+   the four entries with its whole message, and which one a call with several defects reports;
 H. strict mode: one word >= its modulus in term k of group g of either operand is refused with the operand named, and accepted
    with strict mode off.
 """
@@ -411,6 +412,93 @@ def test_refusals_leave_everything_untouched(gpu):
         assert not bool((out == POISON).any())
     assert torch.equal(d1, keep1) and torch.equal(d2, keep2), "a successful call wrote to an operand"
     del ctx, rlk
+    _release()
+
+
+def _refused_with(fn, text, *args, **kw):
+    with pytest.raises(ValueError) as e:
+        fn(*args, **kw)
+    assert str(e.value) == text, f"refused with {str(e.value)!r}, not with {text!r}"
+
+
+def test_every_refusal_and_their_order(gpu):
+    """The refusals of the four entries that test_refusals_leave_everything_untouched does not reach, the whole message compared, and
+    for several defects in one call the one that is reported: the term count, the batch, odd strides, alignment of the operands,
+    overlapping terms, and only then the output (its alignment, then what it lies on).  Nothing is launched."""
+    import torch
+    name = "hyb12_a2"
+    P, ctx, log_n, primes, size_p, ql = _setup(name, gpu)
+    _, bgv, *_ = _setup(name, gpu, plain_t=BGV_T)
+    n, batch, terms = 1 << log_n, 2, 3
+    ct = 2 * ql * n
+    rng = rng_for(9750)
+    keys = P.PhantomRelinKey.from_numpy(_keys(rng, primes, n, ql // size_p), gpu)
+    kp = keys.public_keys_ptr
+    d1 = P.to_device(_operands(rng, primes[:ql], batch, terms, n, blocks=False), gpu)
+    d2 = P.to_device(_operands(rng, primes[:ql], batch, terms, n, blocks=False), gpu)
+    keep1, keep2 = d1.clone(), d2.clone()
+    r2 = _poisoned((batch, ql, n), gpu)
+    dense = (ct, terms * ct, ct, terms * ct)
+    even, aligned = "strides must be even (16-byte loads)", "buffers must be 16-byte aligned"
+    crowded = "term stride below 2 * L * N: the terms of an operand overlap"
+    entries = {   # call(op1, op2, terms, batch, strides, out), the output and how the overlap refusal names it
+        "sum": (lambda a, b, t, B, st, out: ctx.tensor_prod_2x2_sum_batched(a, b, out, r2, ql, t, B, strides=st),
+                _poisoned((batch, 2, ql, n), gpu), "res01"),
+        "rescale": (lambda a, b, t, B, st, out: ctx.inner_product_relin_rescale_batched(ql, a, b, t, B, kp, out, strides=st),
+                    _poisoned((batch, 2, ql - 1, n), gpu), "dst"),
+        "relin": (lambda a, b, t, B, st, out: ctx.inner_product_relin_batched(ql, a, b, t, B, kp, O.CKKS, out, strides=st),
+                  _poisoned((batch, 2, ql, n), gpu), "dst"),
+        "mod_switch": (lambda a, b, t, B, st, out: bgv.inner_product_relin_mod_switch_batched(ql, a, b, t, B, kp, out, strides=st),
+                       _poisoned((batch, 2, ql - 1, n), gpu), "dst"),
+    }
+    off1, off2 = d1.view(-1)[1:], d2.view(-1)[1:]                     # 8 bytes past a 16-byte boundary
+    for call, out, out_name in entries.values():
+        off_out = out.view(-1)[1:]
+        _refused_with(call, "terms out of range", d1, d2, 1 << 32, batch, dense, out)
+        _refused_with(call, "batch out of range", d1, d2, terms, 65536, dense, out)
+        _refused_with(call, aligned, off1, d2, terms, batch, dense, out)
+        _refused_with(call, aligned, d1, off2, terms, batch, dense, out)
+        _refused_with(call, aligned, d1, d2, terms, batch, dense, off_out)
+        _refused_with(call, crowded, d1, d2, terms, batch, (ct - 2, terms * ct, ct, terms * ct), out)
+        _refused_with(call, crowded, d1, d2, terms, batch, (ct, terms * ct, 0, terms * ct), out)
+        _refused_with(call, out_name + " must not overlap an operand ciphertext", d1, d2, terms, batch, dense,
+                      d2.view(-1)[d2.numel() - out.numel():])
+        # every stride and alignment defect at once, then with the winner taken away each time
+        _refused_with(call, even, off1, off2, terms, batch, (ct - 1, terms * ct + 1, 1, 3), off_out)
+        _refused_with(call, aligned, off1, off2, terms, batch, (ct - 2, terms * ct, 0, 2), off_out)
+        _refused_with(call, crowded, d1, d2, terms, batch, (ct - 2, terms * ct, 0, 2), off_out)
+        _refused_with(call, aligned, d1, d2, terms, batch, dense, d1.view(-1)[1:1 + out.numel()])   # misaligned AND on operand 1
+        # the term count and the batch come before the layout
+        _refused_with(call, "terms must be at least 1", off1, d2, 0, 65536, (ct + 1, terms * ct, ct, terms * ct), out)
+        _refused_with(call, "terms out of range", off1, d2, 1 << 32, 65536, (ct + 1, terms * ct, ct, terms * ct), out)
+        _refused_with(call, "batch out of range", off1, d2, terms, 65536, (ct + 1, terms * ct, ct, terms * ct), out)
+    # res2 of the summed tensor product: misaligned, and on top of operand 1
+    f, res01 = ctx.tensor_prod_2x2_sum_batched, entries["sum"][1]
+    _refused_with(f, aligned, d1, d2, res01, r2.view(-1)[1:], ql, terms, batch, strides=dense)
+    _refused_with(f, "res2 must not overlap an operand ciphertext", d1, d2, res01, d1.view(-1)[ct:ct + batch * ql * n], ql, terms, batch, strides=dense)
+    # what the whole operations check themselves, before any of the above
+    g, h = ctx.inner_product_relin_rescale_batched, ctx.inner_product_relin_batched
+    dres, dks = entries["rescale"][1], entries["relin"][1]
+    _refused_with(h, "unsupported scheme", ql, d1, d2, terms, batch, kp, 99, dks)
+    _refused_with(h, "size_Ql out of range", 0, d1, d2, terms, batch, kp, O.CKKS, dks, strides=dense)
+    _refused_with(h, "size_Ql out of range", len(primes), d1, d2, terms, batch, kp, O.CKKS, dks, strides=dense)
+    _refused_with(g, "size_Ql out of range", 0, d1, d2, terms, batch, kp, dres, strides=dense)
+    _refused_with(g, "cannot rescale the last remaining modulus", 1, off1, d2, 0, batch, kp, dres, strides=(1, 1, 1, 1))
+    _refused_with(bgv.inner_product_relin_mod_switch_batched, "cannot switch down the last remaining modulus", 1, off1, d2, 0, batch, kp,
+                  entries["mod_switch"][1], strides=(1, 1, 1, 1))
+    _refused_with(ctx.inner_product_relin_mod_switch_batched, "bgv needs a plain modulus (pha_context_set_plain_modulus)", ql, off1, d2, 0,
+                  batch, kp, entries["mod_switch"][1], strides=(1, 1, 1, 1))
+    _refused_with(h, "bgv needs a plain modulus (pha_context_set_plain_modulus)", ql, off1, d2, 0, batch, kp, O.BGV, dks, strides=(1, 1, 1, 1))
+    log_n2, primes2, size_p2 = primes_of("c2_ntt14")
+    assert size_p2 == 0
+    nop = P.PhantomContext(log_n2, list(primes2), 0, device=gpu)
+    _refused_with(nop.inner_product_relin_rescale_batched, "context has no special modulus", 4, d1, d2, 0, batch, kp, dres, strides=(1, 1, 1, 1))
+    _refused_with(nop.inner_product_relin_batched, "context has no special modulus", 4, d1, d2, 0, batch, kp, O.CKKS, dks, strides=(1, 1, 1, 1))
+    torch.cuda.synchronize()
+    for _, out, _ in entries.values():
+        assert bool((out == POISON).all()), "a refused call wrote to its output"
+    assert bool((r2 == POISON).all()) and torch.equal(d1, keep1) and torch.equal(d2, keep2), "a refused call wrote to a buffer"
+    del ctx, bgv, nop, keys
     _release()
 
 

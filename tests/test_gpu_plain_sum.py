@@ -500,6 +500,83 @@ def test_refusals_leave_everything_untouched(gpu):
     _release()
 
 
+def _refused_with(fn, text, *args, **kw):
+    with pytest.raises(ValueError) as e:
+        fn(*args, **kw)
+    assert str(e.value) == text, f"refused with {str(e.value)!r}, not with {text!r}"
+
+
+def test_every_refusal_and_their_order(gpu):
+    """The refusals of the two entries that test_refusals_leave_everything_untouched does not reach, the whole message compared, and
+    for several defects in one call the one that is reported: the term count, the batch, odd strides, alignment of the operands,
+    overlapping terms of plain, of ct, and only then the output (its alignment, then plain, ct, acc).  Nothing is launched."""
+    import torch
+    name = "hyb12_a2"
+    P, ctx, log_n, primes, size_p, ql = _setup(name, gpu)
+    n, batch, terms = 1 << log_n, 2, 3
+    pl = primes[:ql]
+    ln = ql * n
+    rng = rng_for(10550)
+    dp = P.to_device(_uniform(rng, pl, (batch, terms), n), gpu)
+    dc = P.to_device(_uniform(rng, pl, (batch, terms, 2), n), gpu)
+    da = P.to_device(_uniform(rng, pl, (batch, 2), n), gpu)
+    keep = [x.clone() for x in (dp, dc, da)]
+    dense = (ln, terms * ln, 2 * ln, terms * 2 * ln, 2 * ln)
+    even, aligned = "strides must be even (16-byte loads)", "buffers must be 16-byte aligned"
+    crowded_p, crowded_c = "plain term stride below L * N: the terms of plain overlap", "ct term stride below 2 * L * N: the terms of ct overlap"
+    on_acc = " must not overlap acc (other than res == acc with a stride of 2 * L * N)"
+    entries = (   # call(plain, ct, acc, terms, batch, strides, out), the output, its name in a refusal
+        (lambda p, c, a, t, B, st, out: ctx.multiply_plain_sum_batched(p, c, a, out, ql, t, B, strides=st), _poisoned((batch, 2, ql, n), gpu), "res"),
+        (lambda p, c, a, t, B, st, out: ctx.plain_inner_product_rescale_batched(ql, p, c, a, t, B, O.CKKS, out, strides=st),
+         _poisoned((batch, 2, ql - 1, n), gpu), "dst"),
+    )
+    offp, offc, offa = dp.view(-1)[1:], dc.view(-1)[1:], da.view(-1)[1:]   # 8 bytes past a 16-byte boundary
+    for call, out, out_name in entries:
+        off_out, words = out.view(-1)[1:], out.numel()
+        _refused_with(call, "terms out of range", dp, dc, da, 1 << 32, batch, dense, out)
+        _refused_with(call, "batch out of range", dp, dc, da, terms, 65536, dense, out)
+        for args in ((offp, dc, da), (dp, offc, da), (dp, dc, offa)):
+            _refused_with(call, aligned, *args, terms, batch, dense, out)
+        _refused_with(call, aligned, dp, dc, da, terms, batch, dense, off_out)
+        _refused_with(call, aligned, dp, dc, None, terms, batch, dense, off_out)
+        _refused_with(call, crowded_p, dp, dc, da, terms, batch, (ln - 2,) + dense[1:], out)
+        _refused_with(call, crowded_c, dp, dc, da, terms, batch, dense[:2] + (2 * ln - 2,) + dense[3:], out)
+        _refused_with(call, even, dp, dc, None, terms, batch, dense[:4] + (2 * ln + 1,), out)    # acc's stride although there is no acc
+        _refused_with(call, out_name + " must not overlap a plaintext operand", dp, dc, da, terms, batch, dense, dp.view(-1)[:words])
+        _refused_with(call, out_name + " must not overlap an operand ciphertext", dp, dc, da, terms, batch, dense, dc.view(-1)[dc.numel() - words:])
+        _refused_with(call, out_name + on_acc, dp, dc, da, terms, batch, dense, da.view(-1)[2 * n:2 * n + words])
+        # every stride and alignment defect at once, then with the winner taken away each time
+        _refused_with(call, even, offp, offc, offa, terms, batch, (ln - 1, 1, 2 * ln - 1, 3, 5), off_out)
+        _refused_with(call, aligned, offp, offc, offa, terms, batch, (ln - 2, 0, 2 * ln - 2, 2, 4), off_out)
+        _refused_with(call, crowded_p, dp, dc, da, terms, batch, (ln - 2, 0, 2 * ln - 2, 2, 4), off_out)
+        _refused_with(call, crowded_c, dp, dc, da, terms, batch, (ln, 0, 2 * ln - 2, 2, 4), off_out)
+        _refused_with(call, aligned, dp, dc, da, terms, batch, dense, dp.view(-1)[1:1 + words])   # misaligned AND on a plaintext
+        # the term count and the batch come before the layout
+        _refused_with(call, "terms must be at least 1", offp, dc, da, 0, 65536, (ln + 1,) + dense[1:], out)
+        _refused_with(call, "terms out of range", offp, dc, da, 1 << 32, 65536, (ln + 1,) + dense[1:], out)
+        _refused_with(call, "batch out of range", offp, dc, da, terms, 65536, (ln + 1,) + dense[1:], out)
+    f, g = ctx.multiply_plain_sum_batched, ctx.plain_inner_product_rescale_batched
+    res, dst = entries[0][1], entries[1][1]
+    # res == acc is the sum entry's alone, and only in acc's own layout; the plaintext and the ciphertext are looked at first
+    big_acc = torch.zeros((batch * 4 * ln,), dtype=torch.int64, device=gpu)
+    _refused_with(f, "res" + on_acc, dp, dc, big_acc, big_acc[:batch * 2 * ln], ql, terms, batch, strides=dense[:4] + (4 * ln,))
+    _refused_with(g, "dst" + on_acc, ql, dp, dc, da, terms, batch, O.CKKS, da.view(-1)[:dst.numel()], strides=dense)
+    _refused_with(f, "res must not overlap a plaintext operand", dp, dc, dp.view(-1)[:batch * 2 * ln], dp.view(-1)[:batch * 2 * ln], ql, terms,
+                  batch, strides=dense)
+    # the limb count sits between the term count and the batch; the rescale entry's own checks come before everything shared
+    _refused_with(f, "coeff_mod_size out of range", offp, dc, da, res, 0, terms, 65536, strides=(ln + 1,) + dense[1:])
+    _refused_with(f, "terms out of range", offp, dc, da, res, 0, 1 << 32, 65536, strides=(ln + 1,) + dense[1:])
+    _refused_with(g, "unsupported scheme", ql, dp, dc, da, terms, batch, 99, dst)
+    _refused_with(g, "cannot rescale the last remaining modulus", 1, offp, dc, da, 0, 65536, O.CKKS, dst, strides=(1, 1, 1, 1, 1))
+    _refused_with(g, "bgv needs a plain modulus (pha_context_set_plain_modulus)", ql, offp, dc, da, 0, 65536, O.BGV, dst, strides=(1, 1, 1, 1, 1))
+    _refused_with(g, "size_Ql out of range", 0, offp, dc, da, 0, 65536, O.BGV, dst, strides=(1, 1, 1, 1, 1))
+    torch.cuda.synchronize()
+    assert bool((res == POISON).all()) and bool((dst == POISON).all()), "a refused call wrote to its output"
+    assert all(torch.equal(a, b) for a, b in zip((dp, dc, da), keep)) and not bool(big_acc.any()), "a refused call wrote to an operand"
+    del ctx
+    _release()
+
+
 # ------------------------------------------------------------------------------------------------------------------------------
 # H: strict mode
 # ------------------------------------------------------------------------------------------------------------------------------
