@@ -663,6 +663,56 @@ int pha_relinearize_rotate_batched(pha_context_t ctx, size_t size_Ql, const uint
 int pha_broadcast_keys(pha_context_t ctx, uint64_t *const *keys, size_t n_keys, size_t words_per_key, int root, void *nccl_comm,
                        void *stream);
 
+/* ---- CKKS encoder (PhantomCKKSEncoder, src/ckks.cu; special FFT src/fft.cu; decompose / compose src/rns_base.cu:49-253;
+ *      csrc/pha_ckks.hip, arithmetic in csrc/pha_ckks_fft.h).  N = the context's degree, n = N / 2 slots,
+ *      M = 2 N.  All data buffers are DEVICE memory; complex numbers are interleaved (re, im) doubles.  "Bit-exact" for these
+ *      entries: a complex product is (ar*br - ai*bi, ar*bi + ai*br), every operation rounded on its own, in the radix-2 butterfly
+ *      graph of the reference; the reference's own bits on its hardware depend on its compiler's contraction and are not pinned.
+ *      Only canonical words are written: a coefficient that rounds to -0.0 gives 0 where the reference writes q.
+ * pha_ckks_encoder_create: the tables of PhantomCKKSEncoder's constructor (roots[i] = e^{2 pi i * i / M}, i < M, from polar() over
+ *   an eighth of the circle plus the 8-fold symmetry; group[i] = 5^i mod M, i < n / 2) for ctx, which must outlive the encoder.
+ *   _tables copies them to HOST arrays (roots_host: 2 M doubles, group_host: n / 2 words; either may be null).
+ * pha_special_fft_backward / _forward (special_fft_backward / special_fft_forward, src/fft.cu:348-422): in place on ONE array of
+ *   2^log_n complex numbers, log_n <= log2 n, no bit reversal; backward multiplies the result by `scalar` unless it is 0.
+ * pha_decompose_array (DRNSBase::decompose_array): dst [size_Ql][N] <- round(coefficient j) mod q_i, coefficient j = Re src[j]
+ *   for j < n, Im src[j - n] above; src n complex numbers.  max_coeff_bit_count picks the kernel (<= 64: the coefficient fits a
+ *   word; above: mantissa and exponent), both exact.
+ * pha_compose_array (DRNSBase::compose_array): src [size_Ql][N] in coefficient form -> dst n complex numbers, coefficient j =
+ *   (centred CRT value) * inv_scale accumulated word by word from the low word up as the reference kernel does.  The level's
+ *   big-integer tables are built on the host on its first use.
+ * Extension (no reference launcher: the reference encodes one message per call, one launch per FFT stage above 2048 points, and
+ *   copies the coefficients to the host for their maximum) pha_ckks_encode_batched: message k = values_size complex numbers at
+ *   values + 2 * k * values_stride doubles (values_stride counts complex numbers), k < count <= 65535; plaintext k, in NTT form,
+ *   at dst + k * dst_stride: [size_Ql][N], or with_special != 0 [size_Ql + size_P][N] over the limbs [0, size_Ql) u P (the layout
+ *   the hoisting entries take; equal to those rows of the key-level encoding).  At most two passes over the message for the FFT at
+ *   every N; coefficients that fit a word (max_coeff_bit_count <= 64) are rounded and reduced in the load of the forward
+ *   transform's first pass, every limb reading the same [N] doubles, so the decomposed form [L][N] is never written; wider ones go
+ *   through the decompose kernel and the plain transform (same words).  Refusals as encode_internal
+ *   (status -1): "Input vector is empty", "Input vector exceeds max slots", "scale out of bounds" (scale <= 0 or
+ *   (int) log2(scale) + 1 >= the bit count of q_0 .. q_{size_Ql - 1}), "encoded values are too large" (max_coeff_bit_count =
+ *   ceil(log2(max(max |coefficient|, 1))) + 1, taken from the bit pattern, >= that bit count; Inf / NaN inputs end here).
+ *   bit_counts_host_or_null: HOST array of `count` ints that receives max_coeff_bit_count per message.  The call SYNCHRONISES the
+ *   stream once, reading back `count` words: the refusal and the choice of the decompose kernel need the maxima -- so it cannot be
+ *   captured into a graph.  dst: 16-byte aligned, dst_stride even and >= the plaintext's size when count > 1.
+ * Extension pha_ckks_decode_batched: plaintext k [size_Ql][N] (NTT form, only read) at plain + k * plain_stride -> n complex
+ *   numbers at values_out + 2 * k * values_stride doubles; scale as PhantomPlaintext::scale() ("scale out of bounds" when <= 0
+ *   or (int) log2(scale) >= the level's bit count).  Strict mode checks plain.
+ * Scratch comes from the context's arenas. ---- */
+typedef struct pha_ckks_encoder *pha_ckks_encoder_t;
+int pha_ckks_encoder_create(pha_context_t ctx, pha_ckks_encoder_t *enc);
+void pha_ckks_encoder_destroy(pha_ckks_encoder_t enc);
+int pha_ckks_encoder_tables(pha_ckks_encoder_t enc, double *roots_host, uint32_t *group_host);
+int pha_special_fft_backward(pha_ckks_encoder_t enc, double *inout, size_t log_n, double scalar, void *stream);
+int pha_special_fft_forward(pha_ckks_encoder_t enc, double *inout, size_t log_n, void *stream);
+int pha_decompose_array(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const double *src, uint32_t max_coeff_bit_count,
+                        void *stream);
+int pha_compose_array(pha_context_t ctx, size_t size_Ql, double *dst, const uint64_t *src, double inv_scale, void *stream);
+int pha_ckks_encode_batched(pha_ckks_encoder_t enc, size_t size_Ql, int with_special, const double *values, size_t values_size,
+                            size_t count, size_t values_stride, double scale, uint64_t *dst, size_t dst_stride,
+                            int *bit_counts_host_or_null, void *stream);
+int pha_ckks_decode_batched(pha_ckks_encoder_t enc, size_t size_Ql, const uint64_t *plain, size_t count, size_t plain_stride,
+                            double scale, double *values_out, size_t values_stride, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,6 +28,12 @@ int pha_time_stream(uint64_t *dst, const uint64_t *src, size_t bytes, int mode, 
 /* = pha_time_stream(dst, src, bytes, 0, 1, ...): the nontemporal copy */
 int pha_time_stream_copy(uint64_t *dst, const uint64_t *src, size_t bytes, int iters, void *stream, double *bytes_per_s);
 
+/* which path pha_ckks_encode_batched takes for coefficients that fit a word (max_coeff_bit_count <= 64), process-wide: -1 = the
+ * library's own rule per launch shape (the default), 0 = always the decompose kernel followed by the batched forward transform,
+ * 1 = always round-and-reduce as the load prologue of the transform's first pass (PRO_CKKS).  The words are the same either way;
+ * tools/time_ckks_encoder.py times both.  Wider coefficients always take the decompose kernel. */
+int pha_ckks_set_encode_path(int mode);
+
 /* number of scratch arenas the context currently holds (one per explicit stream, one per live host thread for the per-thread and
  * null streams; a thread's arenas are released when it exits) */
 int pha_context_arena_count(pha_context_t ctx, size_t *count);

@@ -238,6 +238,17 @@ struct HpsQ {
     DevBuf<u64> drop_mod_q, drop_mod_q_shoup;    // [Ql]            product of the dropped primes mod q_i
 };
 
+// ---- CKKS decode at one level (src/rns_base.cu:173-253): the big-integer tables of the CRT composition over q_0 .. q_{size-1},
+//      little-endian words padded to `size` (pha_ckks.hip)
+struct CkksCompose {
+    uint32_t size = 0;
+    int bits = 0;                // total_coeff_modulus_bit_count of the level
+    DevBuf<u64> big_q;           // [size]        Q
+    DevBuf<u64> punct;           // [size][size]  Q / q_i
+    DevBuf<u64x2> inv;           // [size]        (Q / q_i)^-1 mod q_i (+Shoup)
+    DevBuf<u64> thresh;          // [size]        (Q + 1) / 2
+};
+
 // ---- scratch arena: one per (context, stream), grown on demand, never freed until destroy ----
 struct Arena {
     DevBuf<u64> buf;
@@ -282,6 +293,8 @@ struct Context {
     std::unique_ptr<Behz> behz_tool;
     std::unique_ptr<Hps> hps_tool;
     std::map<uint32_t, std::unique_ptr<HpsQ>> hpsq_tools;   // by |Ql| (|Q| = plain hps_overq)
+    std::map<uint32_t, std::unique_ptr<CkksCompose>> ckks_tables;   // by |Ql|; built on first use (pha_ckks.hip)
+    CkksCompose &ckks_compose(uint32_t size_ql);
     uint32_t rows = 0;  // table rows = size_qp + auxiliary moduli
     // keyed by (stream handle, host thread): hipStreamPerThread and the null stream are sentinels that name a different
     // real stream (or none) in every host thread, so those two handles get one arena per calling thread
@@ -378,6 +391,7 @@ struct NttExtra {
     const u64 *pro_src = nullptr;                        // forward only: every limb of polynomial z transforms
     size_t pro_stride = 0;                               //   (pro_src + z * pro_stride) mod its own prime; `in` unused
     u64 pro_lift_t = 0;                                  //   != 0 (EPI_FWD_CANON only): the words are below this t and are LIFTED instead, centred (pha_bfv_lift.h)
+    bool pro_ckks = false;                               //   true (EPI_FWD_CANON only): the words are doubles, rounded and reduced instead (pha_ckks_fft.h, PRO_CKKS)
     size_t aux_pair_stride = 0;                          // EPI_INV_CANON_ADD: polynomials come in pairs; pair g adds aux + g * aux_pair_stride (+ aux_stride for its second)
     uint32_t excl_step = 0;                              // polynomial z skips [excl_start + z*step, min(+len, limit))
     uint32_t excl_limit = 0xffffffffu;

@@ -83,6 +83,7 @@ struct NttKArgs {
     // back on ONE XCD (block b -> XCD b % 8), so that the twiddle rows they share are fetched into that L2 once
     uint32_t zfast_tiles;    // 0 = plain 3-D grid (tile, limb, polynomial); else tiles per limb of the 1-D form
     uint32_t zfast_run;      // tiles of one polynomial that run back to back before the next polynomial's (a multiple of 8)
+    bool pro_ckks;           // the prologue is CKKS round-and-reduce instead (PRO_CKKS kernels): pro_src holds doubles
     u64 pro_t;               // != 0: the prologue is the BFV plain lift instead (PRO_LIFT kernels): pro_src holds words below pro_t
     size_t aux_pair_stride;  // EPI_INV_CANON_ADD: polynomial z adds aux + (z / 2) * aux_pair_stride + (z % 2) * aux_stride (acc of group z / 2)
     const u64 *h_primes;     // HOST copy of the context's primes (launchers only: which limbs run on the FP64 back end)
@@ -352,10 +353,12 @@ static void dispatch_epi(int epi, F &&f) {
     }
 }
 // the load prologue of a forward transform's first pass: the BFV plain lift (a plaintext's words lifted as they are loaded) where
-// k.pro_t asks for it.  ntt_forward admits it with the canonical epilogue only.
+// k.pro_t asks for it, the CKKS round-and-reduce (double coefficients rounded and reduced as they are loaded) where k.pro_ckks does.
+// ntt_forward admits either with the canonical epilogue only.
 template <class F>
 static void dispatch_pro(const NttKArgs &k, F &&f) {
-    if (k.pro_t) f(ProC<PRO_LIFT>{});
+    if (k.pro_ckks) f(ProC<PRO_CKKS>{});
+    else if (k.pro_t) f(ProC<PRO_LIFT>{});
     else f(ProC<PRO_NONE>{});
 }
 
@@ -478,7 +481,7 @@ static void forward_impl(const NttKArgs &k_in, int epi, hipStream_t s, Context *
         throw std::logic_error("ntt_forward: first_pass_done needs the 64 x 1024 plan the fused conversion wrote");
 #if defined(PHA_EXPERIMENTS)
     if constexpr (T::ONE_LAUNCH) {
-        if (fused && epi != EPI_FWD_KSRESCALE && !k.first_pass_done && !k.pro_t) {   // both passes in one launch
+        if (fused && epi != EPI_FWD_KSRESCALE && !k.first_pass_done && !k.pro_t && !k.pro_ckks) {   // both passes in one launch
             bool done = false;
             dispatch_epi<true>(epi, [&](auto e) {
                 if constexpr (e() != EPI_FWD_KSRESCALE) done = launch_fused<P1, P2, true, e(), false>(*fused, k1, k, s);
@@ -585,6 +588,7 @@ static NttKArgs make_args(Context &c, const u64 *in, u64 *mid, u64 *out, const L
     k.pro_src = fwd ? x.pro_src : nullptr;
     k.pro_stride = x.pro_stride;
     k.pro_t = fwd && x.pro_src ? x.pro_lift_t : 0;
+    k.pro_ckks = fwd && x.pro_src && x.pro_ckks;
     k.aux_pair_stride = x.aux_pair_stride;
     return k;
 }
@@ -672,7 +676,8 @@ static void ntt_transform(Context &c, const u64 *in, u64 *mid, u64 *out, const L
     if (sel.count == 0) return;
     check_sel(c, sel);
     NttKArgs k = make_args(c, in, mid, out, sel, x, FWD);
-    if (k.pro_t && (epi != EPI_FWD_CANON || x.first_pass_done)) throw std::logic_error("ntt_forward: the plain lift goes with the plain forward transform only");
+    if ((k.pro_t || k.pro_ckks) && (epi != EPI_FWD_CANON || x.first_pass_done || (k.pro_t && k.pro_ckks)))
+        throw std::logic_error("ntt_forward: the plain lift and the CKKS round-and-reduce go with the plain forward transform only, one at a time");
     const ResolvedPlan r = choose_plan(c, sel, x);
     k.zfast_tiles = r.zfast ? 1u : 0u;   // request: launch_pass turns it into the tile count of the contiguous pass
     dispatch_plan(r, [&](auto logn, auto variant) {

@@ -24,6 +24,7 @@
 #pragma once
 #include "pha_arith.h"
 #include "pha_bfv_lift.h"
+#include "pha_ckks_fft.h"
 
 namespace pha {
 
@@ -48,6 +49,8 @@ enum Epilogue {
 enum Prologue {
     PRO_NONE = 0,
     PRO_LIFT = 1,   // forward: `in` holds words below t; each becomes its centred lift modulo this limb's prime (pha_bfv_lift.h)
+    PRO_CKKS = 2,   // forward: `in` holds doubles (CKKS coefficients of magnitude below 2^63); each is rounded and reduced modulo this
+                    // limb's prime (pha_ckks_fft.h ckks_round_reduce64), so the decomposed form [L][N] is never written
 };
 
 // Round schedule of one pass: LOGT stages split into NR rounds of R0,R1,R2 stages (forward order).
@@ -817,12 +820,16 @@ struct PassProgram {
                 static_assert(FWD && FIRST_PASS, "the plain lift is the load prologue of a forward transform's first pass");
 #pragma unroll
                 for (int i = 0; i < C::EPT; i++) reg[i] = bfv_lift_word(reg[i], a.pro_half, a.pro_inc);
+            } else if constexpr (PRO == PRO_CKKS) {   // CKKS encode: the words just loaded are the bit patterns of double coefficients
+                static_assert(FWD && FIRST_PASS, "round-and-reduce is the load prologue of a forward transform's first pass");
+#pragma unroll
+                for (int i = 0; i < C::EPT; i++) reg[i] = ckks_round_reduce64(as_f64(reg[i]), a.q, a.pro_ratio1);
             } else if (FWD && FIRST_PASS && a.pro_reduce) {  // uniform per workgroup
 #pragma unroll
                 for (int i = 0; i < C::EPT; i++) reg[i] = barrett64(reg[i], a.q, a.pro_ratio1);
             }
         }
-        static_assert(PRO != PRO_LIFT || MODE == SEG_PLAIN, "the load prologue belongs to the pass that loads");
+        static_assert(PRO == PRO_NONE || MODE == SEG_PLAIN, "the load prologue belongs to the pass that loads");
         if (first) fp_after_global_load(a, reg);
         // FP64 forward, whole-transform plans beyond 13 stages: magnitudes grow by q/2 + 1 per stage, and the exactness
         // budget of pha_arith.h (|x| < 2^52.6 ~ 6 q at 50 bits going into a multiply) is spent after 13 of them (q + 13 (q/2 + 1)

@@ -12,6 +12,7 @@
 // Header-only; needs the HIP runtime for device memory (hipMallocAsync / hipFreeAsync on the
 // per-thread stream, like include/cuda_wrapper.cuh:65-189) and libphantom_amd.so for every kernel.
 #pragma once
+#include <hip/hip_complex.h>
 #include <hip/hip_runtime.h>
 #include <phantom_amd.h>
 
@@ -30,6 +31,7 @@
 
 // the reference spells the stream type cudaStream_t in every signature
 using cudaStream_t = hipStream_t;
+using cuDoubleComplex = hipDoubleComplex;   // (x, y) = (re, im), as the reference's encoder signatures spell it
 #ifndef cudaStreamPerThread
 #define cudaStreamPerThread hipStreamPerThread
 #endif
@@ -608,8 +610,8 @@ public:
 };
 
 // PhantomPlaintext (include/plaintext.h:8-116): metadata + one device buffer.  BFV / BGV plaintexts hold N coefficients
-// modulo t (coeff_modulus_size 1); CKKS plaintexts hold [limb][coeff] in NTT form at their chain index.  The encoders
-// that fill it are outside the accelerated path; load_from_host stands in for them.
+// modulo t (coeff_modulus_size 1); CKKS plaintexts hold [limb][coeff] in NTT form at their chain index.  PhantomCKKSEncoder
+// (below) fills CKKS plaintexts; the BFV / BGV batch encoder is outside the accelerated path, load_from_host stands in for it.
 class PhantomPlaintext {
     size_t chain_index_ = 0, poly_modulus_degree_ = 0, coeff_modulus_size_ = 0;
     double scale_ = 1.0;
@@ -667,6 +669,104 @@ public:
         phantom::util::check_hip(hipMemcpyAsync(host, data_.get(), coeff_count() * 8, hipMemcpyDeviceToHost, stream), "hipMemcpyAsync");
         phantom::util::check_hip(hipStreamSynchronize(stream), "hipStreamSynchronize");
     }
+};
+
+// PhantomCKKSEncoder (include/ckks.h:11-115, src/ckks.cu): the reference's signatures, checks and exception types over the
+// batched device entries (pha_ckks_encode_batched / pha_ckks_decode_batched with one message).  encode fills the limbs of the
+// chain index it is given -- at chain index 0 (the key level) the data limbs and the special limbs; the reference allocates
+// all of QP for every plaintext and leaves the rest unwritten, this one allocates what it fills.  The context must outlive the encoder.
+class PhantomCKKSEncoder {
+    pha_ckks_encoder_t enc_ = nullptr;
+    uint32_t slots_ = 0;
+    uint32_t first_chain_index_ = 1;
+
+    // (size_Ql, with_special) of a chain index: 0 is the key level [Q u P], 1 + l drops l data primes
+    static std::pair<size_t, int> level_of(const PhantomContext &context, size_t chain_index) {
+        const size_t limbs = context.get_context_data(chain_index).parms().coeff_modulus().size();
+        if (chain_index == 0 && context.using_keyswitching())
+            return {limbs - context.get_context_data(0).parms().special_modulus_size(), 1};
+        return {limbs, 0};
+    }
+
+    void encode_internal(const PhantomContext &context, const std::vector<cuDoubleComplex> &values, size_t chain_index, double scale,
+                         PhantomPlaintext &destination, const cudaStream_t &stream) {
+        using namespace phantom::util;
+        if (values.empty()) throw std::invalid_argument("Input vector is empty");
+        if (values.size() > slots_) throw std::invalid_argument("Input vector exceeds max slots");
+        const auto level = level_of(context, chain_index);
+        const size_t limbs = context.get_context_data(chain_index).parms().coeff_modulus().size();
+        destination.resize(limbs, context.poly_degree(), stream);
+        auto temp = make_cuda_auto_ptr<cuDoubleComplex>(values.size(), stream);
+        check_hip(hipMemcpyAsync(temp.get(), values.data(), values.size() * sizeof(cuDoubleComplex), hipMemcpyHostToDevice, stream),
+                  "hipMemcpyAsync");
+        check_pha(pha_ckks_encode_batched(enc_, level.first, level.second, reinterpret_cast<const double *>(temp.get()), values.size(), 1,
+                                          values.size(), scale, destination.data(), limbs * context.poly_degree(), nullptr, stream));
+        destination.set_chain_index(chain_index);
+        destination.set_scale(scale);
+    }
+    void encode_internal(const PhantomContext &context, const std::vector<double> &values, size_t chain_index, double scale,
+                         PhantomPlaintext &destination, const cudaStream_t &stream) {
+        std::vector<cuDoubleComplex> input(values.size());
+        for (size_t i = 0; i < values.size(); i++) input[i] = make_hipDoubleComplex(values[i], 0.0);
+        encode_internal(context, input, chain_index, scale, destination, stream);
+    }
+    void decode_internal(const PhantomContext &context, const PhantomPlaintext &plain, std::vector<cuDoubleComplex> &destination,
+                         const cudaStream_t &stream) {
+        using namespace phantom::util;
+        const auto level = level_of(context, plain.chain_index());
+        if (level.second) throw std::invalid_argument("cannot decode a plaintext at the key level");
+        auto out = make_cuda_auto_ptr<cuDoubleComplex>(slots_, stream);
+        check_pha(pha_ckks_decode_batched(enc_, level.first, plain.data(), 1, 0, plain.scale(), reinterpret_cast<double *>(out.get()), slots_,
+                                          stream));
+        destination.resize(slots_);
+        check_hip(hipMemcpyAsync(destination.data(), out.get(), slots_ * sizeof(cuDoubleComplex), hipMemcpyDeviceToHost, stream),
+                  "hipMemcpyAsync");
+        check_hip(hipStreamSynchronize(stream), "hipStreamSynchronize");   // the caller may use the result at once
+    }
+    void decode_internal(const PhantomContext &context, const PhantomPlaintext &plain, std::vector<double> &destination,
+                         const cudaStream_t &stream) {
+        std::vector<cuDoubleComplex> output;
+        decode_internal(context, plain, output, stream);
+        destination.resize(slots_);
+        for (size_t i = 0; i < slots_; i++) destination[i] = output[i].x;
+    }
+
+public:
+    explicit PhantomCKKSEncoder(const PhantomContext &context) {
+        const auto &parms = context.get_context_data(first_chain_index_ < context.total_parm_size() ? first_chain_index_ : 0).parms();
+        if (parms.scheme() != phantom::scheme_type::ckks) throw std::invalid_argument("unsupported scheme");
+        slots_ = static_cast<uint32_t>(parms.poly_modulus_degree() >> 1);
+        phantom::util::check_pha(pha_ckks_encoder_create(context.amd(), &enc_));
+    }
+    PhantomCKKSEncoder(const PhantomCKKSEncoder &) = delete;
+    PhantomCKKSEncoder(PhantomCKKSEncoder &&) = delete;
+    PhantomCKKSEncoder &operator=(const PhantomCKKSEncoder &) = delete;
+    PhantomCKKSEncoder &operator=(PhantomCKKSEncoder &&) = delete;
+    ~PhantomCKKSEncoder() { pha_ckks_encoder_destroy(enc_); }
+
+    template <class T>
+    void encode(const PhantomContext &context, const std::vector<T> &values, double scale, PhantomPlaintext &destination,
+                size_t chain_index = 1) {
+        encode_internal(context, values, chain_index, scale, destination, cudaStreamPerThread);
+    }
+    template <class T>
+    [[nodiscard]] PhantomPlaintext encode(const PhantomContext &context, const std::vector<T> &values, double scale, size_t chain_index = 1) {
+        PhantomPlaintext destination;
+        encode(context, values, scale, destination, chain_index);
+        return destination;
+    }
+    template <class T>
+    void decode(const PhantomContext &context, const PhantomPlaintext &plain, std::vector<T> &destination) {
+        decode_internal(context, plain, destination, cudaStreamPerThread);
+    }
+    template <class T>
+    [[nodiscard]] std::vector<T> decode(const PhantomContext &context, const PhantomPlaintext &plain) {
+        std::vector<T> destination;
+        decode(context, plain, destination);
+        return destination;
+    }
+    [[nodiscard]] std::size_t slot_count() const noexcept { return slots_; }
+    [[nodiscard]] pha_ckks_encoder_t amd() const { return enc_; }
 };
 
 // PhantomRelinKey (include/secretkey.h:102-165): dnum public keys, each a size-2 ciphertext [2][#QP][N] at chain

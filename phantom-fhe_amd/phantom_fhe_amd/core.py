@@ -47,6 +47,13 @@ def _ptr(t):
     return t.data_ptr()
 
 
+def _fptr(t):
+    """Device pointer of a contiguous float64 / complex128 CUDA tensor (the CKKS encoder's messages and coefficients)."""
+    if not (t.is_cuda and t.is_contiguous() and t.dtype in (torch.float64, torch.complex128)):
+        raise ValueError("expected a contiguous torch.float64 or torch.complex128 CUDA tensor")
+    return t.data_ptr()
+
+
 def _stream():
     return torch.cuda.current_stream().cuda_stream
 
@@ -101,6 +108,13 @@ def set_strict(on):
     """Strict mode of the library (pha_set_strict): entry points check caller-supplied operands for words >= their modulus and
     raise ValueError instead of computing.  Returns the previous state.  Process-wide; default from PHA_STRICT=1."""
     return bool(_lib.load().pha_set_strict(1 if on else 0))
+
+
+def set_ckks_encode_path(mode):
+    """Measurement hook (phantom_amd_bench.h: pha_ckks_set_encode_path): which path CKKSEncoder.encode_batched takes for coefficients
+    that fit a word -- -1 the library's rule per launch shape (default), 0 the decompose kernel followed by the forward transform, 1
+    round-and-reduce as the load prologue of the transform's first pass.  The words are the same either way.  Process-wide."""
+    _lib.check(_lib.load().pha_ckks_set_encode_path(int(mode)))
 
 
 def coeff_modulus_create(poly_modulus_degree, bit_sizes):
@@ -722,6 +736,21 @@ class PhantomContext:
         _lib.check(self._L.pha_context_arena_count(self._h, C.byref(cnt)))
         return cnt.value
 
+    # -- CKKS encoder pieces that belong to the level (DRNSBase, src/rns_base.cu:49-253) ------------
+    def decompose_array(self, size_Ql, dst, src, max_coeff_bit_count):
+        """DRNSBase::decompose_array: dst [size_Ql][N] <- the rounded coefficients of src (N / 2 complex numbers: coefficient j is
+        Re src[j], coefficient j + N / 2 is Im src[j]) modulo every prime of the level."""
+        _lib.check(self._L.pha_decompose_array(self._h, size_Ql, _ptr(dst), _fptr(src), int(max_coeff_bit_count), _stream()))
+
+    def compose_array(self, size_Ql, dst, src, inv_scale):
+        """DRNSBase::compose_array: src [size_Ql][N] in coefficient form -> dst N / 2 complex numbers, the centred CRT value of every
+        coefficient times inv_scale."""
+        _lib.check(self._L.pha_compose_array(self._h, size_Ql, _fptr(dst), _ptr(src), float(inv_scale), _stream()))
+
+    def ckks_encoder(self):
+        """A CKKSEncoder over this context."""
+        return CKKSEncoder(self)
+
     # -- measurement ------------------------------------------------------------------------------
     def repeat_forward_ntt_batched(self, inout, cms, start, batch, poly_stride, repeats):
         """`repeats` back-to-back batched forward transforms enqueued from C (bench.py's timed region)."""
@@ -731,6 +760,60 @@ class PhantomContext:
         ms = C.c_float()
         _lib.check(self._L.pha_time_forward_ntt(self._h, _ptr(inout), cms, iters, _stream(), C.byref(ms)))
         return ms.value
+
+
+class CKKSEncoder:
+    """PhantomCKKSEncoder's device work (src/ckks.cu) over the C ABI: the tables, the special FFT launchers, and the batched
+    encode / decode extensions.  Messages are contiguous torch.complex128 (or float64 pairs) CUDA tensors."""
+
+    def __init__(self, ctx):
+        self._ctx, self._L = ctx, _lib.load()    # the context must outlive the encoder: keep it
+        h = C.c_void_p()
+        _lib.check(self._L.pha_ckks_encoder_create(ctx._h, C.byref(h)))
+        self._h = h
+        self.slot_count = ctx.n // 2
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.pha_ckks_encoder_destroy(self._h)
+            self._h = None
+
+    def tables(self):
+        """(roots [2N] complex128, group [N / 4] uint32): the host tables of the constructor."""
+        roots = np.zeros(4 * self.slot_count, dtype=np.complex128)
+        group = np.zeros(self.slot_count // 2, dtype=np.uint32)
+        _lib.check(self._L.pha_ckks_encoder_tables(self._h, roots.ctypes.data_as(C.POINTER(C.c_double)),
+                                                   group.ctypes.data_as(C.POINTER(C.c_uint32))))
+        return roots, group
+
+    def special_fft_backward(self, inout, log_n, scalar):
+        """special_fft_backward (src/fft.cu:385-422): in place on 2^log_n complex numbers, no bit reversal, times `scalar`."""
+        _lib.check(self._L.pha_special_fft_backward(self._h, _fptr(inout), log_n, float(scalar), _stream()))
+
+    def special_fft_forward(self, inout, log_n):
+        """special_fft_forward (src/fft.cu:348-379)."""
+        _lib.check(self._L.pha_special_fft_forward(self._h, _fptr(inout), log_n, _stream()))
+
+    def encode_batched(self, size_Ql, values, values_size, scale, dst, with_special=False, count=None, strides=None):
+        """Extension: plaintext k of dst [count][L][N] (L = size_Ql, or size_Ql + size_P with_special: the limbs [0, size_Ql) u P) <-
+        the NTT-form encoding of message k = the first values_size numbers of values [count][...] at `scale`.  strides: (values in
+        complex numbers, dst in words); None: dense.  Returns max_coeff_bit_count per message; synchronises the stream once."""
+        ctx = self._ctx
+        limbs = size_Ql + (ctx.size_P if with_special else 0)
+        count = int(values.shape[0]) if count is None else int(count)
+        vs, ds = (int(v) for v in strides) if strides is not None else (int(values.numel() // max(count, 1)), limbs * ctx.n)
+        bits = (C.c_int * max(count, 1))()
+        _lib.check(self._L.pha_ckks_encode_batched(self._h, size_Ql, int(bool(with_special)), _fptr(values), int(values_size), count, vs,
+                                                   float(scale), _ptr(dst), ds, bits, _stream()))
+        return [int(b) for b in bits[:count]]
+
+    def decode_batched(self, size_Ql, plain, scale, values_out, count=None, strides=None):
+        """Extension: values_out [count][N / 2] complex <- the decoding of plaintext k of plain [count][size_Ql][N] (NTT form) at
+        `scale`.  strides: (plain in words, values_out in complex numbers); None: dense."""
+        ctx = self._ctx
+        count = int(plain.shape[0]) if count is None else int(count)
+        ps, vs = (int(v) for v in strides) if strides is not None else (size_Ql * ctx.n, self.slot_count)
+        _lib.check(self._L.pha_ckks_decode_batched(self._h, size_Ql, _ptr(plain), count, ps, float(scale), _fptr(values_out), vs, _stream()))
 
 
 class DBaseConverter:

@@ -140,12 +140,22 @@ _SIGS = {
     "pha_apply_galois_for_keyswitch": [vp, vp, vp, vp, C.c_uint32, sz, sz, C.c_int, vp],
     "pha_broadcast_keys": [vp, C.POINTER(vp), sz, sz, C.c_int, vp, vp],
     "pha_relinearize_rotate_batched": [vp, sz, vp, sz, vp, vp, C.c_uint32, C.c_int, vp, sz, vp],
+    # CKKS encoder (csrc/pha_ckks.hip)
+    "pha_ckks_encoder_create": [vp, C.POINTER(vp)],
+    "pha_ckks_encoder_tables": [vp, C.POINTER(C.c_double), C.POINTER(C.c_uint32)],
+    "pha_special_fft_backward": [vp, vp, sz, C.c_double, vp],
+    "pha_special_fft_forward": [vp, vp, sz, vp],
+    "pha_decompose_array": [vp, sz, vp, vp, C.c_uint32, vp],
+    "pha_compose_array": [vp, sz, vp, vp, C.c_double, vp],
+    "pha_ckks_encode_batched": [vp, sz, C.c_int, vp, sz, sz, sz, C.c_double, vp, sz, C.POINTER(C.c_int), vp],
+    "pha_ckks_decode_batched": [vp, sz, vp, sz, sz, C.c_double, vp, sz, vp],
     # include/phantom_amd_bench.h (measurement hooks)
     "pha_time_forward_ntt": [vp, vp, sz, C.c_int, vp, C.POINTER(C.c_float)],
     "pha_repeat_forward_ntt_batched": [vp, vp, sz, sz, sz, sz, C.c_int, vp],
     "pha_time_stream_copy": [vp, vp, sz, C.c_int, vp, C.POINTER(C.c_double)],
     "pha_time_stream": [vp, vp, sz, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double)],
     "pha_context_arena_count": [vp, C.POINTER(C.c_size_t)],
+    "pha_ckks_set_encode_path": [C.c_int],
 }
 # exported by the test-only experiments library alone (csrc/pha_experiments.h); bound when present
 _OPTIONAL = {
@@ -155,6 +165,7 @@ _SPECIAL = {
     "pha_last_error": (C.c_char_p, []),
     "pha_context_destroy": (None, [vp]),
     "pha_base_converter_destroy": (None, [vp]),
+    "pha_ckks_encoder_destroy": (None, [vp]),
     "pha_context_log_n": (C.c_uint32, [vp]),
     "pha_context_size_qp": (C.c_uint32, [vp]),
     "pha_context_size_p": (C.c_uint32, [vp]),

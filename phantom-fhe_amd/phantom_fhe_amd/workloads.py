@@ -11,6 +11,7 @@ results are bit-identical for every number of ranks.
   function (its matmul_bench is a plaintext modular GEMM); the composition is this build's, from the reference's
   hoisting_inplace (src/evaluate.cu:1670-1866), multiply_plain_inplace (:1297-1340) and add_inplace (:116-198).
 """
+import numpy as np
 import torch
 
 from . import dist as pdist
@@ -63,6 +64,30 @@ def relinearize_rotate_sharded(ctx, size_Ql, ct3, relin_key, galois_key, galois_
     if len(mine) == 0:
         return mine, ct3[:0, :2].contiguous()
     return mine, relinearize_rotate_batch(ctx, size_Ql, ct3[mine.start:mine.stop], relin_key, galois_key, galois_elt, scheme)
+
+
+def matrix_diagonals(matrix, slots, steps=None):
+    """The generalised diagonals of a d x d matrix (numpy, real or complex; d divides `slots`) as slot vectors: row k is
+    diag_k[i] = matrix[i % d][(i + steps[k]) % d] for i < slots, so that sum_k diag_k o rotate_{steps[k]}(v) = matrix v for a vector
+    v of period d in the slots (rotate_s(v)[i] = v[i + s]).  steps: the rotation steps (default 0 .. d - 1)."""
+    m = np.asarray(matrix, dtype=np.complex128)
+    d = m.shape[0]
+    if m.ndim != 2 or m.shape[1] != d or d == 0 or slots % d:
+        raise ValueError("expected a square matrix whose size divides the slot count")
+    steps = list(range(d)) if steps is None else [int(s) for s in steps]
+    i = np.arange(slots)
+    return np.stack([m[i % d, (i + s) % d] for s in steps])
+
+
+def encode_diagonals(encoder, size_Ql, matrix, scale, steps=None):
+    """The diagonals of `matrix` (matrix_diagonals) encoded on the device as diag_matvec* take them: [len(steps)][Ql + size_P][N]
+    in NTT form over the limbs [0, Ql) u P, one batched encode (CKKSEncoder.encode_batched with the special limbs)."""
+    ctx = encoder._ctx
+    diags = matrix_diagonals(matrix, encoder.slot_count, steps)
+    values = torch.from_numpy(np.ascontiguousarray(diags)).to(ctx.device)
+    out = torch.empty((diags.shape[0], size_Ql + ctx.size_P, ctx.n), dtype=torch.int64, device=ctx.device)
+    encoder.encode_batched(size_Ql, values, encoder.slot_count, scale, out, with_special=True)
+    return out
 
 
 def diag_matvec(ctx, size_Ql, ct, galois_elts, galois_keys, diagonals, scheme):

@@ -4,9 +4,10 @@
 // accelerated path: enums scheme_type / mul_tech_type, classes modulus, params, context, ciphertext,
 // relin_key, galois_key, and the functions create_coeff_modulus, get_elt_from_step(s), negate, add, sub,
 // add_plain, add_many, sub_plain, multiply, multiply_and_relin, multiply_plain, relinearize, rescale_to_next,
-// mod_switch_to_next / mod_switch_to (ciphertext and plaintext overloads), apply_galois, rotate, hoisting; class plaintext.  Like the reference, every function returns by value.  Key generation, encryption,
-// decryption and the encoders are out of scope, so ciphertexts and keys enter as
+// mod_switch_to_next / mod_switch_to (ciphertext and plaintext overloads), apply_galois, rotate, hoisting; classes plaintext and ckks_encoder.  Like the reference, every function returns by value.  Key generation, encryption,
+// decryption and the BFV / BGV batch encoder are out of scope, so ciphertexts and keys enter as
 // numpy uint64 arrays (`ciphertext.load`, `relin_key.load`) and leave with `ciphertext.to_numpy()`.
+#include <pybind11/complex.h>
 #include <pybind11/numpy.h>
 #include <pybind11/pybind11.h>
 #include <pybind11/stl.h>
@@ -97,7 +98,7 @@ PYBIND11_MODULE(pyPhantom, m) {
         .def("scale", [](const PhantomPlaintext &p) { return p.scale(); })
         .def("set_scale", &PhantomPlaintext::set_scale)
         .def("coeff_modulus_size", [](const PhantomPlaintext &p) { return p.coeff_modulus_size(); })
-        // the encoders are out of scope: a BFV / BGV plaintext is [1][N] coefficients modulo t, a CKKS one [limb][N] in NTT form
+        // the batch encoder is out of scope (ckks_encoder below makes CKKS plaintexts): a BFV / BGV plaintext is [1][N] coefficients modulo t, a CKKS one [limb][N] in NTT form
         .def("load", [](PhantomPlaintext &p, u64_array data, size_t chain_index, double scale) {
             if (data.ndim() != 2) throw std::invalid_argument("expected [limb][coeff]");
             p.load_from_host(data.data(), static_cast<size_t>(data.shape(0)), static_cast<size_t>(data.shape(1)), chain_index, scale);
@@ -107,6 +108,30 @@ PYBIND11_MODULE(pyPhantom, m) {
             p.store_to_host(out.mutable_data());
             return out;
         });
+
+    // ckks_encoder (python/src/binding.cu:98-116): the reference's four method names and slot_count; complex messages are
+    // Python complex numbers
+    py::class_<PhantomCKKSEncoder>(m, "ckks_encoder")
+        .def(py::init<const PhantomContext &>(), py::keep_alive<1, 2>())
+        .def("slot_count", &PhantomCKKSEncoder::slot_count)
+        .def("encode_complex_vector", [](PhantomCKKSEncoder &e, const PhantomContext &c, const std::vector<std::complex<double>> &values,
+                                         double scale, size_t chain_index) {
+            std::vector<cuDoubleComplex> v(values.size());
+            for (size_t i = 0; i < values.size(); i++) v[i] = make_hipDoubleComplex(values[i].real(), values[i].imag());
+            return e.encode(c, v, scale, chain_index);
+        }, py::arg(), py::arg(), py::arg(), py::arg("chain_index") = 1)
+        .def("encode_double_vector", [](PhantomCKKSEncoder &e, const PhantomContext &c, const std::vector<double> &values, double scale,
+                                        size_t chain_index) { return e.encode(c, values, scale, chain_index); },
+             py::arg(), py::arg(), py::arg(), py::arg("chain_index") = 1)
+        .def("decode_complex_vector", [](PhantomCKKSEncoder &e, const PhantomContext &c, const PhantomPlaintext &p) {
+            const std::vector<cuDoubleComplex> v = e.decode<cuDoubleComplex>(c, p);
+            std::vector<std::complex<double>> out(v.size());
+            for (size_t i = 0; i < v.size(); i++) out[i] = {v[i].x, v[i].y};
+            return out;
+        }, py::arg(), py::arg())
+        .def("decode_double_vector", [](PhantomCKKSEncoder &e, const PhantomContext &c, const PhantomPlaintext &p) {
+            return e.decode<double>(c, p);
+        }, py::arg(), py::arg());
 
     py::class_<PhantomRelinKey>(m, "relin_key")
         .def(py::init<>())
