@@ -110,8 +110,9 @@ def diag_matvec_batch(ctx, size_Ql, cts, galois_elts, galois_keys, diagonals, sc
 def diag_matvec_bsgs(ctx, size_Ql, ct, baby_elts, baby_keys, giant_elts, giant_keys, diagonals, scheme):
     """The same block in baby-step / giant-step form (pha_hoisting_weighted_bsgs): with d = n_giant * n_baby diagonals,
     out = sum_i rot_{giant_elts[i]}(sum_j diagonals[i][j] (.) rot_{baby_elts[j]}(ct)) from n_baby + n_giant - 2 Galois keys instead of
-    d - 1.  diagonals[i][j] is diagonal i * n_baby + j of the matrix, rotated back by giant step i and encoded over [Q_l || P]
-    ([Ql + size_P][N], NTT form) -- the usual offline preparation of the BSGS matrix-vector product."""
+    d - 1.  diagonals[i][j] is diagonal i * n_baby + j of the matrix (matrix_diagonals), rotated back by giant step i -- rotate_{-g} with
+    g = i * n_baby the step of giant_elts[i], np.roll(diag, +g) on the slot vector -- and encoded over [Q_l || P] ([Ql + size_P][N], NTT
+    form): the usual offline preparation of the BSGS matrix-vector product (tests/ckks_semantics.py: bsgs_diagonals)."""
     out = ct.clone()
     ctx.hoisting_weighted_bsgs(size_Ql, out, baby_elts, baby_keys, giant_elts, giant_keys, diagonals, scheme)
     return out
