@@ -287,8 +287,14 @@ uint32_t Context::add_aux_moduli(const std::vector<u64> &ntt_primes, u64 table_l
     for (u64 q : ntt_primes) {
         if (q >> 61) throw std::invalid_argument("modulus exceeds 61 bits");
         if (!h_is_prime(q) || (q - 1) % (2 * n)) throw std::invalid_argument("modulus is not an NTT prime");
-        for (u64 p : primes)
-            if (p == q) throw std::invalid_argument("coeff_modulus is not coprime");
+        // an auxiliary base is only ever converted from and to the data base Q: it must be coprime to Q and within itself.  The
+        // special primes and the other auxiliary bases never meet it, and a prime may repeat one of theirs in a row of its own
+        // (the base R of the HPS multiplies is the primes just below the smallest q_i, which is where special primes of the
+        // data primes' size lie, as in the reference)
+        for (uint32_t i = 0; i < size_q; i++)
+            if (primes[i] == q) throw std::invalid_argument("coeff_modulus is not coprime");
+        for (uint32_t i = first; i < primes.size(); i++)
+            if (primes[i] == q) throw std::invalid_argument("coeff_modulus is not coprime");
         primes.push_back(q);
         mods.push_back(h_modulus(q));
     }

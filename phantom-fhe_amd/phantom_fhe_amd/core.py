@@ -582,9 +582,12 @@ class PhantomContext:
         """keyswitch_inplace for BFV with levels dropped (src/eval_key_switch.cu:142-147, 170-175); ct [2][Q][N], c2 [Q][N]."""
         _lib.check(self._L.pha_keyswitch_inplace_bfv_leveled(self._h, size_Ql, _ptr(ct), _ptr(c2), _ptr(rlk_ptrs), _stream()))
 
-    def batched_modular_gemm(self, C, A, B, m, n, k, batch, mod_start=0):
-        """C[z] = A[z] @ B[z] mod q_{mod_start + z}, row-major [batch][m][k] x [batch][k][n] (benchmark/matmul_bench.cu)."""
-        _lib.check(self._L.pha_batched_modular_gemm(self._h, _ptr(C), n, _ptr(A), k, _ptr(B), n, m, n, k, batch, mod_start,
+    def batched_modular_gemm(self, C, A, B, m, n, k, batch, mod_start=0, lda=None, ldb=None, ldc=None):
+        """C[z] = A[z] @ B[z] mod q_{mod_start + z}, row-major [batch][m][k] x [batch][k][n] (benchmark/matmul_bench.cu).
+        lda, ldb, ldc: the leading dimensions in words (None: the rows are dense, k, n and n); matrix z of A starts at
+        z * m * lda, of B at z * k * ldb, of C at z * m * ldc."""
+        lda, ldb, ldc = (k if lda is None else lda), (n if ldb is None else ldb), (n if ldc is None else ldc)
+        _lib.check(self._L.pha_batched_modular_gemm(self._h, _ptr(C), ldc, _ptr(A), lda, _ptr(B), ldb, m, n, k, batch, mod_start,
                                                     _stream()))
 
     def hoisting(self, size_Ql, ct, galois_elts, galois_keys, scheme):

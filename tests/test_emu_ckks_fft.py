@@ -13,7 +13,7 @@ from oracle import oracle as O
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 u64p, u32p, f64p = C.POINTER(C.c_uint64), C.POINTER(C.c_uint32), C.POINTER(C.c_double)
-PRIME_BITS = [30, 36, 37, 40, 41, 42, 43, 45, 46, 47, 48, 49, 50, 55, 60, 61]   # every bit length of a prime in tests/util.py (CONFIGS and MIXED_BITS)
+PRIME_BITS = [30, 36, 37, 40, 41, 42, 43, 44, 45, 46, 47, 48, 49, 50, 51, 55, 59, 60, 61]   # every bit length of a prime in tests/util.py (CONFIGS and MIXED_BITS)
 IN_INTERLEAVED, IN_GATHER, IN_SPLIT = 0, 1, 2
 OUT_INTERLEAVED, OUT_SPLIT, OUT_SCATTER = 0, 1, 2
 

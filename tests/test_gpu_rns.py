@@ -955,6 +955,54 @@ def test_batched_modular_gemm_largest_digits_longest_k(bits, x, gpu):
         assert (got[z] == np.uint64(k * x * x % q)).all(), f"modulus {z}"
 
 
+GEMM_LD_SHAPES = [(bits, m, n, k) for bits in (50, 60) for m, n, k in ((64, 64, 64), (65, 33, 33), (64, 64, 192))] + [(60, 128, 64, 320)]
+GEMM_POISON = 0xDEADBEEFDEADBEEF
+
+
+@pytest.mark.parametrize("bits,m,n,k", GEMM_LD_SHAPES)
+def test_batched_modular_gemm_leading_dimensions_and_modulus_offset(bits, m, n, k, gpu):
+    """Rows longer than the matrices (lda = k + 3, ldb = n + 5, ldc = n + 7) and moduli that do not start at row 0 of the table
+    (mod_start = 2), vs the oracle: A, B and C are views into poisoned buffers, the padding of C keeps the poison (the wide path's
+    accumulate launches read C back and write it again: k = 192 and 320 are whole tiles with a last run of 64), A and B are
+    unchanged.  Then the refusals lda < k, ldb < n, ldc < n with C untouched."""
+    import torch
+
+    import phantom_fhe_amd as P
+    batch, start = 2, 2
+    primes = [int(p) for p in O.get_primes(4096, bits, batch + start)]
+    ctx = P.PhantomContext(12, primes, 0, device=gpu)
+    lda, ldb, ldc = k + 3, n + 5, n + 7
+    r = rng_for(151)
+    qs = np.array(primes[start:], dtype=np.uint64)
+    A = np.full((batch, m, lda), GEMM_POISON, dtype=np.uint64)
+    B = np.full((batch, k, ldb), GEMM_POISON, dtype=np.uint64)
+    for z, q in enumerate(primes[start:]):
+        A[z, :, :k] = r.integers(0, q, (m, k), dtype=np.uint64)
+        B[z, :, :n] = r.integers(0, q, (k, n), dtype=np.uint64)
+    A[:, 0, :k] = qs[:, None] - 1                                     # a row and a column of q - 1
+    B[:, :, 0] = qs[:, None] - 1
+    dA, dB = P.to_device(A, gpu), P.to_device(B, gpu)
+    dC = P.to_device(np.full((batch, m, ldc), GEMM_POISON, dtype=np.uint64), gpu)
+    ctx.batched_modular_gemm(dC, dA, dB, m, n, k, batch, mod_start=start, lda=lda, ldb=ldb, ldc=ldc)
+    got = P.to_host(dC)
+    for z, q in enumerate(primes[start:]):
+        want = O.gemm_mod(q, np.ascontiguousarray(A[z, :, :k]), np.ascontiguousarray(B[z, :, :n]))
+        if not np.array_equal(got[z, :, :n], want):
+            i, j = (int(v) for v in np.argwhere(got[z, :, :n] != want)[0])
+            raise AssertionError(f"modulus {start + z} ({q.bit_length()} bits): {int(np.count_nonzero(got[z, :, :n] != want))} words differ, "
+                                 f"first at ({i}, {j}): got {int(got[z, i, j])}, want {int(want[i, j])}")
+    assert (got[:, :, n:] == np.uint64(GEMM_POISON)).all(), "the gemm wrote to the padding of C"
+    assert np.array_equal(P.to_host(dA), A) and np.array_equal(P.to_host(dB), B), "the gemm wrote to an operand"
+    # leading dimensions shorter than the rows are refused before anything is launched
+    keep = dC.clone()
+    for kw in ({"lda": k - 1}, {"ldb": n - 1}, {"ldc": n - 1}):
+        with pytest.raises(ValueError) as e:
+            ctx.batched_modular_gemm(dC, dA, dB, m, n, k, batch, mod_start=start, **{**{"lda": lda, "ldb": ldb, "ldc": ldc}, **kw})
+        assert str(e.value) == "gemm shape is not valid", str(e.value)
+    torch.cuda.synchronize()
+    assert torch.equal(dC, keep), "a refused gemm wrote to C"
+
+
 @pytest.mark.parametrize("name,ibase,obase", [
     ("hyb12_a2", [6, 7], [0, 1, 2, 3, 4, 5]),            # P -> Q (2 inputs)
     ("hyb12_a2", [0, 1, 2, 3, 4, 5], [6, 7]),            # Q -> P

@@ -31,6 +31,9 @@ CONFIGS = {
     "hyb13_b5": (13, [60] + [50] * 9 + [60] * 2, 2),      # 10 data limbs: beta 5 at levels 10 and 9 (short last digit), 4 at level 8
     "hyb14_b6": (14, [60] + [50] * 11 + [60] * 2, 2),     # beta 6 at N = 2^14, a size whose fused mod-up + inner product stops at beta 4
     "hyb16_b5": (16, [60] + [50] * 44 + [60] * 9, 9),     # 45 data limbs in 5 digits of 9 at N = 2^16: the 16-input fused mod-up conversion with 9 live inputs; beta 5 at levels 45 and 37 (one-limb last digit), 4 at level 36
+    # one limb of every width at which the sum kernels change their flush period (tests/test_gpu_sum_widths.py): FP64 limbs of
+    # 50 .. 41 bits, integer limbs of 51 .. 61 bits, the 61-bit primes as the special base
+    "ladder12": (12, [50, 49, 48, 47, 46, 45, 44, 42, 41, 51, 55, 59, 60, 60, 61, 61], 2),
 }
 
 # (config, live data limbs) -> number of key-switch digits, for the sets above
@@ -82,6 +85,39 @@ def uniform_poly(rng, primes, n):
 
 def rng_for(config_id):
     return np.random.default_rng(0x5EED0000 + config_id)
+
+
+def oracle_bfv_plain_sum(oc, m, ct, ql, t, acc=None, upto=None):
+    """The oracle's loop of bfv_multiply_plain and add over the terms of one group (m [K][N] below t, ct [K][2][L][N] in coefficient
+    form), acc added last -- what tests/test_gpu_bfv_plain_sum.py compares with at t = 65537, for any plain modulus; upto: the sums
+    after those term counts instead (without acc)."""
+    s, partial = None, {}
+    for k in range(m.shape[0]):
+        prod = oc.bfv_multiply_plain(ct[k], m[k], t)
+        s = prod if s is None else np.stack([oc.add(s[p], prod[p], ql) for p in range(2)])
+        if upto and k + 1 in upto:
+            partial[k + 1] = s
+    if upto:
+        return partial
+    if acc is not None:
+        s = np.stack([oc.add(acc[p], s[p], ql) for p in range(2)])
+    return s
+
+
+def first_diff_limb(got, ref, what, primes):
+    """Word-for-word comparison of [..., limb, N] arrays over `primes`; a failure names the limb, its bit length and the first
+    differing word."""
+    assert got.shape == ref.shape, f"{what}: shape {got.shape} != {ref.shape}"
+    if np.array_equal(got, ref):
+        return
+    bad = got != ref
+    idx = tuple(int(v) for v in np.argwhere(bad)[0])
+    limbs = sorted({int(j) for j in np.nonzero(bad.any(axis=-1))[-1]})
+    q = int(primes[idx[-2]])
+    msg = (f"{what}: {int(np.count_nonzero(bad))} words differ in limbs {[(j, int(primes[j]).bit_length()) for j in limbs]} (index, bits), "
+           f"first at {idx} (limb {idx[-2]}, q = {q}, {q.bit_length()} bits): got {int(got[idx])}, want {int(ref[idx])}")
+    print(msg)
+    raise AssertionError(msg)
 
 
 def brev(k, bits):
