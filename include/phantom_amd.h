@@ -57,7 +57,7 @@ const char *pha_last_error(void);
  *   environment when the library was first used.  In strict mode the dyadic, tensor, mod-up / inner-product / mod-down, key-switch,
  *   hoisting and BFV multiply entries check ct / c2 / t_mod_up / keys / weights / ct1 and ct2 before they compute (one
  *   synchronising pass per operand; among them pha_keyswitch_mod_switch, pha_keyswitch_mod_switch_batched,
- *   pha_inner_product_relin_mod_switch_batched, pha_hoisting_batched, pha_hoisting_weighted_batched and pha_hoisting_weighted_bsgs_batched) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
+ *   pha_inner_product_relin_mod_switch_batched, pha_hoisting_batched, pha_hoisting_weighted_batched, pha_hoisting_weighted_bsgs_batched, pha_decrypt_phase_batched, pha_bgv_decrypt_batched and pha_bfv_decrypt_batched) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
 int pha_check_canonical(pha_context_t ctx, const uint64_t *data, size_t coeff_modulus_size, size_t start_modulus_idx,
                         size_t size_P_tail, size_t polys, size_t poly_stride, uint64_t *bad_words, void *stream);
 int pha_check_canonical_keys(pha_context_t ctx, size_t size_Ql, const uint64_t *const *keys, size_t n_keys, uint64_t *bad_words,
@@ -712,6 +712,56 @@ int pha_ckks_encode_batched(pha_ckks_encoder_t enc, size_t size_Ql, int with_spe
                             int *bit_counts_host_or_null, void *stream);
 int pha_ckks_decode_batched(pha_ckks_encoder_t enc, size_t size_Ql, const uint64_t *plain, size_t count, size_t plain_stride,
                             double scale, double *values_out, size_t values_stride, void *stream);
+
+/* ---- decryption (PhantomSecretKey::ckks_decrypt / bgv_decrypt / bfv_decrypt, src/secretkey.cu:533-691; DRNSTool::
+ *      hps_decrypt_scale_and_round src/rns.cu:1519-1689 and decrypt_mod_t; csrc/pha_decrypt.hip, arithmetic and bounds in
+ *      csrc/pha_decrypt.h).  All data buffers are DEVICE memory, strides are 64-bit words, L = size_Ql,
+ *      N = the context's degree.  The secret key enters as the array pha_generate_one_kswitch_key takes; sampling a key, encryption
+ *      and public keys are not part of this library.
+ * pha_secret_key_powers (compute_secret_key_array, src/secretkey.cu:196-230): out [max_power][size_QP][N] = s, s^2, ... in NTT form
+ *   over all QP rows, the reference's secret_key_array layout, from sk_ntt [size_QP][N]: power 1 is a copy (out may be sk_ntt's own
+ *   buffer, then nothing is copied), every further power one pha_multiply_rns_poly.
+ * Extension (no reference launcher: the reference decrypts one ciphertext per call with a device copy of c0 and one
+ *   multiply_and_add_rns_poly launch per further polynomial) pha_decrypt_phase_batched: ciphertext b < batch, in NTT form,
+ *   [cipher_size][L][N] at ct + b * ct_stride; dst (b) [L][N] at dst + b * dst_stride = c0 + sum_{i >= 1} c_i (.) s^i, every word the
+ *   canonical residue -- word for word that copy and those launches: ckks_decrypt, and the first half of bgv_decrypt.  sk_powers as
+ *   pha_secret_key_powers writes it (n_powers powers; rows [0, L) of the first cipher_size - 1 are read).  ONE launch: a thread
+ *   keeps the words of s^i in registers across a group of up to 4 ciphertexts.  dst may be ct itself (result b takes c0 (b)'s place;
+ *   dst_stride == ct_stride then), as a caller who is done with the ciphertexts would want.
+ * Extension pha_bgv_decrypt_batched: the same ciphertexts -> dst (b) [N] words below t (bgv_decrypt): per `chunk` ciphertexts
+ *   (0: the default, 8) the phase kernel into a work buffer ([chunk][L][N] words), ONE batched inverse transform in place, and the
+ *   exact conversion to t (exact_convert_array) over the chunk, which multiplies by the inverse of correction_factors[b] mod t in its
+ *   store -- the words of decrypt_mod_t followed by multiply_scalar_rns_poly.  correction_factors: HOST array of `batch` words, NULL
+ *   = all 1 (a factor of 1 multiplies nothing); a factor that is not invertible mod t returns status -2 "invalid correction factor"
+ *   before anything is launched.
+ * Extension pha_bfv_decrypt_batched: ciphertext b in COEFFICIENT form (bfv's form), size_Ql <= |Q| (the leveled ciphertexts of
+ *   hps_overq_leveled included) -> dst (b) [N] = round(t x / Q_l) mod t of the phase x (bfv_decrypt with the HPS scale-and-round).
+ *   Per chunk: c_1 .. c_{k-1} are transformed forward OUT OF PLACE into the work buffer ([chunk][cipher_size - 1][L][N] words; no
+ *   copy, no memset), the phase kernel runs without c0, ONE batched inverse transform adds c0 in its final store, and the
+ *   scale-and-round writes the plaintexts.  The ciphertexts are only read.  One form of the scale-and-round for every width (the
+ *   reference picks one of four kernels by bit counts): differs from the exact rounding only where t x / Q is within L * 2^-14 of a
+ *   half-integer.  Deviation: where the reference stores llround of a value in [0, t) and can write t itself (a plaintext 0 with
+ *   slightly negative noise), this library writes 0 -- only canonical words are written.
+ * Shared by the three batched entries.  Refused (status -1, nothing launched): a null pointer; size_Ql outside 1..|Q|;
+ *   cipher_size < 2 or n_powers < cipher_size - 1; with batch > 1 a ct stride below cipher_size * L * N or a dst stride below the
+ *   size of a result; an odd stride; buffers that are not 16-byte aligned; dst overlapping sk_powers or ct (except dst == ct of the
+ *   phase entry); for the bgv / bfv entries a context without a plain modulus or a level of more than 64 limbs (the scale-and-round's error bound is derived up to there).  batch == 0 does nothing.  No entry synchronises; once
+ *   the work buffer has its size and the level's tables exist (first call) a call can be captured into a graph.  Every `chunk` gives
+ *   the same bits.  Strict mode (pha_set_strict) checks ct and sk_powers, named "<entry> ct" and "<entry> sk_powers" with <entry> =
+ *   decrypt_phase, bgv_decrypt, bfv_decrypt.
+ * pha_hps_decrypt_scale_and_round / pha_decrypt_mod_t: the two DRNSTool launchers on ONE polynomial, src [L][N] in coefficient form,
+ *   canonical -> dst [N]: round(t x / Q_l) mod t, and the exact conversion of x from Q_l to t of exact_convert_array (no correction
+ *   factor).  The words of the batched entries' last step; also refused: dst overlapping src. ---- */
+int pha_secret_key_powers(pha_context_t ctx, const uint64_t *sk_ntt, size_t max_power, uint64_t *out, void *stream);
+int pha_decrypt_phase_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t cipher_size, size_t batch, size_t ct_stride,
+                              const uint64_t *sk_powers, size_t n_powers, uint64_t *dst, size_t dst_stride, void *stream);
+int pha_bgv_decrypt_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t cipher_size, size_t batch, size_t ct_stride,
+                            const uint64_t *sk_powers, size_t n_powers, const uint64_t *correction_factors, uint64_t *dst,
+                            size_t dst_stride, size_t chunk, void *stream);
+int pha_bfv_decrypt_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t cipher_size, size_t batch, size_t ct_stride,
+                            const uint64_t *sk_powers, size_t n_powers, uint64_t *dst, size_t dst_stride, size_t chunk, void *stream);
+int pha_hps_decrypt_scale_and_round(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream);
+int pha_decrypt_mod_t(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream);
 
 #ifdef __cplusplus
 }

@@ -777,6 +777,7 @@ int pha_context_set_plain_modulus(pha_context_t ctx, uint64_t plain_modulus) {
         c.behz_tool.reset();   // (their auxiliary table rows stay; a later tool appends fresh ones)
         c.hps_tool.reset();
         c.hpsq_tools.clear();
+        c.decrypt_tables.clear();
         c.plain_t = plain_modulus;
     }
     PHA_API_END

@@ -249,6 +249,19 @@ struct CkksCompose {
     DevBuf<u64> thresh;          // [size]        (Q + 1) / 2
 };
 
+// ---- decryption at one level (pha_decrypt.hip; the programs and their bounds: pha_decrypt.h): the tables of the BFV scale-and-round
+//      and of the BGV tail (the exact conversion to t), built on first use; needs the plain modulus
+struct DecryptLevel {
+    uint32_t size = 0;
+    int h = 0;                   // the split point of the scale-and-round
+    DModulus t_mod{};
+    DevBuf<double> frac;         // [size][2]
+    DevBuf<u64> itab;            // [size][2]
+    DevBuf<u64x2> hat_inv;       // [size]  qhat_i^-1 mod q_i (+Shoup)
+    DevBuf<u64> mat, q;          // [size]  qhat_i mod t; q_i
+    u64 q_mod_t = 0;
+};
+
 // ---- scratch arena: one per (context, stream), grown on demand, never freed until destroy ----
 struct Arena {
     DevBuf<u64> buf;
@@ -295,6 +308,8 @@ struct Context {
     std::map<uint32_t, std::unique_ptr<HpsQ>> hpsq_tools;   // by |Ql| (|Q| = plain hps_overq)
     std::map<uint32_t, std::unique_ptr<CkksCompose>> ckks_tables;   // by |Ql|; built on first use (pha_ckks.hip)
     CkksCompose &ckks_compose(uint32_t size_ql);
+    std::map<uint32_t, std::unique_ptr<DecryptLevel>> decrypt_tables;   // by |Ql|; built on first use (pha_decrypt.hip), dropped with the plain modulus
+    DecryptLevel &decrypt_level(uint32_t size_ql);
     uint32_t rows = 0;  // table rows = size_qp + auxiliary moduli
     // keyed by (stream handle, host thread): hipStreamPerThread and the null stream are sentinels that name a different
     // real stream (or none) in every host thread, so those two handles get one arena per calling thread

@@ -325,4 +325,54 @@ inline PlainTables plain_tables(const std::vector<u64> &primes, uint32_t size_ql
     return t;
 }
 
+// ---- decryption at one level (pha_decrypt.h) -------------------------------------------------------------------------------------
+// The BFV scale-and-round: h = ceil(bits of the widest q_i / 2); per limb i, with A_i = t [qhat_i^-1]_{q_i} and B_i = t [qhat_i^-1 2^h]_{q_i}
+// as 128-bit integers (t < 2^60, q_i < 2^61: below 2^121), itab [L][2] = floor(A_i / q_i) mod t, floor(B_i / q_i) mod t and frac [L][2]
+// = (A_i mod q_i) / q_i, (B_i mod q_i) / q_i.  A fraction r / q is taken as floor(r 2^64 / q), exact in 128 bits, and converted once:
+// within 2^-64 + 2^-54 < 2^-52 of its true value (no division of two doubles).
+struct DecryptRoundTables {
+    int h = 0;
+    std::vector<double> frac;   // [L][2]
+    std::vector<u64> itab;      // [L][2]
+};
+inline DecryptRoundTables decrypt_round_tables(const std::vector<u64> &primes, uint32_t size_ql, u64 t) {
+    DecryptRoundTables d;
+    const Rows q = row_range(0, size_ql);
+    int bits = 0;
+    for (uint32_t i = 0; i < size_ql; i++) bits = std::max(bits, h_bits(primes[i]));
+    d.h = (bits + 1) / 2;
+    d.frac.resize(2 * (size_t)size_ql);
+    d.itab.resize(2 * (size_t)size_ql);
+    for (uint32_t i = 0; i < size_ql; i++) {
+        const u64 qi = primes[i];
+        const u64 inv = h_invmod(prod_mod(primes, q, qi, i), qi);
+        const u64 both[2] = {inv, h_mulmod(inv, (u64)(((u128)1 << d.h) % qi), qi)};
+        for (int p = 0; p < 2; p++) {
+            const u128 a = (u128)t * both[p];
+            d.itab[2 * i + p] = (u64)((a / qi) % t);
+            const u64 fix = (u64)((((u128)(u64)(a % qi)) << 64) / qi);   // floor(r 2^64 / q_i), r < q_i
+            d.frac[2 * i + p] = (double)fix * 0x1p-64;
+        }
+    }
+    return d;
+}
+// The BGV tail, exact_convert_array to t (src/rns_bconv.cu:374-431, constants src/host/rns.cu:282-337): qhat_i^-1 mod q_i, qhat_i mod t,
+// Q mod t
+struct DecryptModTTables {
+    std::vector<u64x2> hat_inv;   // [L]
+    std::vector<u64> mat;         // [L]
+    u64 q_mod_t = 0;
+};
+inline DecryptModTTables decrypt_mod_t_tables(const std::vector<u64> &primes, uint32_t size_ql, u64 t) {
+    DecryptModTTables d;
+    const Rows q = row_range(0, size_ql);
+    for (uint32_t i = 0; i < size_ql; i++) {
+        const u64 qi = primes[i];
+        d.hat_inv.push_back(h_pair(h_invmod(prod_mod(primes, q, qi, i), qi), qi));
+        d.mat.push_back(prod_mod(primes, q, t, i));
+    }
+    d.q_mod_t = prod_mod(primes, q, t);
+    return d;
+}
+
 }  // namespace pha

@@ -485,6 +485,58 @@ class PhantomContext:
         _lib.check(self._L.pha_bfv_plain_inner_product_batched(self._h, size_Ql, _ptr(plain), _ptr(ct), _ptr(acc), _ptr(res), terms,
                                                                batch, tp, bp, tc, bc, ba, chunk, slab, _stream()))
 
+    # -- decryption (csrc/pha_decrypt.hip; src/secretkey.cu:533-691) -------------------------------------
+    def secret_key_powers(self, sk_ntt, max_power, out=None):
+        """compute_secret_key_array: [max_power][size_QP][N] = s, s^2, ... in NTT form from sk_ntt [size_QP][N] (the array
+        generate_one_kswitch_key takes).  Returns `out` (allocated when None)."""
+        if out is None:
+            out = torch.empty((max(int(max_power), 1), self.size_QP, self.n), dtype=torch.int64, device=self.device)
+        _lib.check(self._L.pha_secret_key_powers(self._h, _ptr(sk_ntt), max_power, _ptr(out), _stream()))
+        return out
+
+    def _decrypt_layout(self, size_Ql, ct, sk_powers, out_words, cipher_size, batch, n_powers, strides):
+        """(cipher_size, batch, ct stride, n_powers, dst stride) of a decrypt call: from ct [batch][cipher_size][L][N] and sk_powers
+        [n_powers][size_QP][N] unless given; strides: (ct, dst) in 64-bit words, None: dense."""
+        batch = int(ct.shape[0]) if batch is None else int(batch)
+        cipher_size = int(ct.shape[1]) if cipher_size is None else int(cipher_size)
+        n_powers = int(sk_powers.shape[0]) if n_powers is None else int(n_powers)
+        cs, ds = (int(v) for v in strides) if strides is not None else (cipher_size * size_Ql * self.n, out_words)
+        return cipher_size, batch, cs, n_powers, ds
+
+    def decrypt_phase_batched(self, size_Ql, ct, sk_powers, dst, cipher_size=None, batch=None, n_powers=None, strides=None):
+        """Extension (ckks; the first half of bgv): dst (b) [L][N] = c0 + sum_i c_i (.) s^i of ciphertext b of ct [batch][cipher_size][L][N]
+        (NTT form) in one launch; sk_powers as secret_key_powers returns it.  dst may be ct itself (result b in c0 (b)'s place, with
+        strides (s, s))."""
+        k, B, cs, npw, ds = self._decrypt_layout(size_Ql, ct, sk_powers, size_Ql * self.n, cipher_size, batch, n_powers, strides)
+        _lib.check(self._L.pha_decrypt_phase_batched(self._h, size_Ql, _ptr(ct), k, B, cs, _ptr(sk_powers), npw, _ptr(dst), ds, _stream()))
+
+    def bgv_decrypt_batched(self, size_Ql, ct, sk_powers, dst, correction_factors=None, cipher_size=None, batch=None, n_powers=None,
+                            strides=None, chunk=0):
+        """Extension (bgv): dst (b) [N] words below t = the decryption of ciphertext b (NTT form): phase, inverse transform, exact
+        conversion to t times the inverse of correction_factors[b] (host integers; None: all 1).  `chunk` ciphertexts per set of
+        launches (0: the library's default) changes no bit."""
+        k, B, cs, npw, ds = self._decrypt_layout(size_Ql, ct, sk_powers, self.n, cipher_size, batch, n_powers, strides)
+        cf = None if correction_factors is None else (C.c_uint64 * max(len(correction_factors), 1))(*[int(f) for f in correction_factors])
+        if cf is not None and len(correction_factors) < B:
+            raise ValueError("correction_factors holds fewer words than the batch")
+        _lib.check(self._L.pha_bgv_decrypt_batched(self._h, size_Ql, _ptr(ct), k, B, cs, _ptr(sk_powers), npw, cf, _ptr(dst), ds, chunk,
+                                                   _stream()))
+
+    def bfv_decrypt_batched(self, size_Ql, ct, sk_powers, dst, cipher_size=None, batch=None, n_powers=None, strides=None, chunk=0):
+        """Extension (bfv): dst (b) [N] = round(t x / Q_l) mod t of the phase x of ciphertext b (COEFFICIENT form, only read): one
+        forward transform of c_1 .. c_{k-1} per chunk, the phase without c0, one inverse transform that adds c0, the scale-and-round."""
+        k, B, cs, npw, ds = self._decrypt_layout(size_Ql, ct, sk_powers, self.n, cipher_size, batch, n_powers, strides)
+        _lib.check(self._L.pha_bfv_decrypt_batched(self._h, size_Ql, _ptr(ct), k, B, cs, _ptr(sk_powers), npw, _ptr(dst), ds, chunk,
+                                                   _stream()))
+
+    def hps_decrypt_scale_and_round(self, size_Ql, dst, src):
+        """DRNSTool::hps_decrypt_scale_and_round (src/rns.cu:1519-1689): src [L][N] (coefficient form) -> dst [N] = round(t x / Q_l) mod t."""
+        _lib.check(self._L.pha_hps_decrypt_scale_and_round(self._h, size_Ql, _ptr(dst), _ptr(src), _stream()))
+
+    def decrypt_mod_t(self, size_Ql, dst, src):
+        """DRNSTool::decrypt_mod_t: src [L][N] (coefficient form) -> dst [N], the exact conversion to the plain modulus."""
+        _lib.check(self._L.pha_decrypt_mod_t(self._h, size_Ql, _ptr(dst), _ptr(src), _stream()))
+
     def bfv_multiply_behz(self, ct1, ct2, dst):
         """bfv_multiply_behz (src/evaluate.cu:447-548): [2][Q][N] x [2][Q][N] -> [3][Q][N], coefficient form."""
         _lib.check(self._L.pha_bfv_multiply_behz(self._h, _ptr(ct1), _ptr(ct2), _ptr(dst), _stream()))

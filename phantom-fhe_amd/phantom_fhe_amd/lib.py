@@ -149,6 +149,13 @@ _SIGS = {
     "pha_compose_array": [vp, sz, vp, vp, C.c_double, vp],
     "pha_ckks_encode_batched": [vp, sz, C.c_int, vp, sz, sz, sz, C.c_double, vp, sz, C.POINTER(C.c_int), vp],
     "pha_ckks_decode_batched": [vp, sz, vp, sz, sz, C.c_double, vp, sz, vp],
+    # decryption (csrc/pha_decrypt.hip)
+    "pha_secret_key_powers": [vp, vp, sz, vp, vp],
+    "pha_decrypt_phase_batched": [vp, sz, vp, sz, sz, sz, vp, sz, vp, sz, vp],
+    "pha_bgv_decrypt_batched": [vp, sz, vp, sz, sz, sz, vp, sz, u64p, vp, sz, sz, vp],
+    "pha_bfv_decrypt_batched": [vp, sz, vp, sz, sz, sz, vp, sz, vp, sz, sz, vp],
+    "pha_hps_decrypt_scale_and_round": [vp, sz, vp, vp, vp],
+    "pha_decrypt_mod_t": [vp, sz, vp, vp, vp],
     # include/phantom_amd_bench.h (measurement hooks)
     "pha_time_forward_ntt": [vp, vp, sz, C.c_int, vp, C.POINTER(C.c_float)],
     "pha_repeat_forward_ntt_batched": [vp, vp, sz, sz, sz, sz, C.c_int, vp],

@@ -90,6 +90,19 @@ def encode_diagonals(encoder, size_Ql, matrix, scale, steps=None):
     return out
 
 
+def decrypt_decode_batch(ctx, encoder, cts, level, scale, sk_powers):
+    """The exit side of the pipeline for a batch of ckks ciphertexts cts [B][k][level][N] (NTT form, `level` data limbs): the phase
+    of every ciphertext under sk_powers (PhantomContext.secret_key_powers) in one launch, then one batched decode
+    (CKKSEncoder.decode_batched) at `scale`; the plaintexts stay on the device between the two.  Returns [B][N / 2] complex128."""
+    B = cts.shape[0]
+    values = torch.empty((B, encoder.slot_count), dtype=torch.complex128, device=ctx.device)
+    if B:
+        plain = torch.empty((B, level, ctx.n), dtype=torch.int64, device=ctx.device)
+        ctx.decrypt_phase_batched(level, cts.contiguous(), sk_powers, plain)
+        encoder.decode_batched(level, plain, scale, values)
+    return values
+
+
 def diag_matvec(ctx, size_Ql, ct, galois_elts, galois_keys, diagonals, scheme):
     """One block of config 5: out = sum_k diagonals[k] (.) rotate_{galois_elts[k]}(ct) (Halevi-Shoup diagonal
     form), all rotations hoisted behind one mod-up and one mod-down (pha_hoisting_weighted).  diagonals[k] is the
