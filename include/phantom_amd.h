@@ -57,7 +57,9 @@ const char *pha_last_error(void);
  *   environment when the library was first used.  In strict mode the dyadic, tensor, mod-up / inner-product / mod-down, key-switch,
  *   hoisting and BFV multiply entries check ct / c2 / t_mod_up / keys / weights / ct1 and ct2 before they compute (one
  *   synchronising pass per operand; among them pha_keyswitch_mod_switch, pha_keyswitch_mod_switch_batched,
- *   pha_inner_product_relin_mod_switch_batched, pha_hoisting_batched, pha_hoisting_weighted_batched, pha_hoisting_weighted_bsgs_batched, pha_decrypt_phase_batched, pha_bgv_decrypt_batched and pha_bfv_decrypt_batched) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
+ *   pha_inner_product_relin_mod_switch_batched, pha_hoisting_batched, pha_hoisting_weighted_batched, pha_hoisting_weighted_bsgs_batched, pha_decrypt_phase_batched, pha_bgv_decrypt_batched, pha_bfv_decrypt_batched, pha_encrypt_zero_symmetric_batched,
+ *   pha_public_key_generate, pha_encrypt_symmetric_batched and pha_encrypt_asymmetric_batched, which also count sample words of
+ *   magnitude above 2^16) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
 int pha_check_canonical(pha_context_t ctx, const uint64_t *data, size_t coeff_modulus_size, size_t start_modulus_idx,
                         size_t size_P_tail, size_t polys, size_t poly_stride, uint64_t *bad_words, void *stream);
 int pha_check_canonical_keys(pha_context_t ctx, size_t size_Ql, const uint64_t *const *keys, size_t n_keys, uint64_t *bad_words,
@@ -716,8 +718,8 @@ int pha_ckks_decode_batched(pha_ckks_encoder_t enc, size_t size_Ql, const uint64
 /* ---- decryption (PhantomSecretKey::ckks_decrypt / bgv_decrypt / bfv_decrypt, src/secretkey.cu:533-691; DRNSTool::
  *      hps_decrypt_scale_and_round src/rns.cu:1519-1689 and decrypt_mod_t; csrc/pha_decrypt.hip, arithmetic and bounds in
  *      csrc/pha_decrypt.h).  All data buffers are DEVICE memory, strides are 64-bit words, L = size_Ql,
- *      N = the context's degree.  The secret key enters as the array pha_generate_one_kswitch_key takes; sampling a key, encryption
- *      and public keys are not part of this library.
+ *      N = the context's degree.  The secret key enters as the array pha_generate_one_kswitch_key takes; encryption and public keys
+ *      are the next section; sampling (the PRNG of src/prng.cu) is not part of this library.
  * pha_secret_key_powers (compute_secret_key_array, src/secretkey.cu:196-230): out [max_power][size_QP][N] = s, s^2, ... in NTT form
  *   over all QP rows, the reference's secret_key_array layout, from sk_ntt [size_QP][N]: power 1 is a copy (out may be sk_ntt's own
  *   buffer, then nothing is copied), every further power one pha_multiply_rns_poly.
@@ -762,6 +764,53 @@ int pha_bfv_decrypt_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *c
                             const uint64_t *sk_powers, size_t n_powers, uint64_t *dst, size_t dst_stride, size_t chunk, void *stream);
 int pha_hps_decrypt_scale_and_round(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream);
 int pha_decrypt_mod_t(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream);
+
+/* ---- encryption (PhantomSecretKey::encrypt_zero_symmetric / gen_publickey / encrypt_symmetric, PhantomPublicKey::
+ *      encrypt_zero_asymmetric / encrypt_asymmetric, src/secretkey.cu:11-192, 232-295, 382-395, 463-531; csrc/pha_encrypt.hip,
+ *      arithmetic and bounds in csrc/pha_encrypt.h) for BATCHES of ciphertexts.  All data buffers are DEVICE
+ *      memory, strides are 64-bit words, l = size_Ql, N = the context's degree, k = t for bgv and 1 otherwise.  Randomness is the
+ *      caller's, as pha_generate_one_kswitch_key takes it; the PRNG (src/prng.cu) is not part of this library.
+ * Samples: a sampled polynomial (the noise e, the ternary u) is [N] SIGNED 64-bit words in two's complement, |v| <= 2^16 (the
+ *   reference's samplers give |v| <= 21), ONE polynomial shared by every limb: each limb lifts it modulo its own prime as it is
+ *   loaded, the [L][N] residue form is never written.  The entries refuse a context that has a prime below 2^17 among the rows used.
+ * The uniform a: canonical words [rows][N] ALREADY in c1's place in the output buffer, taken as NTT-form as the reference samples it
+ *   (c1 is its own input; no copy).
+ * pha_encrypt_zero_symmetric_batched: ct (b) at ct + b * ct_stride is [2][rows][N], rows = [0, l), or [0, l) u P with with_special
+ *   (the encoder's row convention); sk_ntt [size_QP][N]; e (b) [N] at e + b * e_stride.  On exit, ntt_form != 0: (c0, c1) =
+ *   (-(a (.) s + NTT(k e)), a), c1 untouched -- ONE forward transform per ciphertext whose load lifts the samples and whose store
+ *   forms the product and the sum; ntt_form == 0: (-(iNTT(a (.) s) + e), iNTT(a)), c1 replaced by its inverse transform (bfv's form).
+ * pha_public_key_generate (gen_publickey): the same at size_Ql = |Q|, with_special = 1, ntt_form = 1, count = 1: pk [2][size_QP][N]
+ *   holds a in its second half on entry.
+ * pha_encrypt_symmetric_batched (encrypt_symmetric): ckks: plain (b) [l][N] in NTT form (what pha_ckks_encode_batched writes), added
+ *   in the same store; bgv: plain (b) [N] words below t, c0 += NTT(m mod q_i); bfv: plain (b) [N] words below t, coefficient form,
+ *   then multiply_add_plain_with_scaling_variant.  plain_stride 0 shares one plaintext.  Extension: the reference encrypts bgv / bfv
+ *   at the first data level only; any size_Ql in 1..|Q| is accepted here (the per-level constants of pha_bfv_add_plain).
+ * pha_encrypt_asymmetric_batched (encrypt_asymmetric): pk [2][size_QP][N] in NTT form, u (b) [N] at u + b * u_stride, e (b) [2][N] at
+ *   e + b * e_stride; over rows [0, l) u P: NTT form c_j = pk_j (.) NTT(u) + NTT(k e_j), bfv c_j = iNTT(pk_j (.) NTT(u)) + e_j; then
+ *   DRNSTool::moddown of tool (ctx, size_Ql) on each polynomial and the plaintext step above: ct (b) [2][l][N].  At the top data
+ *   level this is word for word the reference.  Extension: below it the reference cannot be followed (src/secretkey.cu:106-121 indexes
+ *   a level that has dropped one data prime and no special primes and runs the first level's mod-down on it: "use it with caution when
+ *   chain_index != 0"); lower levels are defined here by the same construction over Q_l u P.  `chunk` ciphertexts run per set of
+ *   launches (0: the default, 8); the work buffer ([chunk] (5 l + 3 |P|) N words, and chunk * l * N more under bgv) comes from the
+ *   context's arena.  Every `chunk` gives the same bits.
+ * Shared.  Refused (status -1, nothing launched): a null pointer; size_Ql outside 1..|Q|; a prime below 2^17; with_special or the
+ *   asymmetric entry on a context without special primes; an unknown scheme; bgv / bfv on a context without a plain modulus;
+ *   count > 65535; with count > 1 a ct stride below the size of a ciphertext or a sample / plaintext stride below the size of an
+ *   element (a plain_stride of 0 excepted); an odd stride; buffers that are not 16-byte aligned; ct overlapping an input.
+ *   count == 0 does nothing.  No entry synchronises; once the work buffer has its size and the level's tables exist (first call) a call
+ *   can be captured into a graph.  Strict mode (pha_set_strict) checks the key, the words of a found in ct, the plaintext and the
+ *   sample range, named "<entry> sk", "<entry> pk", "<entry> a", "<entry> plain" and "<entry> samples" with <entry> =
+ *   encrypt_zero_symmetric (pha_public_key_generate too), encrypt_symmetric, encrypt_asymmetric. ---- */
+int pha_encrypt_zero_symmetric_batched(pha_context_t ctx, size_t size_Ql, int with_special, const uint64_t *sk_ntt, const uint64_t *e,
+                                       size_t e_stride, uint64_t *ct, size_t ct_stride, size_t count, int scheme, int ntt_form,
+                                       void *stream);
+int pha_public_key_generate(pha_context_t ctx, const uint64_t *sk_ntt, const uint64_t *e, uint64_t *pk, int scheme, void *stream);
+int pha_encrypt_symmetric_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *sk_ntt, const uint64_t *e, size_t e_stride,
+                                  const uint64_t *plain, size_t plain_stride, uint64_t *ct, size_t ct_stride, size_t count, int scheme,
+                                  void *stream);
+int pha_encrypt_asymmetric_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *pk, const uint64_t *u, size_t u_stride,
+                                   const uint64_t *e, size_t e_stride, const uint64_t *plain, size_t plain_stride, uint64_t *ct,
+                                   size_t ct_stride, size_t count, int scheme, size_t chunk, void *stream);
 
 #ifdef __cplusplus
 }

@@ -411,6 +411,14 @@ struct NttExtra {
     uint32_t excl_step = 0;                              // polynomial z skips [excl_start + z*step, min(+len, limit))
     uint32_t excl_limit = 0xffffffffu;
     uint32_t excl_mod = 0;                               // != 0: the skipped range follows z % excl_mod (batches of ciphertexts)
+    // encryption (pha_encrypt.hip).  pro_small: the words of pro_src are signed samples |v| <= 2^16, lifted (times pro_small_k when
+    // != 0, bgv's t) modulo each limb's prime as they are loaded (PRO_SMALL); goes with EPI_FWD_CANON and the two mul-add epilogues.
+    // EPI_FWD_MULADD / EPI_FWD_NEG_MULADD: aux and aux2 are the factors, aux3 the optional plaintext, all indexed by buffer limb;
+    // polynomial z reads them at z * muladd_stride[0 .. 2], taken as they are (0: one operand shared by every polynomial)
+    bool pro_small = false;
+    u64 pro_small_k = 0;
+    const u64 *aux3 = nullptr;
+    size_t muladd_stride[3] = {0, 0, 0};
 };
 void ntt_forward(Context &c, const u64 *in, u64 *mid, u64 *out, const LimbSel &sel, int epi, const NttExtra &x,
                  hipStream_t s);

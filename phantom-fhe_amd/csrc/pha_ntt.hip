@@ -61,7 +61,11 @@ struct NttKArgs {
     const u64 *scale_shoup;  // [limb] or null
     const u64 *aux;          // fuse_moddown: cx base
     const u64 *aux2;         // EPI_FWD_KSRESCALE: ct base; scale2 / scale2_shoup [limb]: PInv
-    const u64 *scale2, *scale2_shoup;
+    union {
+        const u64 *scale2;
+        const u64 *aux3;     // EPI_FWD_NEG_MULADD (which has no scale2): the plaintext's base, or null
+    };
+    const u64 *scale2_shoup;
     size_t aux2_stride;
     LimbSel sel;
     uint32_t log_n;
@@ -84,10 +88,25 @@ struct NttKArgs {
     uint32_t zfast_tiles;    // 0 = plain 3-D grid (tile, limb, polynomial); else tiles per limb of the 1-D form
     uint32_t zfast_run;      // tiles of one polynomial that run back to back before the next polynomial's (a multiple of 8)
     bool pro_ckks;           // the prologue is CKKS round-and-reduce instead (PRO_CKKS kernels): pro_src holds doubles
-    u64 pro_t;               // != 0: the prologue is the BFV plain lift instead (PRO_LIFT kernels): pro_src holds words below pro_t
-    size_t aux_pair_stride;  // EPI_INV_CANON_ADD: polynomial z adds aux + (z / 2) * aux_pair_stride + (z % 2) * aux_stride (acc of group z / 2)
+    bool pro_small;          // the prologue is the sample lift instead (PRO_SMALL kernels, encryption): pro_src holds signed words |v| <= 2^16
+    union {
+        u64 pro_t;           // != 0 (not pro_small): the prologue is the BFV plain lift instead (PRO_LIFT kernels): pro_src holds words below pro_t
+        u64 pro_k;           // pro_small: != 0: the lifted sample is multiplied by this factor (bgv's t), reduced per limb
+    };
+    union {
+        size_t aux_pair_stride;  // EPI_INV_CANON_ADD: polynomial z adds aux + (z / 2) * aux_pair_stride + (z % 2) * aux_stride (acc of group z / 2)
+        size_t aux3_stride;      // EPI_FWD_NEG_MULADD: polynomial z reads aux3 + z * aux3_stride (and aux, aux2 at z * aux_stride, z * aux2_stride, 0 = shared)
+    };
     const u64 *h_primes;     // HOST copy of the context's primes (launchers only: which limbs run on the FP64 back end)
 };
+// (The encryption launches added no field behind h_primes: a longer NttKArgs moves the kernels' second argument, and every kernel of
+//  this file then differs from its earlier build.  Their flag sits in the padding behind pro_ckks; their third operand, its stride and
+//  the sample factor share the storage of fields no such launch reads -- the anonymous unions above.)
+// The plain modulus of the BFV plain lift, 0 where the launch has none.  The HOST reads pro_t through this alone: under pro_small the
+// word is the sample factor (bgv: t != 0), which must never select a PRO_LIFT kernel.  (The device reads k.pro_t once, in
+// full_tile_args, for operands that only the PRO_LIFT kernels use; scale2 is read under EPI_FWD_KSRESCALE only, which pro_small excludes.)
+static inline u64 lift_t(const NttKArgs &k) { return k.pro_small ? 0 : k.pro_t; }
+static_assert(sizeof(NttKArgs) == 296,"NttKArgs is a kernel argument in front of another: its size is part of every kernel's code");
 
 // Per-tile arguments of limb `twr` (absolute limb index in the buffer), tile `tile`.
 template <bool FWD, int EPI, bool FOLD>
@@ -131,6 +150,13 @@ __device__ __forceinline__ void tile_args(const NttKArgs &k, uint32_t twr, uint3
         a.scale2.y = k.scale2_shoup[twr];
         a.aux2 = k.aux2 + (size_t)twr * n;
     }
+    if (muladd_epilogue(EPI)) {   // the factors and the plaintext are indexed by buffer limb, like out
+        a.aux = k.aux + (size_t)twr * n;
+        a.aux2 = k.aux2 + (size_t)twr * n;
+        a.aux3 = k.aux3 ? k.aux3 + (size_t)twr * n : nullptr;
+        a.ratio0 = k.mod[prime].ratio0;
+        a.ratio1 = k.mod[prime].ratio1;
+    }
 }
 
 // polynomial z skips its own digit: the limbs [excl_start + z*step, min(that + len, limit))  (ntt_modup.cu:422).  The one statement of
@@ -154,13 +180,21 @@ __device__ __forceinline__ void full_tile_args(const NttKArgs &k, uint32_t twr, 
         if (EPI == EPI_FWD_KSRESCALE) a.aux2 += (size_t)z * k.aux2_stride;
     }
     if (EPI == EPI_INV_CANON_ADD) a.aux += (size_t)(z >> 1) * k.aux_pair_stride + (size_t)(z & 1) * k.aux_stride;
+    if (muladd_epilogue(EPI)) {   // (the strides as the caller gave them: 0 shares an operand between the polynomials)
+        a.aux += (size_t)z * k.aux_stride;
+        a.aux2 += (size_t)z * k.aux2_stride;
+        if (a.aux3) a.aux3 += (size_t)z * k.aux3_stride;
+    }
     if (FWD && (C::STRIDED || C::WHOLE) && k.pro_src) {  // rescale prologue: transform (the last limb of polynomial z) mod this prime
         const uint32_t prime = twr >= k.sel.remap_from ? twr + k.sel.remap_add : twr;
         a.in = k.pro_src + (size_t)z * k.pro_stride;
         a.pro_reduce = true;
         a.pro_ratio1 = k.mod[prime].ratio1;
-        a.pro_half = bfv_lift_threshold(k.pro_t);   // (read by the PRO_LIFT kernels only)
+        a.pro_half = bfv_lift_threshold(k.pro_t);   // (read by the PRO_LIFT kernels only; under pro_small the word is pro_k and these two are dead)
         a.pro_inc = bfv_lift_increment(a.q, k.pro_t);
+        a.pro_k = k.pro_k;   // (read by the PRO_SMALL kernels only, as the Barrett ratio; plain loads, so that the other kernels drop them)
+        a.ratio0 = k.mod[prime].ratio0;
+        a.ratio1 = a.pro_ratio1;
     }
 }
 
@@ -358,7 +392,7 @@ static void dispatch_epi(int epi, F &&f) {
 template <class F>
 static void dispatch_pro(const NttKArgs &k, F &&f) {
     if (k.pro_ckks) f(ProC<PRO_CKKS>{});
-    else if (k.pro_t) f(ProC<PRO_LIFT>{});
+    else if (lift_t(k)) f(ProC<PRO_LIFT>{});
     else f(ProC<PRO_NONE>{});
 }
 
@@ -375,6 +409,15 @@ static void launch_whole(NttKArgs k, int epi, hipStream_t s) {
     k.t2 = W::T;
     k.mid = k.out;
     if constexpr (FWD) {
+        if (k.pro_small) {   // encryption: the sample lift with the canonical or a mul-add epilogue, prologue and epilogue in one kernel
+            if constexpr (W::LOGT <= 13) {   // (the product's one-workgroup plans; ntt_transform sends N = 2^14 through two passes)
+                if (epi == EPI_FWD_MULADD) return launch_pass<W, true, EPI_FWD_MULADD, false, PRO_SMALL>(k, s);
+                if (epi == EPI_FWD_NEG_MULADD) return launch_pass<W, true, EPI_FWD_NEG_MULADD, false, PRO_SMALL>(k, s);
+                return launch_pass<W, true, EPI_FWD_CANON, false, PRO_SMALL>(k, s);
+            } else {
+                throw std::logic_error("ntt_forward: the sample lift has no one-workgroup form at this degree");
+            }
+        }
         dispatch_epi<true>(epi, [&](auto e) {
             if constexpr (e() == EPI_FWD_CANON) dispatch_pro(k, [&](auto p) { launch_pass<W, true, EPI_FWD_CANON, false, p()>(k, s); });
             else launch_pass<W, true, e(), false>(k, s);
@@ -479,9 +522,22 @@ static void forward_impl(const NttKArgs &k_in, int epi, hipStream_t s, Context *
     // plan choice that disagrees with it would transform garbage silently (the inverse's second_pass_only has the same guard)
     if (k.first_pass_done && !(LOGN == 16 && VARIANT == 10 && P1::LOGT == 6))
         throw std::logic_error("ntt_forward: first_pass_done needs the 64 x 1024 plan the fused conversion wrote");
+    if (k.pro_small) {
+        // encryption: the sample lift is the load of the strided pass, the canonical or a mul-add epilogue the store of the contiguous
+        // one; both plain passes, on ONE plan per degree (ntt_transform resolves these launches to plan 3), so that the library holds
+        // one pair of new kernels per degree
+        if constexpr (VARIANT == 3) {
+            launch_pass<P1, true, EPI_NONE, false, PRO_SMALL>(k1, s);
+            if (epi == EPI_FWD_MULADD) return launch_pass<P2, true, EPI_FWD_MULADD, false>(k, s);
+            if (epi == EPI_FWD_NEG_MULADD) return launch_pass<P2, true, EPI_FWD_NEG_MULADD, false>(k, s);
+            return launch_pass<P2, true, EPI_FWD_CANON, false>(k, s);
+        } else {
+            throw std::logic_error("ntt_forward: the sample lift runs on plan 3");
+        }
+    }
 #if defined(PHA_EXPERIMENTS)
     if constexpr (T::ONE_LAUNCH) {
-        if (fused && epi != EPI_FWD_KSRESCALE && !k.first_pass_done && !k.pro_t && !k.pro_ckks) {   // both passes in one launch
+        if (fused && epi != EPI_FWD_KSRESCALE && !k.first_pass_done && !lift_t(k) && !k.pro_ckks && !k.pro_small) {   // both passes in one launch
             bool done = false;
             dispatch_epi<true>(epi, [&](auto e) {
                 if constexpr (e() != EPI_FWD_KSRESCALE) done = launch_fused<P1, P2, true, e(), false>(*fused, k1, k, s);
@@ -590,6 +646,14 @@ static NttKArgs make_args(Context &c, const u64 *in, u64 *mid, u64 *out, const L
     k.pro_t = fwd && x.pro_src ? x.pro_lift_t : 0;
     k.pro_ckks = fwd && x.pro_src && x.pro_ckks;
     k.aux_pair_stride = x.aux_pair_stride;
+    k.pro_small = fwd && x.pro_src && x.pro_small;
+    if (k.pro_small) {   // encryption: the fields these launches share with others (see NttKArgs), and the strides as they are given
+        k.pro_k = x.pro_small_k;
+        k.aux3 = x.aux3;
+        k.aux_stride = x.muladd_stride[0];
+        k.aux2_stride = x.muladd_stride[1];
+        k.aux3_stride = x.muladd_stride[2];
+    }
     return k;
 }
 
@@ -676,9 +740,18 @@ static void ntt_transform(Context &c, const u64 *in, u64 *mid, u64 *out, const L
     if (sel.count == 0) return;
     check_sel(c, sel);
     NttKArgs k = make_args(c, in, mid, out, sel, x, FWD);
-    if ((k.pro_t || k.pro_ckks) && (epi != EPI_FWD_CANON || x.first_pass_done || (k.pro_t && k.pro_ckks)))
+    if ((lift_t(k) || k.pro_ckks) && (epi != EPI_FWD_CANON || x.first_pass_done || (lift_t(k) && k.pro_ckks)))
         throw std::logic_error("ntt_forward: the plain lift and the CKKS round-and-reduce go with the plain forward transform only, one at a time");
-    const ResolvedPlan r = choose_plan(c, sel, x);
+    if (muladd_epilogue(epi) && !(FWD && k.pro_small)) throw std::logic_error("ntt_forward: the mul-add epilogues go with the sample lift");
+    if (k.pro_small && (x.pro_lift_t || x.pro_ckks || x.scale2 || x.aux_pair_stride || x.first_pass_done || x.first_pass_only || (epi != EPI_FWD_CANON && !muladd_epilogue(epi))))
+        throw std::logic_error("ntt_forward: the sample lift goes with the canonical and the mul-add epilogues of the plain forward transform, alone");
+    if (muladd_epilogue(epi) && !(x.aux && x.aux2)) throw std::logic_error("ntt_forward: the mul-add epilogues need both factors");
+    ResolvedPlan r = choose_plan(c, sel, x);
+    if (k.pro_small && r.whole > 13) r.whole = 0;
+    if (k.pro_small && !r.whole) {   // a prologue takes the plain passes (as plan_zloop declines pro_src), here on plan 3 at every size
+        r.variant = 3;
+        r.zfast = r.one_launch = false;
+    }
     k.zfast_tiles = r.zfast ? 1u : 0u;   // request: launch_pass turns it into the tile count of the contiguous pass
     dispatch_plan(r, [&](auto logn, auto variant) {
         if constexpr (variant() == kWholePlan) launch_whole<typename WholePlanOf<logn()>::type, FWD>(k, epi, s);

@@ -25,6 +25,7 @@
 #include "pha_arith.h"
 #include "pha_bfv_lift.h"
 #include "pha_ckks_fft.h"
+#include "pha_encrypt.h"
 
 namespace pha {
 
@@ -42,7 +43,11 @@ enum Epilogue {
     // (rns_bconv.cu:763-769) and the rescale epilogue (rns.cu:1141-1158) of key switch + rescale in one (pha_keyswitch_rescale)
     EPI_FWD_KSRESCALE = 6,
     EPI_INV_CANON_ADD = 7,    // inverse: out = acc + iNTT(.), canonical (the one inverse of a BFV plaintext-weighted sum, pha_plain.hip); aux = acc
+    // forward: the product of two NTT-form operands added to the transform in its final store (pha_encrypt.h; encryption):
+    EPI_FWD_MULADD = 8,       //   out = aux (.) aux2 + NTT(.)               (asymmetric: aux = pk_j, aux2 = NTT(u))
+    EPI_FWD_NEG_MULADD = 9,   //   out = -(aux (.) aux2 + NTT(.)) [+ aux3]   (symmetric: aux = the ciphertext's own c1, aux2 = the key, aux3 = the ckks plaintext)
 };
+constexpr bool muladd_epilogue(int epi) { return epi == EPI_FWD_MULADD || epi == EPI_FWD_NEG_MULADD; }
 
 // Load prologues of a transform's first pass that are chosen at compile time (PassProgram's PRO).  PRO_NONE keeps the run-time
 // rescale prologue (PassArgs::pro_reduce) and is what every instantiation from before the BFV plain lift is.
@@ -51,6 +56,8 @@ enum Prologue {
     PRO_LIFT = 1,   // forward: `in` holds words below t; each becomes its centred lift modulo this limb's prime (pha_bfv_lift.h)
     PRO_CKKS = 2,   // forward: `in` holds doubles (CKKS coefficients of magnitude below 2^63); each is rounded and reduced modulo this
                     // limb's prime (pha_ckks_fft.h ckks_round_reduce64), so the decomposed form [L][N] is never written
+    PRO_SMALL = 3,  // forward: `in` holds signed 64-bit samples |v| <= 2^16 (noise, ternary); each becomes [k v] modulo this limb's prime,
+                    // k = 1 or the limb's PassArgs::pro_k (pha_encrypt.h), so the expanded form [L][N] is never written
 };
 
 // Round schedule of one pass: LOGT stages split into NR rounds of R0,R1,R2 stages (forward order).
@@ -140,6 +147,11 @@ struct PassArgs {
     bool pro_reduce;
     u64 pro_ratio1;    // floor(2^64 / q)
     u64 pro_half, pro_inc;   // PRO_LIFT: (t + 1) / 2 and q - t
+    // encryption (pha_encrypt.h).  PRO_SMALL: pro_k = the factor k (any word; reduced per limb), 0 = none; the mul-add epilogues: aux3 = the plaintext's limb
+    // base or null; both: the Barrett ratio of q
+    u64 pro_k;
+    u64 ratio0, ratio1;
+    const u64 *aux3;
 };
 
 template <class C>
@@ -347,7 +359,7 @@ PHA_HD void gs_round(u64 *v, const u64x2 *t, u64 q4, u64 nq, u64x2 ninv, u64x2 w
 // the operands are canonical words below 2^50, every product is an exact fp_mulmod_light (inputs below 2.4 q), and one fp_to_canon
 // ends it -- the same residues, bit for bit.
 constexpr bool fp_epilogue(int epi) {
-    return epi == EPI_FWD_MODDOWN || epi == EPI_FWD_MODDOWN_ADD || epi == EPI_FWD_KSRESCALE || epi == EPI_INV_SCALE;
+    return epi == EPI_FWD_MODDOWN || epi == EPI_FWD_MODDOWN_ADD || epi == EPI_FWD_KSRESCALE || epi == EPI_INV_SCALE || muladd_epilogue(epi);
 }
 template <int EPI>
 PHA_HD u64 apply_epilogue_fp(u64 x, const PassArgs &a, u64 aux, u64 acc) {
@@ -383,8 +395,26 @@ PHA_HD u64 apply_epilogue_v(u64 x, const PassArgs &a, u64 aux, u64 acc) {
     return x;
 }
 
+// the mul-add epilogues of the encryption entries (pha_encrypt.h has the arithmetic and the FP64 form's bounds): x as the last round
+// left it (a lazy integer below 8 q, or the FP64 back end's lazy double), f0 / f1 the words of the two factors, p the plaintext's word
+template <int EPI>
+PHA_HD u64 apply_epilogue_muladd(u64 x, const PassArgs &a, u64 f0, u64 f1, u64 p) {
+    constexpr bool NEG = EPI == EPI_FWD_NEG_MULADD;
+    const bool has_p = NEG && a.aux3 != nullptr;   // (uniform)
+    if (a.fp) {                                     // (uniform)
+        MulAddNoProbe probe;
+        return muladd_fp<NEG>(as_f64(x), f0, f1, has_p, p, a.fpm, probe);
+    }
+    const u64 q = a.q;
+    return muladd_int<NEG>(csub(csub(csub(x, q << 2), q << 1), q), f0, f1, has_p, p, DModulus{q, a.ratio0, a.ratio1});
+}
+
 template <int EPI>
 PHA_HD u64 apply_epilogue(u64 x, const PassArgs &a, size_t gi) {
+    if constexpr (muladd_epilogue(EPI)) {
+        const bool has_p = EPI == EPI_FWD_NEG_MULADD && a.aux3 != nullptr;
+        return apply_epilogue_muladd<EPI>(x, a, a.aux[gi], a.aux2[gi], has_p ? a.aux3[gi] : 0);
+    }
     u64 aux = 0, acc = 0;
     if (EPI == EPI_FWD_MODDOWN || EPI == EPI_FWD_MODDOWN_ADD || EPI == EPI_FWD_KSRESCALE || EPI == EPI_INV_CANON_ADD) aux = a.aux[gi];
     if (EPI == EPI_FWD_MODDOWN_ADD) acc = a.out[gi];
@@ -635,6 +665,16 @@ PHA_HD void round_out(const PassArgs &a, u64 *lds, int tid, const u64 *reg) {
                 u64x2 *p = reinterpret_cast<u64x2 *>(a.out + g0);
 #pragma unroll
                 for (int k = 0; k < K; k += 2) {
+                    if constexpr (muladd_epilogue(EPI)) {
+                        const bool has_p = EPI == EPI_FWD_NEG_MULADD && a.aux3 != nullptr;   // (uniform)
+                        const u64x2 f0 = reinterpret_cast<const u64x2 *>(a.aux + g0)[k >> 1], f1 = reinterpret_cast<const u64x2 *>(a.aux2 + g0)[k >> 1];
+                        const u64x2 pl = has_p ? reinterpret_cast<const u64x2 *>(a.aux3 + g0)[k >> 1] : u64x2{0, 0};
+                        u64x2 t;
+                        t.x = apply_epilogue_muladd<EPI>(rg[k], a, f0.x, f1.x, pl.x);
+                        t.y = apply_epilogue_muladd<EPI>(rg[k + 1], a, f0.y, f1.y, pl.y);
+                        gstore2<false>(p + (k >> 1), t);
+                        continue;
+                    }
                     u64x2 aux{0, 0}, acc{0, 0};
                     if (EPI == EPI_FWD_MODDOWN || EPI == EPI_FWD_MODDOWN_ADD || EPI == EPI_FWD_KSRESCALE || EPI == EPI_INV_CANON_ADD)
                         aux = reinterpret_cast<const u64x2 *>(a.aux + g0)[k >> 1];
@@ -824,6 +864,17 @@ struct PassProgram {
                 static_assert(FWD && FIRST_PASS, "round-and-reduce is the load prologue of a forward transform's first pass");
 #pragma unroll
                 for (int i = 0; i < C::EPT; i++) reg[i] = ckks_round_reduce64(as_f64(reg[i]), a.q, a.pro_ratio1);
+            } else if constexpr (PRO == PRO_SMALL) {   // encryption: the words just loaded are signed samples shared by every limb
+                static_assert(FWD && FIRST_PASS, "the sample lift is the load prologue of a forward transform's first pass");
+                if (a.pro_k) {   // (uniform) bgv: times t, reduced modulo this limb's prime first
+                    const DModulus dm{a.q, a.ratio0, a.ratio1};
+                    const u64 kq = barrett64(a.pro_k, a.q, a.ratio1);
+#pragma unroll
+                    for (int i = 0; i < C::EPT; i++) reg[i] = small_lift_scaled(reg[i], kq, dm);
+                } else {
+#pragma unroll
+                    for (int i = 0; i < C::EPT; i++) reg[i] = small_lift(reg[i], a.q);
+                }
             } else if (FWD && FIRST_PASS && a.pro_reduce) {  // uniform per workgroup
 #pragma unroll
                 for (int i = 0; i < C::EPT; i++) reg[i] = barrett64(reg[i], a.q, a.pro_ratio1);

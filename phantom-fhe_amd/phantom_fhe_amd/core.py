@@ -537,6 +537,45 @@ class PhantomContext:
         """DRNSTool::decrypt_mod_t: src [L][N] (coefficient form) -> dst [N], the exact conversion to the plain modulus."""
         _lib.check(self._L.pha_decrypt_mod_t(self._h, size_Ql, _ptr(dst), _ptr(src), _stream()))
 
+    # -- encryption (csrc/pha_encrypt.hip; src/secretkey.cu:11-192, 232-295, 382-395, 463-531) ---------------------
+    # Samples (the noise e, the ternary u) are [N] SIGNED int64 words, |v| <= 2^16, one polynomial shared by every limb; the uniform a
+    # is already in c1's place in ct (canonical words, taken as NTT form).  Randomness is the caller's.
+    def encrypt_zero_symmetric_batched(self, size_Ql, sk_ntt, e, ct, scheme, with_special=False, ntt_form=True, count=None, strides=None):
+        """encrypt_zero_symmetric for ct [count][2][rows][N] (rows = size_Ql, plus the special rows with_special): c0 (b) =
+        -(a (.) s + NTT(k e (b))) from c1 (b) = a in one forward transform per ciphertext; ntt_form=False: the coefficient form
+        (-(iNTT(a (.) s) + e), iNTT(a)).  e [count][N]; strides: (e, ct) in 64-bit words, None: dense."""
+        rows = size_Ql + (self.size_P if with_special else 0)
+        count = int(ct.shape[0]) if count is None else int(count)
+        es, cs = (int(v) for v in strides) if strides is not None else (self.n, 2 * rows * self.n)
+        _lib.check(self._L.pha_encrypt_zero_symmetric_batched(self._h, size_Ql, int(bool(with_special)), _ptr(sk_ntt), _ptr(e), es, _ptr(ct),
+                                                              cs, count, int(scheme), int(bool(ntt_form)), _stream()))
+
+    def public_key_generate(self, sk_ntt, e, pk, scheme):
+        """gen_publickey: pk [2][size_QP][N] holds the uniform a in its second half; its first becomes -(a (.) s + NTT(k e)) over all
+        QP rows (encrypt_zero_symmetric_batched at the key level, NTT form)."""
+        _lib.check(self._L.pha_public_key_generate(self._h, _ptr(sk_ntt), _ptr(e), _ptr(pk), int(scheme), _stream()))
+
+    def encrypt_symmetric_batched(self, size_Ql, sk_ntt, e, plain, ct, scheme, count=None, strides=None):
+        """encrypt_symmetric for ct [count][2][L][N] (c1 (b) holds a): ckks: plain [count][L][N] in NTT form (what the encoder writes),
+        added in the transform's store; bgv / bfv: plain [count][N] words below t.  strides: (e, plain, ct), a plain stride of 0
+        shares one plaintext; None: dense."""
+        count = int(ct.shape[0]) if count is None else int(count)
+        pw = size_Ql * self.n if int(scheme) == int(scheme_type.ckks) else self.n
+        es, ps, cs = (int(v) for v in strides) if strides is not None else (self.n, pw, 2 * size_Ql * self.n)
+        _lib.check(self._L.pha_encrypt_symmetric_batched(self._h, size_Ql, _ptr(sk_ntt), _ptr(e), es, _ptr(plain), ps, _ptr(ct), cs, count,
+                                                         int(scheme), _stream()))
+
+    def encrypt_asymmetric_batched(self, size_Ql, pk, u, e, plain, ct, scheme, count=None, strides=None, chunk=0):
+        """encrypt_asymmetric for ct [count][2][L][N] (only written): pk [2][size_QP][N] as public_key_generate writes it, u [count][N],
+        e [count][2][N]; c_j = pk_j (.) NTT(u) + NTT(k e_j) over Q_l u P, the mod-down of every polynomial, the plaintext step of
+        encrypt_symmetric_batched.  strides: (u, e, plain, ct); `chunk` ciphertexts per set of launches (0: the library's default)
+        changes no bit."""
+        count = int(ct.shape[0]) if count is None else int(count)
+        pw = size_Ql * self.n if int(scheme) == int(scheme_type.ckks) else self.n
+        us, es, ps, cs = (int(v) for v in strides) if strides is not None else (self.n, 2 * self.n, pw, 2 * size_Ql * self.n)
+        _lib.check(self._L.pha_encrypt_asymmetric_batched(self._h, size_Ql, _ptr(pk), _ptr(u), us, _ptr(e), es, _ptr(plain), ps, _ptr(ct),
+                                                          cs, count, int(scheme), chunk, _stream()))
+
     def bfv_multiply_behz(self, ct1, ct2, dst):
         """bfv_multiply_behz (src/evaluate.cu:447-548): [2][Q][N] x [2][Q][N] -> [3][Q][N], coefficient form."""
         _lib.check(self._L.pha_bfv_multiply_behz(self._h, _ptr(ct1), _ptr(ct2), _ptr(dst), _stream()))

@@ -156,6 +156,11 @@ _SIGS = {
     "pha_bfv_decrypt_batched": [vp, sz, vp, sz, sz, sz, vp, sz, vp, sz, sz, vp],
     "pha_hps_decrypt_scale_and_round": [vp, sz, vp, vp, vp],
     "pha_decrypt_mod_t": [vp, sz, vp, vp, vp],
+    # encryption (csrc/pha_encrypt.hip)
+    "pha_encrypt_zero_symmetric_batched": [vp, sz, C.c_int, vp, vp, sz, vp, sz, sz, C.c_int, C.c_int, vp],
+    "pha_public_key_generate": [vp, vp, vp, vp, C.c_int, vp],
+    "pha_encrypt_symmetric_batched": [vp, sz, vp, vp, sz, vp, sz, vp, sz, sz, C.c_int, vp],
+    "pha_encrypt_asymmetric_batched": [vp, sz, vp, vp, sz, vp, sz, vp, sz, vp, sz, sz, C.c_int, sz, vp],
     # include/phantom_amd_bench.h (measurement hooks)
     "pha_time_forward_ntt": [vp, vp, sz, C.c_int, vp, C.POINTER(C.c_float)],
     "pha_repeat_forward_ntt_batched": [vp, vp, sz, sz, sz, sz, C.c_int, vp],

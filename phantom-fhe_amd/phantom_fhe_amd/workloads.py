@@ -90,6 +90,32 @@ def encode_diagonals(encoder, size_Ql, matrix, scale, steps=None):
     return out
 
 
+def encode_encrypt_batch(ctx, encoder, messages, level, scale, key, samples, public=False):
+    """The entry side of the pipeline, the mirror image of decrypt_decode_batch: messages [B][<= N / 2] complex128 on the device ->
+    one batched encode (CKKSEncoder.encode_batched) at `level` data limbs and `scale`, then one batched encryption of the plaintexts
+    where the encoder left them; nothing passes through the host.  Returns ckks ciphertexts [B][2][level][N] in NTT form.
+    public=False: key = sk_ntt [size_QP][N], samples = (a, e): the uniform a as canonical int64 words, either [B][level][N] (copied
+    into c1's place) or the ciphertext buffer itself, [B][2][level][N] with a in [:, 1] (used and returned); e [B][N] signed noise.
+    public=True: key = pk [2][size_QP][N] (PhantomContext.public_key_generate), samples = (u, e): u [B][N] ternary, e [B][2][N]."""
+    B = messages.shape[0]
+    first, e = samples
+    if public:
+        ct = torch.empty((B, 2, level, ctx.n), dtype=torch.int64, device=ctx.device)
+    elif first.dim() == 4:
+        ct = first
+    else:
+        ct = torch.empty((B, 2, level, ctx.n), dtype=torch.int64, device=ctx.device)
+        ct[:, 1].copy_(first)
+    if B:
+        plain = torch.empty((B, level, ctx.n), dtype=torch.int64, device=ctx.device)
+        encoder.encode_batched(level, messages, messages.shape[1], scale, plain)
+        if public:
+            ctx.encrypt_asymmetric_batched(level, key, first, e, plain, ct, scheme_type.ckks)
+        else:
+            ctx.encrypt_symmetric_batched(level, key, e, plain, ct, scheme_type.ckks)
+    return ct
+
+
 def decrypt_decode_batch(ctx, encoder, cts, level, scale, sk_powers):
     """The exit side of the pipeline for a batch of ckks ciphertexts cts [B][k][level][N] (NTT form, `level` data limbs): the phase
     of every ciphertext under sk_powers (PhantomContext.secret_key_powers) in one launch, then one batched decode
