@@ -59,7 +59,9 @@ const char *pha_last_error(void);
  *   synchronising pass per operand; among them pha_keyswitch_mod_switch, pha_keyswitch_mod_switch_batched,
  *   pha_inner_product_relin_mod_switch_batched, pha_hoisting_batched, pha_hoisting_weighted_batched, pha_hoisting_weighted_bsgs_batched, pha_decrypt_phase_batched, pha_bgv_decrypt_batched, pha_bfv_decrypt_batched, pha_encrypt_zero_symmetric_batched,
  *   pha_public_key_generate, pha_encrypt_symmetric_batched and pha_encrypt_asymmetric_batched, which also count sample words of
- *   magnitude above 2^16) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
+ *   magnitude above 2^16; and the batch encoder's pha_batch_encode_batched, pha_batch_decode_batched,
+ *   pha_plain_nwt_forward_inplace_batched and pha_plain_nwt_backward_inplace_batched, which count words that are not below the plain
+ *   modulus) and fail with status -1 ("PHA_STRICT: <operand> holds k word(s) >= their limb's modulus"); results are unchanged otherwise. ---- */
 int pha_check_canonical(pha_context_t ctx, const uint64_t *data, size_t coeff_modulus_size, size_t start_modulus_idx,
                         size_t size_P_tail, size_t polys, size_t poly_stride, uint64_t *bad_words, void *stream);
 int pha_check_canonical_keys(pha_context_t ctx, size_t size_Ql, const uint64_t *const *keys, size_t n_keys, uint64_t *bad_words,
@@ -811,6 +813,55 @@ int pha_encrypt_symmetric_batched(pha_context_t ctx, size_t size_Ql, const uint6
 int pha_encrypt_asymmetric_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *pk, const uint64_t *u, size_t u_stride,
                                    const uint64_t *e, size_t e_stride, const uint64_t *plain, size_t plain_stride, uint64_t *ct,
                                    size_t ct_stride, size_t count, int scheme, size_t chunk, void *stream);
+
+/* ---- BFV / BGV batch encoder (PhantomBatchEncoder, src/batchencoder.cu:7-118: constructor and populate_matrix_reps_index_map :7-49,
+ *      encode_gpu and encode :51-89, decode_gpu and decode :91-118; csrc/pha_batch.hip, arithmetic and index math in csrc/pha_batch.h,
+ *      DESIGN.md section 4.13) for BATCHES of messages.  All data buffers are DEVICE memory except where a name ends in _host, strides
+ *      are 64-bit words, N = the context's degree = the slot count, t = the context's plain modulus.  A message is up to N words, the
+ *      slots in matrix order (two rows of N / 2); a plaintext is [N] words below t in coefficient form -- what
+ *      pha_encrypt_symmetric_batched, pha_encrypt_asymmetric_batched, pha_bfv_plain_inner_product_batched, pha_bfv_lift_plain_batched
+ *      and pha_bgv_lift_plain take and pha_bfv_decrypt_batched / pha_bgv_decrypt_batched write.
+ * pha_batch_encoder_create: the tables of the constructor and of gpu_plain_tables() for ctx, built on the host: the forward and
+ *   inverse twiddles of t in bit-reversed order with Shoup quotients (psi = the minimal primitive 2N-th root), N^-1,
+ *   matrix_reps_index_map and its inverse permutation.  The encoder owns them: the context's prime table gains no row.  Needs
+ *   pha_context_set_plain_modulus.  Refused (status -1): a context without a plain modulus; a t that is not a prime with t = 1
+ *   (mod 2N): "encryption parameters are not valid for batching".  The encoder snapshots t: every later call returns -1 if the
+ *   context's plain modulus has changed since.  The context must outlive the encoder.
+ * pha_batch_encoder_index_map: matrix_reps_index_map, N words, to a HOST array.
+ * pha_plain_nwt_forward_inplace_batched / _backward_ (nwt_2d_radix8_forward_inplace / nwt_2d_radix8_backward_inplace(data,
+ *   context.gpu_plain_tables(), 1, 0, s), src/batchencoder.cu:88 and :107): the negacyclic transform modulo t, in place, of `count`
+ *   polynomials of [N] words below t, `stride` words apart; the backward one includes N^-1.  Canonical words out.  The same kernels
+ *   as encode and decode, with no permutation.
+ * Extension (no reference launcher: the reference encodes ONE message per call through a staging buffer, with the permutation as a
+ *   launch of its own) pha_batch_encode_batched: message k = values_size words at values + k * values_stride, k < count <= 65535;
+ *   plaintext k at dst + k * dst_stride = the inverse transform of buf[index_map[i]] = v_i, where v_i = values[i] for i <
+ *   values_size and 0 above, and a word with bit 63 set gets + t (the sign rule of encode_gpu: -x in two's complement encodes
+ *   t - x).  values_stride == 0 shares one message; values_size == 0 encodes zeros (values may then be null).  The permutation is
+ *   the gather of the first pass's load, N^-1 and the canonical reduction are in the last store; a message crosses global memory
+ *   at most twice (N <= 2^14: once).  From 2^20 words per call on, a two-pass transform (N > 2^14) takes the permutation as a
+ *   streaming kernel of its own instead, in front of the transform (decode: behind it), where that measured faster (DESIGN.md
+ *   section 4.13); the words are the same.
+ * Extension pha_batch_decode_batched: plaintext k (only read) at plain + k * plain_stride -> N words at values_out + k *
+ *   values_stride: out[i] = ntt[index_map[i]] of the forward transform.
+ * Shared.  Refused: a null encoder (status -1, "null encoder"); a changed plain modulus (-1); values_size > N (status -2, "values_matrix
+ *   size is too large": the reference throws logic_error there); a null pointer; count > 65535; with count > 1 a dst / plain /
+ *   values_out stride below N or a non-zero values stride below values_size; an output overlapping an input.  count == 0 is a no-op
+ *   that returns PHA_OK.  Every gather / scatter index comes from the encoder's own tables: no caller-supplied word becomes an
+ *   address.  Only canonical words are written: outputs are below t.  No entry synchronises; once the scratch of a two-pass
+ *   transform (N > 2^14: count * N words from the context's arena) has its size and the kernels have run once (first call) a call can
+ *   be captured into a graph.  PRECONDITION: after the sign rule every value word is below t, and every plaintext word is below t.
+ *   Strict mode (pha_set_strict) counts the offenders first and fails with "PHA_STRICT: <entry> values holds k word(s) ..." /
+ *   "... <entry> plain ..." with <entry> = batch_encode, batch_decode, plain_nwt_forward, plain_nwt_backward. ---- */
+typedef struct pha_batch_encoder *pha_batch_encoder_t;
+int pha_batch_encoder_create(pha_context_t ctx, pha_batch_encoder_t *enc);
+void pha_batch_encoder_destroy(pha_batch_encoder_t enc);
+int pha_batch_encoder_index_map(pha_batch_encoder_t enc, uint64_t *index_map_host);
+int pha_plain_nwt_forward_inplace_batched(pha_batch_encoder_t enc, uint64_t *inout, size_t count, size_t stride, void *stream);
+int pha_plain_nwt_backward_inplace_batched(pha_batch_encoder_t enc, uint64_t *inout, size_t count, size_t stride, void *stream);
+int pha_batch_encode_batched(pha_batch_encoder_t enc, const uint64_t *values, size_t values_size, size_t count, size_t values_stride,
+                             uint64_t *dst, size_t dst_stride, void *stream);
+int pha_batch_decode_batched(pha_batch_encoder_t enc, const uint64_t *plain, size_t count, size_t plain_stride, uint64_t *values_out,
+                             size_t values_stride, void *stream);
 
 #ifdef __cplusplus
 }

@@ -34,6 +34,14 @@ int pha_time_stream_copy(uint64_t *dst, const uint64_t *src, size_t bytes, int i
  * tools/time_ckks_encoder.py times both.  Wider coefficients always take the decompose kernel. */
 int pha_ckks_set_encode_path(int mode);
 
+/* which form pha_batch_encode_batched / pha_batch_decode_batched take, process-wide: -1 = the library's own rule per launch shape
+ * (the default); 0 = always the permutation as a kernel of its own (encode: the permutation kernel followed by the inverse
+ * transform; decode: a plain last store of the forward transform followed by the gather kernel); 1 = always the permutation inside
+ * the transform (encode: the gather of the first load; decode: the scatter of the last store).  The words are the same either way;
+ * tools/measure_batch_encoder.py times both. */
+int pha_batch_set_encode_path(int mode);
+int pha_batch_set_decode_path(int mode);
+
 /* number of scratch arenas the context currently holds (one per explicit stream, one per live host thread for the per-thread and
  * null streams; a thread's arenas are released when it exits) */
 int pha_context_arena_count(pha_context_t ctx, size_t *count);

@@ -117,6 +117,20 @@ def set_ckks_encode_path(mode):
     _lib.check(_lib.load().pha_ckks_set_encode_path(int(mode)))
 
 
+def set_batch_encode_path(mode):
+    """Measurement hook (phantom_amd_bench.h: pha_batch_set_encode_path): which form BatchEncoder.encode_batched takes -- -1 the
+    library's rule per launch shape (default), 0 the permutation kernel followed by the inverse transform, 1 the gather in the
+    inverse transform's first load.  The words are the same either way.  Process-wide."""
+    _lib.check(_lib.load().pha_batch_set_encode_path(int(mode)))
+
+
+def set_batch_decode_path(mode):
+    """Measurement hook (phantom_amd_bench.h: pha_batch_set_decode_path): which form BatchEncoder.decode_batched takes -- -1 the
+    library's rule per launch shape (default), 0 a plain last store followed by the gather kernel, 1 the scatter in the forward
+    transform's last store.  The words are the same either way.  Process-wide."""
+    _lib.check(_lib.load().pha_batch_set_decode_path(int(mode)))
+
+
 def coeff_modulus_create(poly_modulus_degree, bit_sizes):
     """CoeffModulus::Create (src/host/modulus.cu:82-111)."""
     L = _lib.load()
@@ -908,6 +922,62 @@ class CKKSEncoder:
         count = int(plain.shape[0]) if count is None else int(count)
         ps, vs = (int(v) for v in strides) if strides is not None else (size_Ql * ctx.n, self.slot_count)
         _lib.check(self._L.pha_ckks_decode_batched(self._h, size_Ql, _ptr(plain), count, ps, float(scale), _fptr(values_out), vs, _stream()))
+
+
+class BatchEncoder:
+    """PhantomBatchEncoder's device work (src/batchencoder.cu) over the C ABI: the index map, the transforms modulo the plain modulus
+    (gpu_plain_tables()), and the batched encode / decode extensions.  Messages and plaintexts are contiguous torch.int64 CUDA
+    tensors holding uint64 bit patterns; a plaintext is [N] words below t in coefficient form.  The context needs a plain modulus
+    that is a prime = 1 (mod 2N), and must keep it: a call after set_plain_modulus changed it raises ValueError."""
+
+    def __init__(self, ctx):
+        self._ctx, self._L = ctx, _lib.load()    # the context must outlive the encoder: keep it
+        h = C.c_void_p()
+        _lib.check(self._L.pha_batch_encoder_create(ctx._h, C.byref(h)))
+        self._h = h
+        self.slot_count = ctx.n
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            self._L.pha_batch_encoder_destroy(self._h)
+            self._h = None
+
+    def index_map(self):
+        """matrix_reps_index_map (populate_matrix_reps_index_map, src/batchencoder.cu:25-49): numpy uint64 [N]."""
+        out = np.zeros(self.slot_count, dtype=np.uint64)
+        _lib.check(self._L.pha_batch_encoder_index_map(self._h, out.ctypes.data_as(_lib.u64p)))
+        return out
+
+    def _layout(self, t, count, stride):
+        count = (int(t.shape[0]) if t.dim() > 1 else 1) if count is None else int(count)
+        return count, self.slot_count if stride is None else int(stride)
+
+    def plain_nwt_forward_inplace_batched(self, inout, count=None, stride=None):
+        """nwt_2d_radix8_forward_inplace over gpu_plain_tables() for inout [count][N] (words below t), in place; stride in words,
+        None: dense."""
+        count, stride = self._layout(inout, count, stride)
+        _lib.check(self._L.pha_plain_nwt_forward_inplace_batched(self._h, _ptr(inout), count, stride, _stream()))
+
+    def plain_nwt_backward_inplace_batched(self, inout, count=None, stride=None):
+        """nwt_2d_radix8_backward_inplace over gpu_plain_tables() (N^-1 included), in place."""
+        count, stride = self._layout(inout, count, stride)
+        _lib.check(self._L.pha_plain_nwt_backward_inplace_batched(self._h, _ptr(inout), count, stride, _stream()))
+
+    def encode_batched(self, values, values_size, dst, count=None, strides=None):
+        """Extension: plaintext k of dst [count][N] <- the encoding of message k = the first values_size words of values [count][...]
+        (slots past values_size are zero; a word with bit 63 set, i.e. a negative int64, gets + t).  strides: (values, dst) in words,
+        a values stride of 0 shares one message; None: dense.  No synchronisation."""
+        count = (int(dst.shape[0]) if dst.dim() > 1 else 1) if count is None else int(count)
+        dense = 0 if values is None else int(values.numel() // max(count, 1))
+        vs, ds = (int(v) for v in strides) if strides is not None else (dense, self.slot_count)
+        _lib.check(self._L.pha_batch_encode_batched(self._h, _ptr(values), int(values_size), count, vs, _ptr(dst), ds, _stream()))
+
+    def decode_batched(self, plain, values_out, count=None, strides=None):
+        """Extension: values_out [count][N] <- the decoding of plaintext k of plain [count][N] (only read).  strides: (plain,
+        values_out) in words; None: dense."""
+        count = (int(plain.shape[0]) if plain.dim() > 1 else 1) if count is None else int(count)
+        ps, vs = (int(v) for v in strides) if strides is not None else (self.slot_count, self.slot_count)
+        _lib.check(self._L.pha_batch_decode_batched(self._h, _ptr(plain), count, ps, _ptr(values_out), vs, _stream()))
 
 
 class DBaseConverter:

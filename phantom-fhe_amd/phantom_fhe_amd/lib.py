@@ -161,6 +161,13 @@ _SIGS = {
     "pha_public_key_generate": [vp, vp, vp, vp, C.c_int, vp],
     "pha_encrypt_symmetric_batched": [vp, sz, vp, vp, sz, vp, sz, vp, sz, sz, C.c_int, vp],
     "pha_encrypt_asymmetric_batched": [vp, sz, vp, vp, sz, vp, sz, vp, sz, vp, sz, sz, C.c_int, sz, vp],
+    # BFV / BGV batch encoder (csrc/pha_batch.hip)
+    "pha_batch_encoder_create": [vp, C.POINTER(vp)],
+    "pha_batch_encoder_index_map": [vp, u64p],
+    "pha_plain_nwt_forward_inplace_batched": [vp, vp, sz, sz, vp],
+    "pha_plain_nwt_backward_inplace_batched": [vp, vp, sz, sz, vp],
+    "pha_batch_encode_batched": [vp, vp, sz, sz, sz, vp, sz, vp],
+    "pha_batch_decode_batched": [vp, vp, sz, sz, vp, sz, vp],
     # include/phantom_amd_bench.h (measurement hooks)
     "pha_time_forward_ntt": [vp, vp, sz, C.c_int, vp, C.POINTER(C.c_float)],
     "pha_repeat_forward_ntt_batched": [vp, vp, sz, sz, sz, sz, C.c_int, vp],
@@ -168,6 +175,8 @@ _SIGS = {
     "pha_time_stream": [vp, vp, sz, C.c_int, C.c_int, C.c_int, vp, C.POINTER(C.c_double)],
     "pha_context_arena_count": [vp, C.POINTER(C.c_size_t)],
     "pha_ckks_set_encode_path": [C.c_int],
+    "pha_batch_set_encode_path": [C.c_int],
+    "pha_batch_set_decode_path": [C.c_int],
 }
 # exported by the test-only experiments library alone (csrc/pha_experiments.h); bound when present
 _OPTIONAL = {
@@ -178,6 +187,7 @@ _SPECIAL = {
     "pha_context_destroy": (None, [vp]),
     "pha_base_converter_destroy": (None, [vp]),
     "pha_ckks_encoder_destroy": (None, [vp]),
+    "pha_batch_encoder_destroy": (None, [vp]),
     "pha_context_log_n": (C.c_uint32, [vp]),
     "pha_context_size_qp": (C.c_uint32, [vp]),
     "pha_context_size_p": (C.c_uint32, [vp]),

@@ -129,6 +129,51 @@ def decrypt_decode_batch(ctx, encoder, cts, level, scale, sk_powers):
     return values
 
 
+def batch_encode_encrypt(ctx, encoder, messages, level, key, samples, scheme, public=False):
+    """The bfv / bgv twin of encode_encrypt_batch: messages [B][<= N] int64 words on the device (below t, or negative: the encoder's
+    sign rule) -> one batched encode (BatchEncoder.encode_batched), then one batched encryption of the plaintexts [B][N] where the
+    encoder left them; nothing passes through the host.  Returns ciphertexts [B][2][level][N], bfv in coefficient form, bgv in NTT form.
+    key and samples as encode_encrypt_batch takes them."""
+    if int(scheme) not in (int(scheme_type.bfv), int(scheme_type.bgv)):
+        raise ValueError("batch_encode_encrypt is for bfv and bgv (ckks: encode_encrypt_batch)")
+    B = messages.shape[0]
+    first, e = samples
+    if public:
+        ct = torch.empty((B, 2, level, ctx.n), dtype=torch.int64, device=ctx.device)
+    elif first.dim() == 4:
+        ct = first
+    else:
+        ct = torch.empty((B, 2, level, ctx.n), dtype=torch.int64, device=ctx.device)
+        ct[:, 1].copy_(first)
+    if B:
+        plain = torch.empty((B, ctx.n), dtype=torch.int64, device=ctx.device)
+        encoder.encode_batched(messages, messages.shape[1], plain)
+        if public:
+            ctx.encrypt_asymmetric_batched(level, key, first, e, plain, ct, scheme)
+        else:
+            ctx.encrypt_symmetric_batched(level, key, e, plain, ct, scheme)
+    return ct
+
+
+def batch_decrypt_decode(ctx, encoder, cts, level, sk_powers, scheme, correction_factors=None):
+    """The bfv / bgv twin of decrypt_decode_batch for ciphertexts cts [B][k][level][N] (bfv: coefficient form, bgv: NTT form): one
+    batched decryption (bfv_decrypt_batched / bgv_decrypt_batched; correction_factors: bgv only) into plaintexts [B][N], then one
+    batched decode (BatchEncoder.decode_batched); the plaintexts stay on the device between the two.  Returns [B][N] int64 words
+    below t."""
+    if int(scheme) not in (int(scheme_type.bfv), int(scheme_type.bgv)):
+        raise ValueError("batch_decrypt_decode is for bfv and bgv (ckks: decrypt_decode_batch)")
+    B = cts.shape[0]
+    values = torch.empty((B, encoder.slot_count), dtype=torch.int64, device=ctx.device)
+    if B:
+        plain = torch.empty((B, ctx.n), dtype=torch.int64, device=ctx.device)
+        if int(scheme) == int(scheme_type.bfv):
+            ctx.bfv_decrypt_batched(level, cts.contiguous(), sk_powers, plain)
+        else:
+            ctx.bgv_decrypt_batched(level, cts.contiguous(), sk_powers, plain, correction_factors)
+        encoder.decode_batched(plain, values)
+    return values
+
+
 def diag_matvec(ctx, size_Ql, ct, galois_elts, galois_keys, diagonals, scheme):
     """One block of config 5: out = sum_k diagonals[k] (.) rotate_{galois_elts[k]}(ct) (Halevi-Shoup diagonal
     form), all rotations hoisted behind one mod-up and one mod-down (pha_hoisting_weighted).  diagonals[k] is the
