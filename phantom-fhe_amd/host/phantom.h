@@ -1031,7 +1031,9 @@ inline std::tuple<uint64_t, uint64_t, uint64_t> balance_correction_factors(uint6
     return {mulmod(e1, factor1 % t), e1, e2};
 }
 // BGV: bring two ciphertexts to a common correction factor before adding / subtracting (src/evaluate.cu:148-168);
-// returns the (possibly scaled) second operand
+// returns the (possibly scaled) second operand.  As in the reference, e1 and e2 are multiplied in as residues in [0, t): a negative
+// e costs log2 t bits of noise where its centred value would cost log2 |e| (tests/test_bv_semantics.py measures both:
+// 140 against 150 bits of margin at hyb12_a2, profiles/bv_semantics.md)
 inline const PhantomCiphertext &balance(const PhantomContext &context, PhantomCiphertext &encrypted1,
                                         const PhantomCiphertext &encrypted2, PhantomCiphertext &scratch2) {
     if (encrypted1.correction_factor() == encrypted2.correction_factor()) return encrypted2;
