@@ -474,8 +474,8 @@ int pha_hoisting_weighted_batched(pha_context_t ctx, size_t size_Ql, const uint6
                                   size_t n_elts, const uint64_t *const *const *glk, const uint64_t *const *weights, int scheme,
                                   uint64_t *out, size_t chunk, void *stream);
 /* PhantomSecretKey::generate_one_kswitch_key (src/secretkey.cu:297-341 with encrypt_zero_symmetric :232-295),
- * arithmetic part; the randomness comes from the caller because the PRNG (sample_uniform_poly /
- * sample_error_poly, src/prng.cu) is outside the accelerated path.  All buffers on the device:
+ * arithmetic part on caller-supplied randomness (pha_generate_kswitch_keys_seeded samples a and e on the device with
+ * sample_uniform_poly / sample_error_poly, src/prng.cu, and builds all keys of a set at once).  All buffers on the device:
  *   sk_ntt [QP][N] secret key, NTT form;  new_key_ntt [Q][N] key to switch from (s^2 or galois(s)), NTT form;
  *   a [dnum][QP][N] uniform residues (used as the NTT-form c1, as the reference samples it);
  *   e [dnum][QP][N] noise residues in COEFFICIENT form -- clobbered (scaled by t for bgv, then NTT in place);
@@ -721,7 +721,7 @@ int pha_ckks_decode_batched(pha_ckks_encoder_t enc, size_t size_Ql, const uint64
  *      hps_decrypt_scale_and_round src/rns.cu:1519-1689 and decrypt_mod_t; csrc/pha_decrypt.hip, arithmetic and bounds in
  *      csrc/pha_decrypt.h).  All data buffers are DEVICE memory, strides are 64-bit words, L = size_Ql,
  *      N = the context's degree.  The secret key enters as the array pha_generate_one_kswitch_key takes; encryption and public keys
- *      are the next section; sampling (the PRNG of src/prng.cu) is not part of this library.
+ *      are the next section; sampling (the PRNG of src/prng.cu) is the last section, from seeds: managing them is not part of this library.
  * pha_secret_key_powers (compute_secret_key_array, src/secretkey.cu:196-230): out [max_power][size_QP][N] = s, s^2, ... in NTT form
  *   over all QP rows, the reference's secret_key_array layout, from sk_ntt [size_QP][N]: power 1 is a copy (out may be sk_ntt's own
  *   buffer, then nothing is copied), every further power one pha_multiply_rns_poly.
@@ -771,7 +771,8 @@ int pha_decrypt_mod_t(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const ui
  *      encrypt_zero_asymmetric / encrypt_asymmetric, src/secretkey.cu:11-192, 232-295, 382-395, 463-531; csrc/pha_encrypt.hip,
  *      arithmetic and bounds in csrc/pha_encrypt.h) for BATCHES of ciphertexts.  All data buffers are DEVICE
  *      memory, strides are 64-bit words, l = size_Ql, N = the context's degree, k = t for bgv and 1 otherwise.  Randomness is the
- *      caller's, as pha_generate_one_kswitch_key takes it; the PRNG (src/prng.cu) is not part of this library.
+ *      caller's, as pha_generate_one_kswitch_key takes it; the seeded samplers (src/prng.cu) that make such operands on the device are
+ *      the last section.
  * Samples: a sampled polynomial (the noise e, the ternary u) is [N] SIGNED 64-bit words in two's complement, |v| <= 2^16 (the
  *   reference's samplers give |v| <= 21), ONE polynomial shared by every limb: each limb lifts it modulo its own prime as it is
  *   loaded, the [L][N] residue form is never written.  The entries refuse a context that has a prime below 2^17 among the rows used.
@@ -862,6 +863,67 @@ int pha_batch_encode_batched(pha_batch_encoder_t enc, const uint64_t *values, si
                              uint64_t *dst, size_t dst_stride, void *stream);
 int pha_batch_decode_batched(pha_batch_encoder_t enc, const uint64_t *plain, size_t count, size_t plain_stride, uint64_t *values_out,
                              size_t values_stride, void *stream);
+
+/* ---- seeded samplers and key generation (src/prng.cu: salsa20_gpu, sample_ternary_poly, sample_error_poly, sample_uniform_poly,
+ *      random_bytes; the call sequences of src/secretkey.cu:297-460: gen_secretkey, generate_one_kswitch_key, gen_relinkey,
+ *      create_galois_keys; csrc/pha_prng.hip, arithmetic in csrc/pha_prng.h).  All data buffers are DEVICE
+ *      memory, strides are 64-bit words, N = the context's degree.  A seed is 64 bytes of DEVICE memory (bytes 56..63 are never
+ *      read, as in the reference); a `seeds` argument holds `count` of them back to back, seed b at seeds + 64 * b.  The caller
+ *      supplies every seed: only pha_random_bytes draws entropy.  Everything else is deterministic, seed in and words out.
+ * The generator block: 16 32-bit input words = seed bytes 0..31, the 64-bit nonce (low, high), seed bytes 32..55; 10 double rounds of
+ *   the Salsa20 quarter-round, plus the input: the Salsa20 core WITHOUT constants on the reference's own layout (published Salsa20
+ *   stream vectors do not apply).
+ * Reference layout (the launch sites a port keeps; rows [mod_start_idx, mod_start_idx + coeff_mod_size) of the QP table):
+ *   pha_sample_ternary_poly: out [cms][N], coefficient i of every limb = [byte0 % 3 - 1] mod q from the block of nonce i.
+ *   pha_sample_error_poly:   out [cms][N], the centred binomial value (|v| <= 21) of the block of nonce i, modulo every limb.
+ *     Both compute ONE block per coefficient and write it to every limb (the reference recomputes it per limb: the same words).
+ *   pha_sample_uniform_poly: out [cms][N]; group g = limb position * (N / 8) + j gives words 8 j .. 8 j + 7 of its limb from the
+ *     block of nonce g; a word above (2^64 - 1) - ((2^64 - 1) mod q) - 1 is replaced by the same word of a new block of nonce
+ *     g + tries * N * cms (tries = blocks this group has drawn), later words read the newest block; stored modulo q.
+ * The forms this library consumes:
+ *   pha_sample_ternary_signed_batched / pha_sample_error_signed_batched: out (b) at out + b * out_stride = [N] SIGNED 64-bit words
+ *     from seed b -- exactly the u / e operands of pha_encrypt_*_batched; the [L][N] residue form is never written.  (The asymmetric
+ *     entry's e [count][2][N] is a batch of 2 * count with stride N.)
+ *   pha_sample_uniform_batched: out (b) [rows][N], rows = [0, size_Ql), or [0, size_Ql) u P with with_special (the encoder's row
+ *     convention); the nonce uses the row's POSITION, the modulus is the row's prime.  At size_Ql = |Q| with_special this is
+ *     pha_sample_uniform_poly over QP.  `out` is meant to be c1's place of a ciphertext buffer or the second half of a key, out_stride
+ *     the ciphertext stride: a is never copied.
+ * Key generation, composed on the device:
+ *   pha_secret_key_generate (gen_secretkey): sk_ntt [size_QP][N] = the forward transform of the ternary sample over all QP limbs --
+ *     the array every other entry takes.
+ *   pha_generate_kswitch_keys_seeded: n_keys keys of dnum = |Q| / |P| components each.  Component b = key * dnum + digit is
+ *     [2][size_QP][N] at evk + b * evk_stride (the tables of device pointers the key switch takes are the caller's, over this
+ *     storage: the batched zero encryption addresses ciphertext b as base + b * stride, so the components of one call share one
+ *     stride); seeds [n_keys][dnum][2][64]: the uniform seed, then the noise seed; new_keys_ntt: key k [size_Q][N] in NTT form at
+ *     new_keys_ntt + k * new_key_stride (s^2: gen_relinkey; galois(s): create_galois_keys).  Three launches and one transform for all
+ *     components: a sampled straight into every second half, the noise as [N] signed words (count * N words from the context's
+ *     arena), ONE pha_encrypt_zero_symmetric_batched at the key level, P * new_key added on each digit's own limbs.  Word for word
+ *     pha_generate_one_kswitch_key per key on the same a and the same noise expanded to residues.
+ * pha_random_bytes (random_bytes): `count` bytes of std::random_device into a HOST buffer.
+ * Shared.  Refused (status -1, nothing launched): a null pointer; rows outside the context; with_special or key generation on a
+ *   context without special primes; |Q| not a multiple of |P|; an unknown scheme, bgv without a plain modulus; count (n_keys * dnum)
+ *   above 65535; an odd stride; with count > 1 a stride below the size of an element; buffers (seeds included) that are not 16-byte
+ *   aligned; evk overlapping an input; a degree below 8; for the noise in residue form a prime that is not above 21.  count == 0
+ *   does nothing.  No entry synchronises; once the arena has its size (first call) a call can be captured into a graph.
+ *   Deviation from the reference's public-key encryption, which samples both noise polynomials from ONE seed
+ *   (src/secretkey.cu:46-55, 80-81: e_0 = e_1): here every polynomial has its own seed; equal seeds reproduce the reference. ---- */
+int pha_random_bytes(unsigned char *host_buf, size_t count);
+int pha_sample_ternary_poly(pha_context_t ctx, uint64_t *out, const uint8_t *seed, size_t coeff_mod_size, size_t mod_start_idx,
+                            void *stream);
+int pha_sample_error_poly(pha_context_t ctx, uint64_t *out, const uint8_t *seed, size_t coeff_mod_size, size_t mod_start_idx,
+                          void *stream);
+int pha_sample_uniform_poly(pha_context_t ctx, uint64_t *out, const uint8_t *seed, size_t coeff_mod_size, size_t mod_start_idx,
+                            void *stream);
+int pha_sample_ternary_signed_batched(pha_context_t ctx, const uint8_t *seeds, size_t count, uint64_t *out, size_t out_stride,
+                                      void *stream);
+int pha_sample_error_signed_batched(pha_context_t ctx, const uint8_t *seeds, size_t count, uint64_t *out, size_t out_stride,
+                                    void *stream);
+int pha_sample_uniform_batched(pha_context_t ctx, size_t size_Ql, int with_special, const uint8_t *seeds, size_t count, uint64_t *out,
+                               size_t out_stride, void *stream);
+int pha_secret_key_generate(pha_context_t ctx, const uint8_t *seed, uint64_t *sk_ntt, void *stream);
+int pha_generate_kswitch_keys_seeded(pha_context_t ctx, const uint64_t *sk_ntt, const uint64_t *new_keys_ntt, size_t n_keys,
+                                     size_t new_key_stride, const uint8_t *seeds, uint64_t *evk, size_t evk_stride, int scheme,
+                                     void *stream);
 
 #ifdef __cplusplus
 }

@@ -819,6 +819,33 @@ public:
                                                               static_cast<int>(parms.scheme()), stream));
         gen_flag_ = true;
     }
+    // keys from device memory: component d [2][#QP][N] at comps + d * stride (copied)
+    void load_from_device(const PhantomContext &context, const uint64_t *comps, size_t dnum, size_t stride,
+                          const cudaStream_t &stream = cudaStreamPerThread) {
+        const size_t words = 2 * context.coeff_mod_size() * context.poly_degree();
+        allocate(context, dnum, stream);
+        for (size_t d = 0; d < dnum; d++)
+            phantom::util::check_hip(hipMemcpyAsync(public_keys_[d].data(), comps + d * stride, words * 8, hipMemcpyDeviceToDevice, stream),
+                                     "hipMemcpyAsync");
+        gen_flag_ = true;
+    }
+    // gen_relinkey / one key of create_galois_keys (src/secretkey.cu:397-460) from seeds: a thin call of
+    // pha_generate_kswitch_keys_seeded with n_keys = 1.  sk_ntt [QP][N], new_key_ntt [Q][N] (s^2 or galois(s)), seeds: DEVICE
+    // [dnum][2][64] (uniform seed, noise seed).  The entry wants the components of a call one stride apart, so they are generated in
+    // one allocation and copied into the key's ciphertexts.
+    void generate_seeded(const PhantomContext &context, const uint64_t *sk_ntt, const uint64_t *new_key_ntt, const uint8_t *seeds,
+                         const cudaStream_t &stream = cudaStreamPerThread) {
+        const auto &parms = context.get_context_data(0).parms();
+        const size_t size_p = parms.special_modulus_size();
+        if (!context.using_keyswitching() || size_p == 0) throw std::invalid_argument("keyswitching is not supported by the context");
+        const size_t dnum = (parms.coeff_modulus().size() - size_p) / size_p;
+        const size_t words = 2 * context.coeff_mod_size() * context.poly_degree();
+        auto slab = phantom::util::make_cuda_auto_ptr<uint64_t>(dnum * words, stream);
+        phantom::util::check_pha(pha_generate_kswitch_keys_seeded(context.amd(), sk_ntt, new_key_ntt, 1, 0, seeds, slab.get(), words,
+                                                                  static_cast<int>(parms.scheme()), stream));
+        load_from_device(context, slab.get(), dnum, words, stream);
+        phantom::util::check_hip(hipStreamSynchronize(stream), "hipStreamSynchronize");   // the slab is released on return
+    }
     // include/secretkey.h:129-163: dnum, then every public key as a ciphertext dump
     void save(std::ostream &stream) const {
         if (!gen_flag_) throw std::invalid_argument("PhantomRelinKey has not been generated");
@@ -868,6 +895,28 @@ public:
     }
     [[nodiscard]] const std::vector<uint32_t> &galois_elts() const { return galois_elts_; }
     [[nodiscard]] const PhantomRelinKey &get_relin_keys(size_t index) const { return relin_keys_.at(index); }
+    // create_galois_keys (src/secretkey.cu:421-460) from seeds: ONE pha_generate_kswitch_keys_seeded call for all elements.
+    // new_keys_ntt: DEVICE [n][Q][N], key i = galois_elts[i] applied to s in NTT form; seeds: DEVICE [n][dnum][2][64]
+    void generate_seeded(const PhantomContext &context, const uint64_t *sk_ntt, const uint64_t *new_keys_ntt,
+                         const std::vector<uint32_t> &galois_elts, const uint8_t *seeds, const cudaStream_t &stream = cudaStreamPerThread) {
+        const auto &parms = context.get_context_data(0).parms();
+        const size_t size_p = parms.special_modulus_size();
+        if (!context.using_keyswitching() || size_p == 0) throw std::invalid_argument("keyswitching is not supported by the context");
+        const size_t size_q = parms.coeff_modulus().size() - size_p, dnum = size_q / size_p, n = context.poly_degree();
+        const size_t words = 2 * context.coeff_mod_size() * n;
+        galois_elts_.clear();
+        relin_keys_.clear();
+        if (galois_elts.empty()) return;
+        auto slab = phantom::util::make_cuda_auto_ptr<uint64_t>(galois_elts.size() * dnum * words, stream);
+        phantom::util::check_pha(pha_generate_kswitch_keys_seeded(context.amd(), sk_ntt, new_keys_ntt, galois_elts.size(), size_q * n, seeds,
+                                                                  slab.get(), words, static_cast<int>(parms.scheme()), stream));
+        for (size_t i = 0; i < galois_elts.size(); i++) {
+            PhantomRelinKey key;
+            key.load_from_device(context, slab.get() + i * dnum * words, dnum, words, stream);
+            add(galois_elts[i], std::move(key));
+        }
+        phantom::util::check_hip(hipStreamSynchronize(stream), "hipStreamSynchronize");   // the slab is released on return
+    }
     // Extension: every key of the set from rank `root` to all ranks of `nccl_comm` (see PhantomRelinKey::broadcast)
     void broadcast(const PhantomContext &context, int root, void *nccl_comm, const cudaStream_t &stream = cudaStreamPerThread) {
         for (auto &rlk : relin_keys_) rlk.broadcast(context, root, nccl_comm, stream);
@@ -1613,6 +1662,40 @@ inline void nwt_2d_radix8_backward_inplace_include_temp_mod_scale(uint64_t *inou
                                                                            total_modulus_size, scale, scale_shoup, stream));
 }
 #undef PHA_NTT_FWD_
+
+// include/prng.cuh: random_bytes (both overloads), and the three samplers of src/prng.cu as HOST launchers whose first argument is
+// the table handle in place of the launch configuration and of the device modulus pointer (the deviation of the polymath.cuh kernels
+// below): sample_error_poly<<<g, b, 0, s>>>(out, seed, modulus, N, cms) becomes sample_error_poly(tables, out, seed, cms, start, s).
+// prng_seed is a DEVICE pointer to 64 bytes.
+inline void random_bytes(unsigned char *buf, size_t count, const cudaStream_t &stream) {
+    std::vector<uint8_t> temp(count);
+    phantom::util::check_pha(pha_random_bytes(temp.data(), count));
+    phantom::util::check_hip(hipMemcpyAsync(buf, temp.data(), count, hipMemcpyHostToDevice, stream), "hipMemcpyAsync");
+    phantom::util::check_hip(hipStreamSynchronize(stream), "hipStreamSynchronize");   // temp leaves scope
+}
+inline std::vector<uint8_t> random_bytes(size_t count) {
+    std::vector<uint8_t> temp(count);
+    phantom::util::check_pha(pha_random_bytes(temp.data(), count));
+    return temp;
+}
+inline void sample_ternary_poly(const DNTTTable &t, uint64_t *out, const uint8_t *prng_seed, size_t coeff_mod_size, size_t start_modulus_idx,
+                                const cudaStream_t &stream) {
+    phantom::util::check_pha(pha_sample_ternary_poly(t.amd(), out, prng_seed, coeff_mod_size, start_modulus_idx, stream));
+}
+inline void sample_error_poly(const DNTTTable &t, uint64_t *out, const uint8_t *prng_seed, size_t coeff_mod_size, size_t start_modulus_idx,
+                              const cudaStream_t &stream) {
+    phantom::util::check_pha(pha_sample_error_poly(t.amd(), out, prng_seed, coeff_mod_size, start_modulus_idx, stream));
+}
+inline void sample_uniform_poly(const DNTTTable &t, uint64_t *out, const uint8_t *prng_seed, size_t coeff_mod_size, size_t start_modulus_idx,
+                                const cudaStream_t &stream) {
+    phantom::util::check_pha(pha_sample_uniform_poly(t.amd(), out, prng_seed, coeff_mod_size, start_modulus_idx, stream));
+}
+// sample_uniform_poly_wrap(out, seed, modulus, N, cms, s) of src/prng.cu:206-210 with the table handle first; poly_degree is the table's
+inline void sample_uniform_poly_wrap(const DNTTTable &t, uint64_t *out, const uint8_t *prng_seed, uint64_t poly_degree, uint64_t coeff_mod_size,
+                                     const cudaStream_t &stream) {
+    if (poly_degree != t.n()) throw std::invalid_argument("poly_degree does not match the tables");
+    sample_uniform_poly(t, out, prng_seed, coeff_mod_size, 0, stream);
+}
 
 namespace phantom {
 

@@ -58,6 +58,24 @@ def _stream():
     return torch.cuda.current_stream().cuda_stream
 
 
+def _sptr(t, count):
+    """Device pointer of `count` 64-byte seeds: a contiguous torch.uint8 CUDA tensor of at least 64 * count bytes."""
+    if t is None:
+        return None
+    if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.uint8):
+        raise ValueError("expected a contiguous torch.uint8 CUDA tensor of 64-byte seeds")
+    if t.numel() < 64 * int(count):
+        raise ValueError(f"{int(count)} seed(s) need {64 * int(count)} bytes, the tensor holds {t.numel()}")
+    return t.data_ptr()
+
+
+def random_bytes(count):
+    """random_bytes (src/prng.cu): `count` bytes of std::random_device as a bytes object -- the library's one source of entropy."""
+    buf = (C.c_ubyte * max(int(count), 1))()
+    _lib.check(_lib.load().pha_random_bytes(buf, int(count)))
+    return bytes(buf[:int(count)])
+
+
 def _elts_keys(elts, keys, optional=True):
     """Galois elements and the key tables of their PhantomRelinKeys as the hoisting entries take them; optional: a key may be None
     (element 1 needs none)."""
@@ -589,6 +607,67 @@ class PhantomContext:
         us, es, ps, cs = (int(v) for v in strides) if strides is not None else (self.n, 2 * self.n, pw, 2 * size_Ql * self.n)
         _lib.check(self._L.pha_encrypt_asymmetric_batched(self._h, size_Ql, _ptr(pk), _ptr(u), us, _ptr(e), es, _ptr(plain), ps, _ptr(ct),
                                                           cs, count, int(scheme), chunk, _stream()))
+
+    # -- seeded samplers and key generation (csrc/pha_prng.hip; src/prng.cu, src/secretkey.cu:297-460) ---------------
+    # A seed is 64 bytes; seed arguments are contiguous torch.uint8 CUDA tensors, [64] or [count][64].  The caller supplies every seed.
+    def sample_ternary_poly(self, out, seed, coeff_mod_size, mod_start_idx=0):
+        """sample_ternary_poly: out [cms][N] canonical residues of the ternary sample of `seed` over rows [mod_start_idx, + cms)."""
+        _lib.check(self._L.pha_sample_ternary_poly(self._h, _ptr(out), _sptr(seed, 1), coeff_mod_size, mod_start_idx, _stream()))
+
+    def sample_error_poly(self, out, seed, coeff_mod_size, mod_start_idx=0):
+        """sample_error_poly: out [cms][N] canonical residues of the centred binomial noise (|v| <= 21) of `seed`."""
+        _lib.check(self._L.pha_sample_error_poly(self._h, _ptr(out), _sptr(seed, 1), coeff_mod_size, mod_start_idx, _stream()))
+
+    def sample_uniform_poly(self, out, seed, coeff_mod_size, mod_start_idx=0):
+        """sample_uniform_poly: out [cms][N] uniform residues by rejection, limb y modulo the prime of row mod_start_idx + y."""
+        _lib.check(self._L.pha_sample_uniform_poly(self._h, _ptr(out), _sptr(seed, 1), coeff_mod_size, mod_start_idx, _stream()))
+
+    def sample_ternary_signed_batched(self, seeds, out, count=None, out_stride=None):
+        """out (b) = [N] signed int64 words of the ternary sample of seeds[b]: the u of encrypt_asymmetric_batched.  out [count][N]
+        unless count / out_stride (64-bit words) say otherwise."""
+        count = int(out.shape[0]) if count is None else int(count)
+        stride = self.n if out_stride is None else int(out_stride)
+        _lib.check(self._L.pha_sample_ternary_signed_batched(self._h, _sptr(seeds, count), count, _ptr(out), stride, _stream()))
+
+    def sample_error_signed_batched(self, seeds, out, count=None, out_stride=None):
+        """out (b) = [N] signed int64 words of the noise sample of seeds[b]: the e of the encryption entries (the asymmetric entry's
+        [count][2][N] is a batch of 2 * count)."""
+        count = int(out.shape[0]) if count is None else int(count)
+        stride = self.n if out_stride is None else int(out_stride)
+        _lib.check(self._L.pha_sample_error_signed_batched(self._h, _sptr(seeds, count), count, _ptr(out), stride, _stream()))
+
+    def sample_uniform_batched(self, size_Ql, seeds, out, with_special=False, count=None, out_stride=None):
+        """out (b) = [rows][N] uniform residues of seeds[b] over rows [0, size_Ql) (u P with_special), at out + b * out_stride words.
+        `out` may be a view that starts at c1 of a ciphertext buffer (ct[:, 1] of [count][2][rows][N]): its first element and its
+        leading stride are used, a is never copied."""
+        rows = size_Ql + (self.size_P if with_special else 0)
+        count = int(out.shape[0]) if count is None else int(count)
+        stride = int(out_stride) if out_stride is not None else (int(out.stride(0)) if out.dim() == 3 else rows * self.n)
+        if not (out.is_cuda and out.dtype == torch.int64 and (out.dim() < 3 or out[0].is_contiguous())):
+            raise ValueError("expected torch.int64 CUDA polynomials, each contiguous")
+        _lib.check(self._L.pha_sample_uniform_batched(self._h, size_Ql, int(bool(with_special)), _sptr(seeds, count), count,
+                                                      out.data_ptr(), stride, _stream()))
+
+    def secret_key_generate(self, seed, sk_ntt=None):
+        """gen_secretkey: sk_ntt [size_QP][N] = the forward transform of the ternary sample of `seed` over all QP limbs.  Returns it."""
+        if sk_ntt is None:
+            sk_ntt = torch.empty((self.size_QP, self.n), dtype=torch.int64, device=self.device)
+        _lib.check(self._L.pha_secret_key_generate(self._h, _sptr(seed, 1), _ptr(sk_ntt), _stream()))
+        return sk_ntt
+
+    def generate_kswitch_keys_seeded(self, sk_ntt, new_keys_ntt, seeds, scheme, evk=None):
+        """n_keys key-switching keys at once (gen_relinkey: new_keys_ntt = s^2; create_galois_keys: galois(s) per element) from
+        new_keys_ntt [n_keys][size_Q][N] and seeds [n_keys][dnum][2][64] (uniform seed, noise seed): a and e are sampled on the
+        device, one batched zero encryption, P * new_key on each digit's limbs.  evk: the storage [n_keys][dnum][2][size_QP][N]
+        (allocated when None).  Returns a list of n_keys PhantomRelinKey over that storage."""
+        dnum = self.size_Q // self.size_P
+        n_keys = int(new_keys_ntt.shape[0])
+        if evk is None:
+            evk = torch.empty((n_keys, dnum, 2, self.size_QP, self.n), dtype=torch.int64, device=self.device)
+        _lib.check(self._L.pha_generate_kswitch_keys_seeded(self._h, _ptr(sk_ntt), _ptr(new_keys_ntt), n_keys, self.size_Q * self.n,
+                                                            _sptr(seeds, 2 * n_keys * dnum), _ptr(evk), 2 * self.size_QP * self.n,
+                                                            int(scheme), _stream()))
+        return [PhantomRelinKey([evk[k, d] for d in range(dnum)]) for k in range(n_keys)]
 
     def bfv_multiply_behz(self, ct1, ct2, dst):
         """bfv_multiply_behz (src/evaluate.cu:447-548): [2][Q][N] x [2][Q][N] -> [3][Q][N], coefficient form."""

@@ -168,6 +168,16 @@ _SIGS = {
     "pha_plain_nwt_backward_inplace_batched": [vp, vp, sz, sz, vp],
     "pha_batch_encode_batched": [vp, vp, sz, sz, sz, vp, sz, vp],
     "pha_batch_decode_batched": [vp, vp, sz, sz, vp, sz, vp],
+    # seeded samplers and key generation (csrc/pha_prng.hip)
+    "pha_random_bytes": [vp, sz],
+    "pha_sample_ternary_poly": [vp, vp, vp, sz, sz, vp],
+    "pha_sample_error_poly": [vp, vp, vp, sz, sz, vp],
+    "pha_sample_uniform_poly": [vp, vp, vp, sz, sz, vp],
+    "pha_sample_ternary_signed_batched": [vp, vp, sz, vp, sz, vp],
+    "pha_sample_error_signed_batched": [vp, vp, sz, vp, sz, vp],
+    "pha_sample_uniform_batched": [vp, sz, C.c_int, vp, sz, vp, sz, vp],
+    "pha_secret_key_generate": [vp, vp, vp, vp],
+    "pha_generate_kswitch_keys_seeded": [vp, vp, vp, sz, sz, vp, vp, sz, C.c_int, vp],
     # include/phantom_amd_bench.h (measurement hooks)
     "pha_time_forward_ntt": [vp, vp, sz, C.c_int, vp, C.POINTER(C.c_float)],
     "pha_repeat_forward_ntt_batched": [vp, vp, sz, sz, sz, sz, C.c_int, vp],

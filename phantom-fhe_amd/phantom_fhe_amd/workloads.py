@@ -11,6 +11,9 @@ results are bit-identical for every number of ranks.
   function (its matmul_bench is a plaintext modular GEMM); the composition is this build's, from the reference's
   hoisting_inplace (src/evaluate.cu:1670-1866), multiply_plain_inplace (:1297-1340) and add_inplace (:116-198).
 """
+import hashlib
+import os
+
 import numpy as np
 import torch
 
@@ -172,6 +175,68 @@ def batch_decrypt_decode(ctx, encoder, cts, level, sk_powers, scheme, correction
             ctx.bgv_decrypt_batched(level, cts.contiguous(), sk_powers, plain, correction_factors)
         encoder.decode_batched(plain, values)
     return values
+
+
+def derive_seeds(master, label, count):
+    """`count` 64-byte child seeds of `master` (bytes; None: os.urandom(64)) as a uint8 numpy array [count][64], on the host:
+    seed i = blake2b(master || label || i as 8 little-endian bytes, digest_size=64).  Different labels and different counters give
+    unrelated seeds; the same (master, label, i) always gives the same one."""
+    master = os.urandom(64) if master is None else bytes(master)
+    label = label.encode() if isinstance(label, str) else bytes(label)
+    out = np.empty((int(count), 64), dtype=np.uint8)
+    for i in range(int(count)):
+        out[i] = np.frombuffer(hashlib.blake2b(master + label + i.to_bytes(8, "little"), digest_size=64).digest(), dtype=np.uint8)
+    return out
+
+
+def _device_seeds(ctx, master, label, count):
+    return torch.from_numpy(derive_seeds(master, label, count)).to(ctx.device)
+
+
+def keygen(ctx, scheme, galois_elts=(), master=None, max_power=2):
+    """Every key of one party from one master seed (None: fresh entropy), sampled and built on the device: a dict with
+    sk_ntt [size_QP][N] (gen_secretkey), sk_powers [max_power][size_QP][N] (compute_secret_key_array), pk [2][size_QP][N]
+    (gen_publickey), relin (PhantomRelinKey of s^2: gen_relinkey), galois ({element: PhantomRelinKey}: create_galois_keys) and the
+    master seed used.  The only host work is the derivation of the 64-byte seeds (derive_seeds, labels "sk", "pk", "ksk")."""
+    master = os.urandom(64) if master is None else bytes(master)
+    elts = [int(e) for e in galois_elts]
+    dnum = ctx.size_Q // ctx.size_P
+    sk_ntt = ctx.secret_key_generate(_device_seeds(ctx, master, "sk", 1))
+    sk_powers = ctx.secret_key_powers(sk_ntt, max(int(max_power), 2))
+    pk_seeds = _device_seeds(ctx, master, "pk", 2)                       # the uniform seed, the noise seed
+    pk = torch.empty((2, ctx.size_QP, ctx.n), dtype=torch.int64, device=ctx.device)
+    e = torch.empty((1, ctx.n), dtype=torch.int64, device=ctx.device)
+    ctx.sample_uniform_batched(ctx.size_Q, pk_seeds[0:1], pk[1:2], with_special=True)
+    ctx.sample_error_signed_batched(pk_seeds[1:2], e)
+    ctx.public_key_generate(sk_ntt, e, pk, scheme)
+    # key 0 switches from s^2, key 1 + i from galois_elts[i] (s)
+    new_keys = torch.empty((1 + len(elts), ctx.size_Q, ctx.n), dtype=torch.int64, device=ctx.device)
+    new_keys[0].copy_(sk_powers[1, :ctx.size_Q])
+    for i, elt in enumerate(elts):
+        ctx.apply_galois_ntt(sk_ntt, new_keys[1 + i], elt, ctx.size_Q)
+    keys = ctx.generate_kswitch_keys_seeded(sk_ntt, new_keys, _device_seeds(ctx, master, "ksk", 2 * dnum * (1 + len(elts))), scheme)
+    return {"sk_ntt": sk_ntt, "sk_powers": sk_powers, "pk": pk, "relin": keys[0], "galois": dict(zip(elts, keys[1:])), "master": master}
+
+
+def sample_encryption(ctx, level, count, master, public=False):
+    """The `samples` tuple encode_encrypt_batch / batch_encode_encrypt take for `count` ciphertexts at `level` data limbs, sampled on
+    the device from seeds derived from `master` (labels "enc.a" / "enc.e", "enc.u").  public=False: (ct, e) with ct the ciphertext
+    buffer [count][2][level][N] whose [:, 1] holds the uniform a (sampled in place, never copied) and e [count][N];
+    public=True: (u, e) with u [count][N] ternary and e [count][2][N], one seed per polynomial."""
+    n = ctx.n
+    if public:
+        u = torch.empty((count, n), dtype=torch.int64, device=ctx.device)
+        e = torch.empty((count, 2, n), dtype=torch.int64, device=ctx.device)
+        if count:
+            ctx.sample_ternary_signed_batched(_device_seeds(ctx, master, "enc.u", count), u)
+            ctx.sample_error_signed_batched(_device_seeds(ctx, master, "enc.e", 2 * count), e.view(2 * count, n))
+        return u, e
+    ct = torch.empty((count, 2, level, n), dtype=torch.int64, device=ctx.device)
+    e = torch.empty((count, n), dtype=torch.int64, device=ctx.device)
+    if count:
+        ctx.sample_uniform_batched(level, _device_seeds(ctx, master, "enc.a", count), ct[:, 1])
+        ctx.sample_error_signed_batched(_device_seeds(ctx, master, "enc.e", count), e)
+    return ct, e
 
 
 def diag_matvec(ctx, size_Ql, ct, galois_elts, galois_keys, diagonals, scheme):
