@@ -57,7 +57,7 @@ const char *pha_last_error(void);
  *   environment when the library was first used.  In strict mode the dyadic, tensor, mod-up / inner-product / mod-down, key-switch,
  *   hoisting and BFV multiply entries check ct / c2 / t_mod_up / keys / weights / ct1 and ct2 before they compute (one
  *   synchronising pass per operand; among them pha_keyswitch_mod_switch, pha_keyswitch_mod_switch_batched,
- *   pha_inner_product_relin_mod_switch_batched, pha_hoisting_batched, pha_hoisting_weighted_batched, pha_hoisting_weighted_bsgs_batched, pha_decrypt_phase_batched, pha_bgv_decrypt_batched, pha_bfv_decrypt_batched, pha_encrypt_zero_symmetric_batched,
+ *   pha_inner_product_relin_mod_switch_batched, pha_hoisting_batched, pha_hoisting_weighted_batched, pha_hoisting_weighted_bsgs_batched, pha_decrypt_phase_batched, pha_bgv_decrypt_batched, pha_bfv_decrypt_batched, pha_poly_infty_norm_batched, pha_invariant_noise_budget_batched, pha_encrypt_zero_symmetric_batched,
  *   pha_public_key_generate, pha_encrypt_symmetric_batched and pha_encrypt_asymmetric_batched, which also count sample words of
  *   magnitude above 2^16; and the batch encoder's pha_batch_encode_batched, pha_batch_decode_batched,
  *   pha_plain_nwt_forward_inplace_batched and pha_plain_nwt_backward_inplace_batched, which count words that are not below the plain
@@ -766,6 +766,37 @@ int pha_bfv_decrypt_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *c
                             const uint64_t *sk_powers, size_t n_powers, uint64_t *dst, size_t dst_stride, size_t chunk, void *stream);
 int pha_hps_decrypt_scale_and_round(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream);
 int pha_decrypt_mod_t(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream);
+
+/* ---- noise (PhantomSecretKey::invariant_noise_budget, src/secretkey.cu:752-840, with compose_array and
+ *      poly_infinity_norm_coeffmod; csrc/pha_noise.hip, arithmetic and bounds in csrc/pha_noise.h).  The
+ *      reference copies the phase to the host, composes it with multi-precision integers and takes the norm on the CPU, one
+ *      ciphertext per call behind a stream synchronise; here the norm is a device-side quantity of a BATCH.  All data buffers are
+ *      DEVICE memory, strides are 64-bit words, L = size_Ql <= 64, N = the context's degree.  Exact integer arithmetic throughout: no
+ *      floating point, no atomics, no dependence on launch order.
+ * Extension pha_poly_infty_norm_batched: polynomial c < count, [L][N] in coefficient form with canonical residues at src +
+ *   c * src_stride.  With v_j in [0, Q_l) the CRT composition of [scalar * x_{i,j}]_{q_i} (scalar: any 64-bit word, reduced modulo
+ *   every q_i on the host), the polynomial's norm is max_j min(v_j, Q_l - v_j): norm [count][L] receives it as L little-endian 64-bit
+ *   words (NULL: not written), bits [count] its significant bit count (0 for a zero norm).  Two launches: mixed-radix (Garner)
+ *   digits per coefficient and one candidate per workgroup, then the maximum, its conversion to binary and the stores.
+ * Extension pha_invariant_noise_budget_batched: ciphertexts and sk_powers as the decrypt entries take them; PHA_SCHEME_BFV:
+ *   COEFFICIENT form, the phase of pha_bfv_decrypt_batched (forward transforms of c_1 .. out of place, the phase kernel, one batched
+ *   inverse that adds c0), norm taken with scalar = t; PHA_SCHEME_BGV / PHA_SCHEME_CKKS: NTT form, the phase of
+ *   pha_bgv_decrypt_batched up to its inverse transform, scalar = 1 (the reference multiplies by t under bfv only; under ckks the
+ *   result is the headroom above scale * message).  budget [batch] (int32) = max(0, bitcount(Q_l) - bits - 1); norm [batch][L] may
+ *   be NULL.  chunk as in the decrypt entries (0: the default, 8; work buffer [chunk][L][N] words, bfv [chunk][cipher_size - 1][L][N],
+ *   plus the candidates).  Every `chunk` gives the same words.  The ciphertexts are only read.
+ * Refused (status -1, nothing launched, nothing written): what the decrypt entries refuse (a null ct / sk_powers / src / budget /
+ *   bits; size_Ql outside 1..|Q| or above 64; cipher_size < 2 or n_powers < cipher_size - 1; with batch > 1 a ct (src) stride below
+ *   the size of an element; an odd ct stride; ct or sk_powers not 16-byte aligned); an unknown scheme; PHA_SCHEME_BFV or
+ *   PHA_SCHEME_BGV on a context without a plain modulus; norm / budget / bits overlapping an input or each other.  batch == 0
+ *   (count == 0) does nothing.  No entry synchronises; once the work buffer has its size and the tables exist (first call) a call
+ *   can be captured into a graph.  Strict mode (pha_set_strict) checks ct, sk_powers and src, named "noise_budget ct",
+ *   "noise_budget sk_powers" and "poly_infty_norm src". ---- */
+int pha_poly_infty_norm_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *src, size_t count, size_t src_stride,
+                                uint64_t scalar, uint64_t *norm, uint32_t *bits, void *stream);
+int pha_invariant_noise_budget_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t cipher_size, size_t batch,
+                                       size_t ct_stride, const uint64_t *sk_powers, size_t n_powers, int scheme, int32_t *budget,
+                                       uint64_t *norm, size_t chunk, void *stream);
 
 /* ---- encryption (PhantomSecretKey::encrypt_zero_symmetric / gen_publickey / encrypt_symmetric, PhantomPublicKey::
  *      encrypt_zero_asymmetric / encrypt_asymmetric, src/secretkey.cu:11-192, 232-295, 382-395, 463-531; csrc/pha_encrypt.hip,

@@ -20,7 +20,7 @@
 namespace pha {
 
 constexpr int kDecThreads = 256;
-constexpr size_t kDecChunk = 8;        // ciphertexts per set of launches of the BGV / BFV entries (work buffer: chunk * (k - 1) * L * N words)
+constexpr size_t kDecChunk = kDecryptChunk;   // ciphertexts per set of launches of the BGV / BFV entries (work buffer: chunk * (k - 1) * L * N words)
 constexpr int kModTPolys = 16;         // polynomials per conversion launch: their factors travel in the kernel arguments
 
 struct PhaseArgs {
@@ -74,8 +74,8 @@ __global__ __launch_bounds__(kDecThreads) void phase_kernel(const PhaseArgs k) {
     }
 }
 
-// launch only: the callers have validated.  c0 == null drops it.
-static void launch_phase(Context &c, size_t size_Ql, const u64 *c0, const u64 *c1, size_t cipher_size, size_t batch, size_t ct_stride,
+// launch only: the callers have validated.  c0 == null drops it.  (pha_internal.h: the noise budget of pha_noise.hip starts here too)
+void launch_phase(Context &c, size_t size_Ql, const u64 *c0, const u64 *c1, size_t cipher_size, size_t batch, size_t ct_stride,
                          const u64 *sk, u64 *dst, size_t dst_stride, hipStream_t s) {
     const PhaseArgs k{c0, c1, sk, dst, c.d_mod.p, c.d_fpinfo.p, (uint32_t)c.n, (uint32_t)size_Ql, (uint32_t)cipher_size, (uint32_t)batch,
                       ct_stride, (size_t)c.size_qp * c.n, dst_stride};

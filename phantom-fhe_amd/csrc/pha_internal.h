@@ -262,6 +262,19 @@ struct DecryptLevel {
     u64 q_mod_t = 0;
 };
 
+// ---- the noise kernels (pha_noise.hip; the programs: pha_noise.h): the mixed-radix tables over the first min(|Q|, 64) primes, ONE
+//      set for every level, and per level the digits of (Q_l - 1) / 2 and bitcount(Q_l); built on first use, independent of t
+struct NoiseBase {
+    uint32_t size = 0;           // the row pitch of inv
+    DevBuf<u64x2> inv;           // [size][size]  entry (i, j), i < j: q_i^-1 mod q_j (+Shoup)
+    DevBuf<u64> lift;            // [size]        q_j ceil(2^61 / q_j)
+};
+struct NoiseLevel {
+    uint32_t size = 0;
+    int q_bits = 0;
+    DevBuf<u64> half;            // [size]
+};
+
 // ---- scratch arena: one per (context, stream), grown on demand, never freed until destroy ----
 struct Arena {
     DevBuf<u64> buf;
@@ -310,6 +323,10 @@ struct Context {
     CkksCompose &ckks_compose(uint32_t size_ql);
     std::map<uint32_t, std::unique_ptr<DecryptLevel>> decrypt_tables;   // by |Ql|; built on first use (pha_decrypt.hip), dropped with the plain modulus
     DecryptLevel &decrypt_level(uint32_t size_ql);
+    std::unique_ptr<NoiseBase> noise_tables;                        // built on first use (pha_noise.hip)
+    std::map<uint32_t, std::unique_ptr<NoiseLevel>> noise_levels;   // by |Ql|
+    NoiseBase &noise_base();
+    NoiseLevel &noise_level(uint32_t size_ql);
     uint32_t rows = 0;  // table rows = size_qp + auxiliary moduli
     // keyed by (stream handle, host thread): hipStreamPerThread and the null stream are sentinels that name a different
     // real stream (or none) in every host thread, so those two handles get one arena per calling thread
@@ -496,6 +513,11 @@ struct KsScratch {
     KsScratch(u64 *base, const Context &c, const Tool &t, size_t B) : KsScratch(base, t.size_ql, t.size_qlp, t.beta, c.n, B) {}
 };
 
+// the phase kernel of pha_decrypt.hip, launch only (the caller has validated): dst (b) = c0 (b) + sum_i c_i (b) (.) s^i over NTT-form
+// operands, polynomial i >= 1 of ciphertext b at c1 + b * ct_stride + (i - 1) * L * N; c0 == null drops it
+constexpr size_t kDecryptChunk = 8;   // ciphertexts per set of launches of the chunked entries (0 = this default)
+void launch_phase(Context &c, size_t size_Ql, const u64 *c0, const u64 *c1, size_t cipher_size, size_t batch, size_t ct_stride,
+                  const u64 *sk, u64 *dst, size_t dst_stride, hipStream_t s);
 bool ntt_domain_scheme(int scheme);   // ckks / bgv: true, bfv: false; throws on anything else
 void check_level(Context &c, size_t size_Ql, bool need_p);
 // argument checks shared by the entry points

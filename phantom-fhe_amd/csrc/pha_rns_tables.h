@@ -375,4 +375,51 @@ inline DecryptModTTables decrypt_mod_t_tables(const std::vector<u64> &primes, ui
     return d;
 }
 
+// ---- mixed-radix tables of the noise kernels (pha_noise.h) ------------------------------------------------------------------------
+// Over the first `size` primes, ONE set for every level (digit a_j depends on q_0 .. q_j only): inv [size][size], entry i * size + j
+// (i < j) = (q_i^-1 mod q_j, Shoup), zero elsewhere; lift [size] = q_j ceil(2^61 / q_j), the multiple of q_j in [2^61, 2^61 + q_j).
+struct NoiseTables {
+    uint32_t size = 0;
+    std::vector<u64x2> inv;
+    std::vector<u64> lift;
+};
+inline NoiseTables noise_tables(const std::vector<u64> &primes, uint32_t size) {
+    NoiseTables t;
+    t.size = size;
+    t.inv.assign((size_t)size * size, u64x2{0, 0});
+    t.lift.resize(size);
+    for (uint32_t j = 0; j < size; j++) {
+        const u64 qj = primes[j];
+        if (qj >> 61) throw std::invalid_argument("the noise kernels take moduli below 2^61");
+        t.lift[j] = qj * ((((u64)1 << 61) + qj - 1) / qj);
+        for (uint32_t i = 0; i < j; i++) t.inv[(size_t)i * size + j] = h_pair(h_invmod(primes[i] % qj, qj), qj);
+    }
+    return t;
+}
+// Per level: the mixed-radix digits of (Q_l - 1) / 2 (repeated division of the big integer by q_0, q_1, ...), bitcount(Q_l), and
+// scalar mod q_i for the factor the norm is taken with (t can exceed a 41-bit limb).
+struct NoiseLevelTables {
+    std::vector<u64> half;   // [size_ql]
+    int q_bits = 0;
+};
+inline NoiseLevelTables noise_level_tables(const std::vector<u64> &primes, uint32_t size_ql) {
+    NoiseLevelTables t;
+    Big q{1};
+    for (uint32_t i = 0; i < size_ql; i++) big_mul(q, primes[i]);
+    t.q_bits = big_bits(q);
+    Big h(q);                // (Q - 1) / 2 = Q >> 1 for odd Q
+    for (size_t w = 0; w < h.size(); w++) h[w] = (h[w] >> 1) | (w + 1 < h.size() ? h[w + 1] << 63 : 0);
+    t.half.resize(size_ql);
+    for (uint32_t i = 0; i < size_ql; i++) {
+        t.half[i] = big_mod(h, primes[i]);
+        big_div(h, primes[i]);
+    }
+    return t;
+}
+inline std::vector<u64> noise_scalar_table(const std::vector<u64> &primes, uint32_t size_ql, u64 scalar) {
+    std::vector<u64> s(size_ql);
+    for (uint32_t i = 0; i < size_ql; i++) s[i] = scalar % primes[i];
+    return s;
+}
+
 }  // namespace pha

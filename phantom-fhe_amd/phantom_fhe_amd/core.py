@@ -47,6 +47,13 @@ def _ptr(t):
     return t.data_ptr()
 
 
+def _i32ptr(t):
+    """Device pointer of a contiguous int32 CUDA tensor (bit counts and noise budgets)."""
+    if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32):
+        raise ValueError("expected a contiguous torch.int32 CUDA tensor")
+    return t.data_ptr()
+
+
 def _fptr(t):
     """Device pointer of a contiguous float64 / complex128 CUDA tensor (the CKKS encoder's messages and coefficients)."""
     if not (t.is_cuda and t.is_contiguous() and t.dtype in (torch.float64, torch.complex128)):
@@ -568,6 +575,27 @@ class PhantomContext:
     def decrypt_mod_t(self, size_Ql, dst, src):
         """DRNSTool::decrypt_mod_t: src [L][N] (coefficient form) -> dst [N], the exact conversion to the plain modulus."""
         _lib.check(self._L.pha_decrypt_mod_t(self._h, size_Ql, _ptr(dst), _ptr(src), _stream()))
+
+    # -- noise (csrc/pha_noise.hip; src/secretkey.cu:752-840) --------------------------------------------
+    def poly_infty_norm_batched(self, size_Ql, src, bits, norm=None, scalar=1, count=None, stride=None):
+        """Extension: the exact infinity norm max_j min(v_j, Q_l - v_j) of polynomial c of src [count][L][N] (coefficient form,
+        canonical), v_j the CRT composition of scalar * x mod q_i: bits [count] int32 = its significant bit count, norm [count][L]
+        (None: not written) its little-endian 64-bit words.  stride: words between polynomials, None: dense."""
+        count = int(src.shape[0]) if count is None else int(count)
+        stride = size_Ql * self.n if stride is None else int(stride)
+        _lib.check(self._L.pha_poly_infty_norm_batched(self._h, size_Ql, _ptr(src), count, stride, int(scalar), _ptr(norm), _i32ptr(bits),
+                                                       _stream()))
+
+    def invariant_noise_budget_batched(self, size_Ql, ct, sk_powers, scheme, budget, norm=None, cipher_size=None, batch=None,
+                                       n_powers=None, stride=None, chunk=0):
+        """Extension (invariant_noise_budget for a batch): budget [batch] int32 = max(0, bitcount(Q_l) - bitcount(norm) - 1) of
+        ciphertext b of ct [batch][cipher_size][L][N] (bfv: coefficient form, norm of t * phase; bgv / ckks: NTT form, norm of the
+        phase), norm [batch][L] (None: not written) the exact norm's words.  The ciphertexts are only read; nothing synchronises.
+        stride: words between ciphertexts, None: dense; `chunk` ciphertexts per set of launches changes no word."""
+        k, B, cs, npw, _ = self._decrypt_layout(size_Ql, ct, sk_powers, 0, cipher_size, batch, n_powers,
+                                                None if stride is None else (stride, 0))
+        _lib.check(self._L.pha_invariant_noise_budget_batched(self._h, size_Ql, _ptr(ct), k, B, cs, _ptr(sk_powers), npw, int(scheme),
+                                                              _i32ptr(budget), _ptr(norm), chunk, _stream()))
 
     # -- encryption (csrc/pha_encrypt.hip; src/secretkey.cu:11-192, 232-295, 382-395, 463-531) ---------------------
     # Samples (the noise e, the ternary u) are [N] SIGNED int64 words, |v| <= 2^16, one polynomial shared by every limb; the uniform a

@@ -156,6 +156,9 @@ _SIGS = {
     "pha_bfv_decrypt_batched": [vp, sz, vp, sz, sz, sz, vp, sz, vp, sz, sz, vp],
     "pha_hps_decrypt_scale_and_round": [vp, sz, vp, vp, vp],
     "pha_decrypt_mod_t": [vp, sz, vp, vp, vp],
+    # noise (csrc/pha_noise.hip)
+    "pha_poly_infty_norm_batched": [vp, sz, vp, sz, sz, C.c_uint64, vp, vp, vp],
+    "pha_invariant_noise_budget_batched": [vp, sz, vp, sz, sz, sz, vp, sz, C.c_int, vp, vp, sz, vp],
     # encryption (csrc/pha_encrypt.hip)
     "pha_encrypt_zero_symmetric_batched": [vp, sz, C.c_int, vp, vp, sz, vp, sz, sz, C.c_int, C.c_int, vp],
     "pha_public_key_generate": [vp, vp, vp, vp, C.c_int, vp],

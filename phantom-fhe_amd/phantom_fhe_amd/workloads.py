@@ -132,6 +132,17 @@ def decrypt_decode_batch(ctx, encoder, cts, level, scale, sk_powers):
     return values
 
 
+def noise_budget_batch(ctx, cts, level, sk_powers, scheme):
+    """The invariant noise budget of every ciphertext of cts [B][k][level][N] (bfv: coefficient form, bgv / ckks: NTT form) under
+    sk_powers (PhantomContext.secret_key_powers), in bits: int32 [B] on the device, computed there exactly
+    (PhantomContext.invariant_noise_budget_batched) -- no host round trip and no synchronisation, so a pipeline can ask after every
+    homomorphic step."""
+    budget = torch.empty((cts.shape[0],), dtype=torch.int32, device=ctx.device)
+    if cts.shape[0]:
+        ctx.invariant_noise_budget_batched(level, cts.contiguous(), sk_powers, scheme, budget)
+    return budget
+
+
 def batch_encode_encrypt(ctx, encoder, messages, level, key, samples, scheme, public=False):
     """The bfv / bgv twin of encode_encrypt_batch: messages [B][<= N] int64 words on the device (below t, or negative: the encoder's
     sign rule) -> one batched encode (BatchEncoder.encode_batched), then one batched encryption of the plaintexts [B][N] where the
