@@ -243,10 +243,6 @@ bool fused_encode(size_t /*count*/, size_t /*limbs*/) {
     return mode < 0 || mode == 1;
 }
 
-void check_ckks_level(const Context &c, size_t size_Ql) {
-    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("RNSBase is invalid");
-}
-
 void check_dst(const void *p, size_t stride, size_t count, size_t words, const char *what) {
     if (reinterpret_cast<uintptr_t>(p) & 15) throw std::invalid_argument("buffers must be 16-byte aligned");
     if (count > 1 && (stride & 1)) throw std::invalid_argument("strides must be even (16-byte loads)");
@@ -260,7 +256,7 @@ CkksCompose &Context::ckks_compose(uint32_t size_ql) {
     std::lock_guard<std::mutex> lk(mu);
     auto it = ckks_tables.find(size_ql);
     if (it != ckks_tables.end()) return *it->second;
-    if (size_ql < 1 || size_ql > size_q) throw std::invalid_argument("RNSBase is invalid");
+    check_rns_level(size_ql, size_q);
     PHA_HIP(hipSetDevice(device));
     auto t = std::make_unique<CkksCompose>();
     t->size = size_ql;
@@ -376,7 +372,7 @@ int pha_decompose_array(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const 
     PHA_CTX_BEGIN(ctx)
     need(dst); need(src);
     Context &c = ctx->c;
-    check_ckks_level(c, size_Ql);
+    check_rns_level(size_Ql, c.size_q);
     launch_decompose(c, dst, 0, src, 0, false, (uint32_t)size_Ql, (uint32_t)size_Ql, 1, max_coeff_bit_count > 64, as_stream(stream));
     PHA_API_END
 }
@@ -385,7 +381,7 @@ int pha_compose_array(pha_context_t ctx, size_t size_Ql, double *dst, const uint
     PHA_CTX_BEGIN(ctx)
     need(dst); need(src);
     Context &c = ctx->c;
-    check_ckks_level(c, size_Ql);
+    check_rns_level(size_Ql, c.size_q);
     CkksCompose &t = c.ckks_compose((uint32_t)size_Ql);
     u64 *acc = c.scratch(stream, size_Ql * c.n);
     launch_compose(c, t, dst, 0, false, src, 0, acc, 1, inv_scale, as_stream(stream));
@@ -398,7 +394,7 @@ int pha_ckks_encode_batched(pha_ckks_encoder_t enc, size_t size_Ql, int with_spe
     PHA_ENC_BEGIN(enc)
     need(values); need(dst);
     Context &c = enc->ctx->c;
-    check_ckks_level(c, size_Ql);
+    check_rns_level(size_Ql, c.size_q);
     const size_t slots = (size_t)1 << enc->log_slots, limbs = size_Ql + (with_special ? c.size_p : 0);
     if (values_size == 0) throw std::invalid_argument("Input vector is empty");
     if (values_size > slots) throw std::invalid_argument("Input vector exceeds max slots");
@@ -452,7 +448,7 @@ int pha_ckks_decode_batched(pha_ckks_encoder_t enc, size_t size_Ql, const uint64
     PHA_ENC_BEGIN(enc)
     need(plain); need(values_out);
     Context &c = enc->ctx->c;
-    check_ckks_level(c, size_Ql);
+    check_rns_level(size_Ql, c.size_q);
     const size_t slots = (size_t)1 << enc->log_slots, ln = size_Ql * c.n;
     CkksCompose &t = c.ckks_compose((uint32_t)size_Ql);
     if (!(scale > 0) || !std::isfinite(scale) || static_cast<int>(std::log2(scale)) >= t.bits) throw std::invalid_argument("scale out of bounds");

@@ -20,7 +20,7 @@
 namespace pha {
 
 constexpr int kDecThreads = 256;
-constexpr size_t kDecChunk = kDecryptChunk;   // ciphertexts per set of launches of the BGV / BFV entries (work buffer: chunk * (k - 1) * L * N words)
+static_assert(kPhaseBatchMax == (size_t)kPhaseGroup * 65535, "pha_layout.h: a group per workgroup row, the row in blockIdx.z");
 constexpr int kModTPolys = 16;         // polynomials per conversion launch: their factors travel in the kernel arguments
 
 struct PhaseArgs {
@@ -74,8 +74,8 @@ __global__ __launch_bounds__(kDecThreads) void phase_kernel(const PhaseArgs k) {
     }
 }
 
-// launch only: the callers have validated.  c0 == null drops it.  (pha_internal.h: the noise budget of pha_noise.hip starts here too)
-void launch_phase(Context &c, size_t size_Ql, const u64 *c0, const u64 *c1, size_t cipher_size, size_t batch, size_t ct_stride,
+// launch only: the callers have validated.  c0 == null drops it
+static void launch_phase(Context &c, size_t size_Ql, const u64 *c0, const u64 *c1, size_t cipher_size, size_t batch, size_t ct_stride,
                          const u64 *sk, u64 *dst, size_t dst_stride, hipStream_t s) {
     const PhaseArgs k{c0, c1, sk, dst, c.d_mod.p, c.d_fpinfo.p, (uint32_t)c.n, (uint32_t)size_Ql, (uint32_t)cipher_size, (uint32_t)batch,
                       ct_stride, (size_t)c.size_qp * c.n, dst_stride};
@@ -84,6 +84,38 @@ void launch_phase(Context &c, size_t size_Ql, const u64 *c0, const u64 *c1, size
     else if (cipher_size == 3) hipLaunchKernelGGL(phase_kernel<3>, grid, block, 0, s, k);
     else hipLaunchKernelGGL(phase_kernel<0>, grid, block, 0, s, k);
     check_launch();
+}
+
+// NTT form (bgv, ckks): the phase kernel, one batched inverse transform.  Coefficient form (bfv): the three steps below
+void phase_to_coeff(Context &c, size_t size_Ql, bool ntt_form, const CtBatch &chunk, u64 *work, size_t wst, hipStream_t s) {
+    const size_t ln = size_Ql * c.n, km1 = chunk.cipher_size - 1, B = chunk.batch, ct_stride = chunk.ct_stride;
+    const LimbSel sel = plain_sel(0, size_Ql);
+    NttExtra x;
+    x.batch = (uint32_t)B;
+    x.poly_stride = wst;
+    if (ntt_form) {
+        launch_phase(c, size_Ql, chunk.ct, chunk.ct + ln, chunk.cipher_size, B, ct_stride, chunk.sk_powers, work, wst, s);
+        return ntt_inverse(c, work, work, work, sel, EPI_INV_CANON, x, s);
+    }
+    // 1. c1 .. c_{k-1} of every ciphertext forward, out of place into the work buffer [B][k - 1][L][N]
+    NttExtra f;
+    f.poly_stride = ln;
+    if (km1 == 1 || B == 1) {   // one polynomial per ciphertext, or one ciphertext: the polynomials are evenly spaced
+        f.batch = (uint32_t)(B * km1);
+        f.in_stride = km1 == 1 ? ct_stride : ln;
+        ntt_forward(c, chunk.ct + ln, work, work, sel, EPI_FWD_CANON, f, s);
+    } else {
+        f.batch = (uint32_t)km1;
+        f.in_stride = ln;
+        for (size_t g = 0; g < B; g++) ntt_forward(c, chunk.ct + g * ct_stride + ln, work + g * wst, work + g * wst, sel, EPI_FWD_CANON, f, s);
+    }
+    // 2. the phase without c0; result b takes the place of its own c1 in the work buffer (a thread reads its words before it writes)
+    launch_phase(c, size_Ql, nullptr, work, chunk.cipher_size, B, wst, chunk.sk_powers, work, wst, s);
+    // 3. back to coefficient form in place, c0 (b) added in the final store
+    x.aux = chunk.ct;
+    x.aux_stride = ct_stride ? ct_stride : wst;   // (B == 1 with stride 0: unused)
+    x.aux_pair_stride = 2 * ct_stride;            // polynomial z adds c0 of ciphertext z: (z / 2) * 2 stride + (z % 2) * stride
+    ntt_inverse(c, work, work, work, sel, EPI_INV_CANON_ADD, x, s);
 }
 
 // ---- the two tails: one coefficient per thread, the polynomial is blockIdx.y ----------------------------------------------------
@@ -130,8 +162,8 @@ DecryptLevel &Context::decrypt_level(uint32_t size_ql) {
     std::lock_guard<std::mutex> lk(mu);
     auto it = decrypt_tables.find(size_ql);
     if (it != decrypt_tables.end()) return *it->second;
-    if (size_ql < 1 || size_ql > size_q) throw std::invalid_argument("RNSBase is invalid");
-    if (!plain_t) throw std::invalid_argument("the context has no plain modulus (pha_context_set_plain_modulus)");
+    check_rns_level(size_ql, size_q);
+    need_plain_modulus(shape(*this));
     if (size_ql > kDecryptMaxLimbs) throw std::invalid_argument("decryption to a plain modulus takes levels of at most 64 limbs");
     PHA_HIP(hipSetDevice(device));
     auto d = std::make_unique<DecryptLevel>();
@@ -168,36 +200,13 @@ static void launch_mod_t(Context &c, DecryptLevel &d, u64 *dst, size_t dst_strid
     }
 }
 
-// ---- what the three batched entries refuse, in this order ---------------------------------------------------------------------------
-// out_words: the size of one result (L * N for the phase, N for the plaintexts).  in_place_ok: dst may be ct itself (c0's place).
-static void decrypt_check(Context &c, size_t size_Ql, const u64 *ct, size_t cipher_size, size_t batch, size_t ct_stride, const u64 *sk_powers,
-                          size_t n_powers, const u64 *dst, size_t dst_stride, size_t out_words, bool in_place_ok, bool need_t) {
-    need(ct); need(sk_powers); need(dst);
-    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("RNSBase is invalid");
-    if (need_t && !c.plain_t) throw std::invalid_argument("the context has no plain modulus (pha_context_set_plain_modulus)");
-    if (cipher_size < 2 || cipher_size > 65535) throw std::invalid_argument("cipher_size out of range");
-    if (n_powers < cipher_size - 1) throw std::invalid_argument("sk_powers holds fewer powers than the ciphertext has polynomials beyond c0");
-    if (batch > (size_t)kPhaseGroup * 65535) throw std::invalid_argument("batch out of range");
-    const size_t ln = size_Ql * c.n, ct_words = cipher_size * ln;
-    if (batch > 1 && ct_stride < ct_words) throw std::invalid_argument("ct stride below cipher_size * L * N: the ciphertexts overlap");
-    if (batch > 1 && dst_stride < out_words) throw std::invalid_argument("dst stride below the size of a result: the results overlap");
-    if ((ct_stride | dst_stride) & 1) throw std::invalid_argument("strides must be even (16-byte loads)");
-    if ((reinterpret_cast<uintptr_t>(ct) | reinterpret_cast<uintptr_t>(sk_powers) | reinterpret_cast<uintptr_t>(dst)) & 15)
-        throw std::invalid_argument("buffers must be 16-byte aligned");
-    if (batch == 0) return;
-    const size_t dst_span = (batch - 1) * dst_stride + out_words, ct_span = (batch - 1) * ct_stride + ct_words;
-    const size_t sk_span = (cipher_size - 2) * (size_t)c.size_qp * c.n + ln;
-    if (overlaps(dst, dst_span, sk_powers, sk_span)) throw std::invalid_argument("dst must not overlap sk_powers");
-    const bool in_place = in_place_ok && dst == ct && (batch == 1 || dst_stride == ct_stride);   // result b takes c0 (b)'s place
-    if (!in_place && overlaps(dst, dst_span, ct, ct_span)) throw std::invalid_argument("dst must not overlap ct");
-}
-
-static void decrypt_strict(Context &c, const char *ct_name, const char *sk_name, size_t size_Ql, const u64 *ct, size_t cipher_size,
-                           size_t batch, size_t ct_stride, const u64 *sk_powers, hipStream_t s) {
+// strict mode of the entries over a CtBatch (what they refuse: check_decrypt / check_noise_budget of pha_layout.h)
+void decrypt_strict(Context &c, const char *entry, size_t size_Ql, const CtBatch &b, hipStream_t s) {
     if (!strict_mode()) return;
-    const size_t ln = size_Ql * c.n;
-    for (size_t b = 0; b < batch; b++) strict_operand(c, ct_name, ct + b * ct_stride, rows_plain(0, size_Ql), (uint32_t)cipher_size, ln, s);
-    strict_operand(c, sk_name, sk_powers, rows_plain(0, size_Ql), (uint32_t)(cipher_size - 1), (size_t)c.size_qp * c.n, s);
+    const std::string ct_name = std::string(entry) + " ct", sk_name = std::string(entry) + " sk_powers";
+    for (size_t i = 0; i < b.batch; i++)
+        strict_operand(c, ct_name.c_str(), b.ct + i * b.ct_stride, rows_plain(0, size_Ql), (uint32_t)b.cipher_size, size_Ql * c.n, s);
+    strict_operand(c, sk_name.c_str(), b.sk_powers, rows_plain(0, size_Ql), (uint32_t)(b.cipher_size - 1), (size_t)c.size_qp * c.n, s);
 }
 
 // the inverse correction factors of a batch, mod t: every factor is validated before anything is launched
@@ -215,17 +224,38 @@ static std::vector<u64> invert_factors(Context &c, const uint64_t *factors, size
     return inv;
 }
 
+// the two entries that decrypt to a plain modulus: the phase front end per chunk, then the bgv tail (factors may be null) or the bfv tail
+static void decrypt_to_plain(Context &c, bool bfv, size_t size_Ql, const CtBatch &b, const uint64_t *factors, u64 *dst, size_t dst_stride,
+                             size_t chunk, void *stream) {
+    check_decrypt(shape(c), size_Ql, b, dst, dst_stride, c.n, false, true);
+    const std::vector<u64> inv = invert_factors(c, factors, b.batch);
+    if (b.batch == 0) return;
+    hipStream_t s = as_stream(stream);
+    decrypt_strict(c, bfv ? "bfv_decrypt" : "bgv_decrypt", size_Ql, b, s);
+    DecryptLevel &d = c.decrypt_level((uint32_t)size_Ql);
+    const PhaseChunk pc = phase_chunk(!bfv, b.cipher_size, size_Ql * c.n, b.batch, chunk, kDecryptChunk);
+    u64 *work = c.scratch_outer(stream, pc.C * pc.wst);
+    for (size_t b0 = 0; b0 < b.batch; b0 += pc.C) {
+        const size_t B = std::min(pc.C, b.batch - b0);
+        phase_to_coeff(c, size_Ql, !bfv, CtBatch{b.ct + b0 * b.ct_stride, b.cipher_size, B, b.ct_stride, b.sk_powers, b.n_powers}, work, pc.wst, s);
+        if (bfv) launch_scale_round(c, d, dst + b0 * dst_stride, dst_stride, work, pc.wst, B, s);   // floor(t x / Q + 1/2) mod t
+        else launch_mod_t(c, d, dst + b0 * dst_stride, dst_stride, work, pc.wst, B, inv.empty() ? nullptr : inv.data() + b0, s);
+    }
+}
+
+// the two DRNSTool launchers on ONE polynomial: what they refuse, strict mode, the level's tables
+static DecryptLevel &one_polynomial(Context &c, const char *src_name, size_t size_Ql, const u64 *dst, const u64 *src, hipStream_t s) {
+    need(dst); need(src);
+    check_rns_level(size_Ql, c.size_q);
+    DecryptLevel &d = c.decrypt_level((uint32_t)size_Ql);
+    if (overlaps(dst, c.n, src, size_Ql * c.n)) throw std::invalid_argument("dst must not overlap src");
+    strict_operand(c, src_name, src, rows_plain(0, size_Ql), 1, 0, s);
+    return d;
+}
+
 }  // namespace pha
 
 using namespace pha;
-
-static void rc(int status) {   // an inner ABI call failed: re-raise with its own category
-    if (status == 0) return;
-    const std::string what = pha_last_error();
-    if (status == -1) throw std::invalid_argument(what);
-    if (status == -2) throw std::logic_error(what);
-    throw std::runtime_error(what);
-}
 
 extern "C" {
 
@@ -248,10 +278,11 @@ int pha_decrypt_phase_batched(pha_context_t ctx, size_t size_Ql, const uint64_t 
     PHA_CTX_BEGIN(ctx)
     Context &c = ctx->c;
     const size_t ln = size_Ql * c.n;
-    decrypt_check(c, size_Ql, ct, cipher_size, batch, ct_stride, sk_powers, n_powers, dst, dst_stride, ln, true, false);
+    const CtBatch b{ct, cipher_size, batch, ct_stride, sk_powers, n_powers};
+    check_decrypt(shape(c), size_Ql, b, dst, dst_stride, ln, true, false);
     if (batch == 0) return 0;
     hipStream_t s = as_stream(stream);
-    decrypt_strict(c, "decrypt_phase ct", "decrypt_phase sk_powers", size_Ql, ct, cipher_size, batch, ct_stride, sk_powers, s);
+    decrypt_strict(c, "decrypt_phase", size_Ql, b, s);
     launch_phase(c, size_Ql, ct, ct + ln, cipher_size, batch, ct_stride, sk_powers, dst, dst_stride, s);
     PHA_API_END
 }
@@ -260,95 +291,28 @@ int pha_bgv_decrypt_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *c
                             const uint64_t *sk_powers, size_t n_powers, const uint64_t *correction_factors, uint64_t *dst,
                             size_t dst_stride, size_t chunk, void *stream) {
     PHA_CTX_BEGIN(ctx)
-    Context &c = ctx->c;
-    decrypt_check(c, size_Ql, ct, cipher_size, batch, ct_stride, sk_powers, n_powers, dst, dst_stride, c.n, false, true);
-    const std::vector<u64> inv = invert_factors(c, correction_factors, batch);
-    if (batch == 0) return 0;
-    hipStream_t s = as_stream(stream);
-    decrypt_strict(c, "bgv_decrypt ct", "bgv_decrypt sk_powers", size_Ql, ct, cipher_size, batch, ct_stride, sk_powers, s);
-    DecryptLevel &d = c.decrypt_level((uint32_t)size_Ql);
-    const size_t ln = size_Ql * c.n, C = std::min<size_t>(std::min(chunk ? chunk : kDecChunk, batch), 65535);
-    u64 *work = c.scratch_outer(stream, C * ln);
-    for (size_t b0 = 0; b0 < batch; b0 += C) {
-        const size_t B = std::min(C, batch - b0);
-        const u64 *cb = ct + b0 * ct_stride;
-        launch_phase(c, size_Ql, cb, cb + ln, cipher_size, B, ct_stride, sk_powers, work, ln, s);
-        NttExtra x;
-        x.batch = (uint32_t)B;
-        x.poly_stride = ln;
-        ntt_inverse(c, work, work, work, plain_sel(0, size_Ql), EPI_INV_CANON, x, s);
-        launch_mod_t(c, d, dst + b0 * dst_stride, dst_stride, work, ln, B, inv.empty() ? nullptr : inv.data() + b0, s);
-    }
+    decrypt_to_plain(ctx->c, false, size_Ql, CtBatch{ct, cipher_size, batch, ct_stride, sk_powers, n_powers}, correction_factors, dst, dst_stride, chunk, stream);
     PHA_API_END
 }
 
 int pha_bfv_decrypt_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *ct, size_t cipher_size, size_t batch, size_t ct_stride,
                             const uint64_t *sk_powers, size_t n_powers, uint64_t *dst, size_t dst_stride, size_t chunk, void *stream) {
     PHA_CTX_BEGIN(ctx)
-    Context &c = ctx->c;
-    decrypt_check(c, size_Ql, ct, cipher_size, batch, ct_stride, sk_powers, n_powers, dst, dst_stride, c.n, false, true);
-    if (batch == 0) return 0;
-    hipStream_t s = as_stream(stream);
-    decrypt_strict(c, "bfv_decrypt ct", "bfv_decrypt sk_powers", size_Ql, ct, cipher_size, batch, ct_stride, sk_powers, s);
-    DecryptLevel &d = c.decrypt_level((uint32_t)size_Ql);
-    const size_t ln = size_Ql * c.n, km1 = cipher_size - 1, wst = km1 * ln;   // the work buffer: [chunk][k - 1][L][N]
-    const size_t C = std::min<size_t>(std::min(chunk ? chunk : kDecChunk, batch), 65535 / km1 ? 65535 / km1 : 1);
-    u64 *work = c.scratch_outer(stream, C * wst);
-    const LimbSel sel = plain_sel(0, size_Ql);
-    for (size_t b0 = 0; b0 < batch; b0 += C) {
-        const size_t B = std::min(C, batch - b0);
-        const u64 *cb = ct + b0 * ct_stride;
-        // 1. c1 .. c_{k-1} of every ciphertext forward, out of place into the work buffer
-        NttExtra f;
-        f.poly_stride = ln;
-        if (km1 == 1 || B == 1) {   // one polynomial per ciphertext, or one ciphertext: the polynomials are evenly spaced
-            f.batch = (uint32_t)(B * km1);
-            f.in_stride = km1 == 1 ? ct_stride : ln;
-            ntt_forward(c, cb + ln, work, work, sel, EPI_FWD_CANON, f, s);
-        } else {
-            f.batch = (uint32_t)km1;
-            f.in_stride = ln;
-            for (size_t g = 0; g < B; g++) ntt_forward(c, cb + g * ct_stride + ln, work + g * wst, work + g * wst, sel, EPI_FWD_CANON, f, s);
-        }
-        // 2. the phase without c0; result b takes the place of its own c1 in the work buffer (a thread reads its words before it writes)
-        launch_phase(c, size_Ql, nullptr, work, cipher_size, B, wst, sk_powers, work, wst, s);
-        // 3. back to coefficient form in place, c0 (b) added in the final store
-        NttExtra x;
-        x.batch = (uint32_t)B;
-        x.poly_stride = wst;
-        x.aux = cb;
-        x.aux_stride = ct_stride ? ct_stride : wst;   // (B == 1 with stride 0: unused)
-        x.aux_pair_stride = 2 * ct_stride;            // polynomial z adds c0 of ciphertext z: (z / 2) * 2 stride + (z % 2) * stride
-        ntt_inverse(c, work, work, work, sel, EPI_INV_CANON_ADD, x, s);
-        // 4. floor(t x / Q + 1/2) mod t
-        launch_scale_round(c, d, dst + b0 * dst_stride, dst_stride, work, wst, B, s);
-    }
+    decrypt_to_plain(ctx->c, true, size_Ql, CtBatch{ct, cipher_size, batch, ct_stride, sk_powers, n_powers}, nullptr, dst, dst_stride, chunk, stream);
     PHA_API_END
 }
 
 int pha_hps_decrypt_scale_and_round(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream) {
     PHA_CTX_BEGIN(ctx)   // DRNSTool::hps_decrypt_scale_and_round src/rns.cu:1519-1689, the one form of pha_decrypt.h
-    need(dst); need(src);
-    Context &c = ctx->c;
-    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("RNSBase is invalid");
-    DecryptLevel &d = c.decrypt_level((uint32_t)size_Ql);
-    if (overlaps(dst, c.n, src, size_Ql * c.n)) throw std::invalid_argument("dst must not overlap src");
     hipStream_t s = as_stream(stream);
-    strict_operand(c, "hps_decrypt_scale_and_round src", src, rows_plain(0, size_Ql), 1, 0, s);
-    launch_scale_round(c, d, dst, 0, src, 0, 1, s);
+    launch_scale_round(ctx->c, one_polynomial(ctx->c, "hps_decrypt_scale_and_round src", size_Ql, dst, src, s), dst, 0, src, 0, 1, s);
     PHA_API_END
 }
 
 int pha_decrypt_mod_t(pha_context_t ctx, size_t size_Ql, uint64_t *dst, const uint64_t *src, void *stream) {
     PHA_CTX_BEGIN(ctx)   // DRNSTool::decrypt_mod_t: base_q_to_t_conv_.exact_convert_array
-    need(dst); need(src);
-    Context &c = ctx->c;
-    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("RNSBase is invalid");
-    DecryptLevel &d = c.decrypt_level((uint32_t)size_Ql);
-    if (overlaps(dst, c.n, src, size_Ql * c.n)) throw std::invalid_argument("dst must not overlap src");
     hipStream_t s = as_stream(stream);
-    strict_operand(c, "decrypt_mod_t src", src, rows_plain(0, size_Ql), 1, 0, s);
-    launch_mod_t(c, d, dst, 0, src, 0, 1, nullptr, s);
+    launch_mod_t(ctx->c, one_polynomial(ctx->c, "decrypt_mod_t src", size_Ql, dst, src, s), dst, 0, src, 0, 1, nullptr, s);
     PHA_API_END
 }
 

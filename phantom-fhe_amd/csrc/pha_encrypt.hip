@@ -26,7 +26,6 @@ namespace pha {
 constexpr int kEncThreads = 256;
 constexpr size_t kEncChunk = 8;          // ciphertexts per set of launches of the asymmetric entry (work buffer: chunk * (5 l + 3 alpha) * N words)
 constexpr size_t kEncPlainChunk = 64;    // bgv, symmetric: plaintexts lifted per launch (work buffer: chunk * l * N words)
-constexpr size_t kEncMaxCount = 65535;   // a launch carries the ciphertext in blockIdx.z
 
 // a ciphertext polynomial of `l` data rows, then `special` special rows: the prime-table row of buffer row y
 struct EncRows {
@@ -213,45 +212,6 @@ static void launch_fused(Context &c, const EncRows &r, int epi, const u64 *e, si
     });
 }
 
-// ---- what the entries refuse, in this order ----------------------------------------------------------------------------------------
-static int check_scheme(Context &c, int scheme) {
-    ntt_domain_scheme(scheme);   // throws on anything but ckks / bgv / bfv
-    if (scheme != PHA_SCHEME_CKKS && !c.plain_t) throw std::invalid_argument("the context has no plain modulus (pha_context_set_plain_modulus)");
-    return scheme;
-}
-static void check_rows(Context &c, size_t size_Ql, bool special) {
-    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("RNSBase is invalid");
-    if (special && c.size_p == 0) throw std::invalid_argument("context has no special modulus");
-    for (uint32_t y = 0; y < size_Ql + (special ? c.size_p : 0); y++)
-        if ((c.primes[y < size_Ql ? y : c.size_q + (y - size_Ql)] >> (kSmallMinPrimeBits - 1)) == 0)
-            throw std::invalid_argument("a sample of magnitude 2^16 needs every prime of the rows used at or above 2^17");
-}
-struct EncBuf {
-    const char *name;
-    const u64 *p;
-    size_t words, stride;   // one element, and the words between consecutive elements (0: shared)
-    bool may_share;         // a stride of 0 is allowed
-};
-static size_t span(const EncBuf &b, size_t count) { return count ? (b.stride ? (count - 1) * b.stride : 0) + b.words : 0; }
-// ct: the results; ins: what is read.  Strides, alignment, overlap -- nothing else
-static void check_layout(const EncBuf &ct, std::initializer_list<EncBuf> ins, size_t count) {
-    if (count > kEncMaxCount) throw std::invalid_argument("count out of range");
-    if (count > 1 && ct.stride < ct.words) throw std::invalid_argument("ct stride below the size of a ciphertext: the ciphertexts overlap");
-    uintptr_t bits = reinterpret_cast<uintptr_t>(ct.p);
-    size_t strides = ct.stride;
-    for (const EncBuf &b : ins) {
-        if (count > 1 && b.stride < b.words && !(b.may_share && b.stride == 0))
-            throw std::invalid_argument(std::string(b.name) + " stride below the size of an element: the elements overlap");
-        bits |= reinterpret_cast<uintptr_t>(b.p);
-        strides |= b.stride;
-    }
-    if (strides & 1) throw std::invalid_argument("strides must be even (16-byte loads)");
-    if (bits & 15) throw std::invalid_argument("buffers must be 16-byte aligned");
-    if (count == 0) return;
-    for (const EncBuf &b : ins)
-        if (overlaps(ct.p, span(ct, count), b.p, span(b, count))) throw std::invalid_argument(std::string("ct must not overlap ") + b.name);
-}
-
 // strict mode: the uniform words found in c1's place, over the rows of r
 static void strict_a(Context &c, const char *what, const EncRows &r, const u64 *ct, size_t ct_stride, size_t count, hipStream_t s) {
     const RowMap rows = r.special ? rows_qlp(r.l, c.size_q, c.size_p) : rows_plain(0, r.l);
@@ -267,6 +227,17 @@ static void strict_plaintext(Context &c, const char *what, int scheme, size_t l,
     else strict_plain(c, what, plain, c.plain_t, polys, plain_stride, s);
 }
 
+// bgv: NTT(m mod q_i) of `polys` plaintexts of [N] words below t into work [polys][l][N] (pha_bgv_lift_plain for a chunk: every limb
+// reduces the same N words modulo its own prime on load)
+static void lift_plain(Context &c, size_t size_Ql, const u64 *plain, size_t plain_stride, u64 *work, size_t polys, hipStream_t s) {
+    NttExtra x;
+    x.batch = (uint32_t)polys;
+    x.poly_stride = size_Ql * c.n;
+    x.pro_src = plain;
+    x.pro_stride = plain_stride;
+    ntt_forward(c, work, work, work, plain_sel(0, size_Ql), EPI_FWD_CANON, x, s);
+}
+
 // the zero encryption of B ciphertexts over the rows of r, in place of ct (c1 holds a): NTT form with the optional NTT-form plaintext
 // fused, or coefficient form
 static void zero_symmetric(Context &c, const EncRows &r, const u64 *sk, const u64 *e, size_t e_stride, u64 *ct, size_t ct_stride, size_t B,
@@ -278,7 +249,7 @@ static void zero_symmetric(Context &c, const EncRows &r, const u64 *sk, const u6
         return launch_fused(c, r, EPI_FWD_NEG_MULADD, e, e_stride, scheme == PHA_SCHEME_BGV ? c.plain_t : 0, o, ct, cs, B, s);
     }
     launch_mul(c, r, ct, cs, ct + rn, cs, sk, false, B, s);                    // c0 = a (.) s
-    if (cs == 2 * rn && 2 * B <= kEncMaxCount) inverse_polys(c, r, ct, rn, 2 * B, s);   // c0, c1 of every ciphertext lie in a row
+    if (cs == 2 * rn && 2 * B <= kMaxCount) inverse_polys(c, r, ct, rn, 2 * B, s);   // c0, c1 of every ciphertext lie in a row
     else {
         inverse_polys(c, r, ct, cs, B, s);
         inverse_polys(c, r, ct + rn, cs, B, s);
@@ -297,13 +268,8 @@ int pha_encrypt_zero_symmetric_batched(pha_context_t ctx, size_t size_Ql, int wi
                                        void *stream) {
     PHA_CTX_BEGIN(ctx)
     Context &c = ctx->c;
-    need(sk_ntt); need(e); need(ct);
-    check_rows(c, size_Ql, with_special != 0);
-    check_scheme(c, scheme);
+    check_encrypt(shape(c), size_Ql, with_special != 0, false, scheme, sk_ntt, nullptr, 0, e, e_stride, nullptr, 0, 0, ct, ct_stride, count);
     const EncRows r{(uint32_t)size_Ql, with_special ? c.size_p : 0u, c.size_q};
-    const size_t rn = (size_t)r.rows() * c.n;
-    check_layout(EncBuf{"ct", ct, 2 * rn, ct_stride, false},
-                 {EncBuf{"sk_ntt", sk_ntt, (size_t)c.size_qp * c.n, 0, true}, EncBuf{"e", e, c.n, e_stride, false}}, count);
     if (count == 0) return 0;
     hipStream_t s = as_stream(stream);
     strict_key(c, "encrypt_zero_symmetric sk", r, sk_ntt, 1, s);
@@ -323,14 +289,9 @@ int pha_encrypt_symmetric_batched(pha_context_t ctx, size_t size_Ql, const uint6
                                   void *stream) {
     PHA_CTX_BEGIN(ctx)
     Context &c = ctx->c;
-    need(sk_ntt); need(e); need(plain); need(ct);
-    check_rows(c, size_Ql, false);
-    check_scheme(c, scheme);
-    const EncRows r{(uint32_t)size_Ql, 0u, c.size_q};
     const size_t ln = size_Ql * c.n, pw = scheme == PHA_SCHEME_CKKS ? ln : c.n;
-    check_layout(EncBuf{"ct", ct, 2 * ln, ct_stride, false},
-                 {EncBuf{"sk_ntt", sk_ntt, (size_t)c.size_qp * c.n, 0, true}, EncBuf{"e", e, c.n, e_stride, false},
-                  EncBuf{"plain", plain, pw, plain_stride, true}}, count);
+    check_encrypt(shape(c), size_Ql, false, false, scheme, sk_ntt, nullptr, 0, e, e_stride, plain, pw, plain_stride, ct, ct_stride, count);
+    const EncRows r{(uint32_t)size_Ql, 0u, c.size_q};
     if (count == 0) return 0;
     hipStream_t s = as_stream(stream);
     strict_key(c, "encrypt_symmetric sk", r, sk_ntt, 1, s);
@@ -345,14 +306,7 @@ int pha_encrypt_symmetric_batched(pha_context_t ctx, size_t size_Ql, const uint6
         u64 *work = c.scratch_outer(stream, (shared ? 1 : C) * ln);
         for (size_t b0 = 0; b0 < count; b0 += C) {
             const size_t B = std::min(C, count - b0);
-            if (b0 == 0 || !shared) {
-                NttExtra x;   // pha_bgv_lift_plain for the chunk: every limb reduces the same N words modulo its own prime on load
-                x.batch = (uint32_t)(shared ? 1 : B);
-                x.poly_stride = ln;
-                x.pro_src = plain + b0 * plain_stride;
-                x.pro_stride = plain_stride;
-                ntt_forward(c, work, work, work, plain_sel(0, size_Ql), EPI_FWD_CANON, x, s);
-            }
+            if (b0 == 0 || !shared) lift_plain(c, size_Ql, plain + b0 * plain_stride, plain_stride, work, shared ? 1 : B, s);
             zero_symmetric(c, r, sk_ntt, e + b0 * e_stride, e_stride, ct + b0 * ct_stride, ct_stride, B, scheme, true, work, shared ? 0 : ln, s);
         }
     } else {                                  // bfv: coefficient form, then multiply_add_plain_with_scaling_variant
@@ -367,14 +321,9 @@ int pha_encrypt_asymmetric_batched(pha_context_t ctx, size_t size_Ql, const uint
                                    size_t ct_stride, size_t count, int scheme, size_t chunk, void *stream) {
     PHA_CTX_BEGIN(ctx)
     Context &c = ctx->c;
-    need(pk); need(u); need(e); need(plain); need(ct);
-    check_rows(c, size_Ql, true);
-    check_scheme(c, scheme);
     const EncRows r{(uint32_t)size_Ql, c.size_p, c.size_q};
     const size_t n = c.n, ln = size_Ql * n, rn = (size_t)r.rows() * n, pw = scheme == PHA_SCHEME_CKKS ? ln : n;
-    check_layout(EncBuf{"ct", ct, 2 * ln, ct_stride, false},
-                 {EncBuf{"pk", pk, 2 * (size_t)c.size_qp * n, 0, true}, EncBuf{"u", u, n, u_stride, false}, EncBuf{"e", e, 2 * n, e_stride, false},
-                  EncBuf{"plain", plain, pw, plain_stride, true}}, count);
+    check_encrypt(shape(c), size_Ql, true, true, scheme, pk, u, u_stride, e, e_stride, plain, pw, plain_stride, ct, ct_stride, count);
     if (count == 0) return 0;
     hipStream_t s = as_stream(stream);
     strict_key(c, "encrypt_asymmetric pk", r, pk, 2, s);
@@ -414,14 +363,7 @@ int pha_encrypt_asymmetric_batched(pha_context_t ctx, size_t size_Ql, const uint
         const u64 *pb = plain + b0 * plain_stride;
         const size_t cs = B > 1 ? ct_stride : 2 * ln;
         if (bgv) {
-            if (b0 == 0 || !shared) {
-                NttExtra x;
-                x.batch = (uint32_t)(shared ? 1 : B);
-                x.poly_stride = ln;
-                x.pro_src = pb;
-                x.pro_stride = plain_stride;
-                ntt_forward(c, pl, pl, pl, plain_sel(0, size_Ql), EPI_FWD_CANON, x, s);
-            }
+            if (b0 == 0 || !shared) lift_plain(c, size_Ql, pb, plain_stride, pl, shared ? 1 : B, s);
             launch_plain(c, size_Ql, cb, cs, pl, shared ? 0 : ln, true, B, s);
         } else {
             launch_plain(c, size_Ql, cb, cs, pb, plain_stride, ntt_form, B, s);

@@ -16,6 +16,7 @@
 
 #include "pha_arith.h"
 #include "pha_rns_tables.h"
+#include "pha_layout.h"        // the host-only argument checks of the secret-key layer: ContextShape, EncBuf, check_layout()
 #include "pha_sum_operand.h"   // overlaps(), SumOperand
 
 namespace pha {
@@ -513,16 +514,19 @@ struct KsScratch {
     KsScratch(u64 *base, const Context &c, const Tool &t, size_t B) : KsScratch(base, t.size_ql, t.size_qlp, t.beta, c.n, B) {}
 };
 
-// the phase kernel of pha_decrypt.hip, launch only (the caller has validated): dst (b) = c0 (b) + sum_i c_i (b) (.) s^i over NTT-form
-// operands, polynomial i >= 1 of ciphertext b at c1 + b * ct_stride + (i - 1) * L * N; c0 == null drops it
+// the phase front end of pha_decrypt.hip, launch only (the caller has validated): the phase c0 (b) + sum_i c_i (b) (.) s^i of the B
+// ciphertexts of `chunk` is left in COEFFICIENT form at work + b * wst, wst as phase_chunk() (pha_layout.h) gives it
 constexpr size_t kDecryptChunk = 8;   // ciphertexts per set of launches of the chunked entries (0 = this default)
-void launch_phase(Context &c, size_t size_Ql, const u64 *c0, const u64 *c1, size_t cipher_size, size_t batch, size_t ct_stride,
-                  const u64 *sk, u64 *dst, size_t dst_stride, hipStream_t s);
-bool ntt_domain_scheme(int scheme);   // ckks / bgv: true, bfv: false; throws on anything else
+void phase_to_coeff(Context &c, size_t size_Ql, bool ntt_form, const CtBatch &chunk, u64 *work, size_t wst, hipStream_t s);
+void decrypt_strict(Context &c, const char *entry, size_t size_Ql, const CtBatch &b, hipStream_t s);   // names "<entry> ct", "<entry> sk_powers"
 void check_level(Context &c, size_t size_Ql, bool need_p);
-// argument checks shared by the entry points
-inline void need(const void *p) {
-    if (!p) throw std::invalid_argument("null device pointer");
+inline ContextShape shape(const Context &c) { return ContextShape{c.n, c.size_q, c.size_p, c.size_qp, c.plain_t, c.primes.data()}; }
+inline void rc(int status) {   // an inner ABI call failed: re-raise with its own category
+    if (status == 0) return;
+    const std::string what = pha_last_error();
+    if (status == -1) throw std::invalid_argument(what);
+    if (status == -2) throw std::logic_error(what);
+    throw std::runtime_error(what);
 }
 inline void check_galois_elt(const Context &c, uint32_t elt) {
     if (!(elt & 1) || elt >= 2 * c.n) throw std::invalid_argument("Galois element is not valid");

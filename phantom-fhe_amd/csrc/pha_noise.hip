@@ -12,7 +12,6 @@
 // to binary (Horner, L-word arithmetic in LDS) and writes norm, bits and the budget.  No atomics: the result does not depend on the
 // order in which workgroups run.
 #include "../../include/phantom_amd.h"
-#include "pha_decrypt.h"
 #include "pha_internal.h"
 #include "pha_noise.h"
 #include "pha_ntt_core.h"
@@ -144,10 +143,6 @@ NoiseLevel &Context::noise_level(uint32_t size_ql) {
     return *(noise_levels[size_ql] = std::move(d));
 }
 
-static void check_noise_level(Context &c, size_t size_Ql) {
-    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("RNSBase is invalid");
-    if (size_Ql > kNoiseMaxLimbs) throw std::invalid_argument("the noise entries take levels of at most 64 limbs");
-}
 static size_t norm_cand_words(Context &c, size_t size_Ql, size_t count) { return count * (c.n / norm_threads(size_Ql, c.n)) * size_Ql; }
 
 // launch only: `count` <= 65535 polynomials [L][N] at src + z * src_stride -> norm / bits / budget (each may be null) at index z
@@ -169,25 +164,14 @@ static void launch_norm(Context &c, size_t size_Ql, const u64 *src, size_t count
 
 using namespace pha;
 
-static const uint64_t *as_words(const void *p) { return reinterpret_cast<const uint64_t *>(p); }
-
 extern "C" {
 
 int pha_poly_infty_norm_batched(pha_context_t ctx, size_t size_Ql, const uint64_t *src, size_t count, size_t src_stride,
                                 uint64_t scalar, uint64_t *norm, uint32_t *bits, void *stream) {
     PHA_CTX_BEGIN(ctx)
     Context &c = ctx->c;
-    need(src); need(bits);
-    check_noise_level(c, size_Ql);
-    const size_t ln = size_Ql * c.n;
-    if (count > 1 && src_stride < ln) throw std::invalid_argument("src stride below L * N: the polynomials overlap");
-    if ((reinterpret_cast<uintptr_t>(norm) & 7) || (reinterpret_cast<uintptr_t>(bits) & 3) || (reinterpret_cast<uintptr_t>(src) & 7))
-        throw std::invalid_argument("buffers must be aligned to their words");
+    check_poly_norm(shape(c), size_Ql, src, count, src_stride, norm, bits, kNoiseMaxLimbs);
     if (count == 0) return 0;
-    const size_t src_span = (count - 1) * src_stride + ln;
-    if (norm && overlaps(norm, count * size_Ql, src, src_span)) throw std::invalid_argument("norm must not overlap src");
-    if (overlaps(as_words(bits), (count + 1) / 2, src, src_span)) throw std::invalid_argument("bits must not overlap src");
-    if (norm && overlaps(as_words(bits), (count + 1) / 2, norm, count * size_Ql)) throw std::invalid_argument("bits must not overlap norm");
     hipStream_t s = as_stream(stream);
     if (strict_mode())
         for (size_t z0 = 0; z0 < count; z0 += 65535)
@@ -206,68 +190,18 @@ int pha_invariant_noise_budget_batched(pha_context_t ctx, size_t size_Ql, const 
                                        void *stream) {
     PHA_CTX_BEGIN(ctx)
     Context &c = ctx->c;
-    // the refusals of the decrypt entries (pha_decrypt.hip decrypt_check), in their order, then this entry's own
-    need(ct); need(sk_powers); need(budget);
-    const bool ntt_form = ntt_domain_scheme(scheme);   // refuses an unknown scheme
-    check_noise_level(c, size_Ql);
-    if (scheme != PHA_SCHEME_CKKS && !c.plain_t) throw std::invalid_argument("the context has no plain modulus (pha_context_set_plain_modulus)");
-    if (cipher_size < 2 || cipher_size > 65535) throw std::invalid_argument("cipher_size out of range");
-    if (n_powers < cipher_size - 1) throw std::invalid_argument("sk_powers holds fewer powers than the ciphertext has polynomials beyond c0");
-    if (batch > (size_t)kPhaseGroup * 65535)throw std::invalid_argument("batch out of range");
-    const size_t ln = size_Ql * c.n, ct_words = cipher_size * ln;
-    if (batch > 1 && ct_stride < ct_words) throw std::invalid_argument("ct stride below cipher_size * L * N: the ciphertexts overlap");
-    if (ct_stride & 1) throw std::invalid_argument("strides must be even (16-byte loads)");
-    if ((reinterpret_cast<uintptr_t>(ct) | reinterpret_cast<uintptr_t>(sk_powers)) & 15) throw std::invalid_argument("buffers must be 16-byte aligned");
-    if ((reinterpret_cast<uintptr_t>(budget) & 3) || (reinterpret_cast<uintptr_t>(norm) & 7)) throw std::invalid_argument("buffers must be aligned to their words");
+    const CtBatch b{ct, cipher_size, batch, ct_stride, sk_powers, n_powers};
+    const bool ntt_form = check_noise_budget(shape(c), size_Ql, b, scheme, budget, norm, kNoiseMaxLimbs);
     if (batch == 0) return 0;
-    const size_t ct_span = (batch - 1) * ct_stride + ct_words, sk_span = (cipher_size - 2) * (size_t)c.size_qp * c.n + ln;
-    const size_t budget_words = (batch + 1) / 2, norm_words = batch * size_Ql;
-    if (overlaps(as_words(budget), budget_words, ct, ct_span)) throw std::invalid_argument("budget must not overlap ct");
-    if (overlaps(as_words(budget), budget_words, sk_powers, sk_span)) throw std::invalid_argument("budget must not overlap sk_powers");
-    if (norm && overlaps(norm, norm_words, ct, ct_span)) throw std::invalid_argument("norm must not overlap ct");
-    if (norm && overlaps(norm, norm_words, sk_powers, sk_span)) throw std::invalid_argument("norm must not overlap sk_powers");
-    if (norm && overlaps(norm, norm_words, as_words(budget), budget_words)) throw std::invalid_argument("norm must not overlap budget");
     hipStream_t s = as_stream(stream);
-    if (strict_mode()) {
-        for (size_t b = 0; b < batch; b++) strict_operand(c, "noise_budget ct", ct + b * ct_stride, rows_plain(0, size_Ql), (uint32_t)cipher_size, ln, s);
-        strict_operand(c, "noise_budget sk_powers", sk_powers, rows_plain(0, size_Ql), (uint32_t)(cipher_size - 1), (size_t)c.size_qp * c.n, s);
-    }
-    const size_t km1 = cipher_size - 1, wst = ntt_form ? ln : km1 * ln;   // the work buffer: [chunk][L][N], bfv [chunk][k - 1][L][N]
-    const size_t C = std::min<size_t>(std::min(chunk ? chunk : kDecryptChunk, batch), ntt_form ? 65535 : (65535 / km1 ? 65535 / km1 : 1));
-    u64 *work = c.scratch_outer(stream, C * wst + norm_cand_words(c, size_Ql, C)), *cand = work + C * wst;
-    const LimbSel sel = plain_sel(0, size_Ql);
+    decrypt_strict(c, "noise_budget", size_Ql, b, s);
+    const PhaseChunk pc = phase_chunk(ntt_form, cipher_size, size_Ql * c.n, batch, chunk, kDecryptChunk);
+    u64 *work = c.scratch_outer(stream, pc.C * pc.wst + norm_cand_words(c, size_Ql, pc.C)), *cand = work + pc.C * pc.wst;
     const u64 scalar = scheme == PHA_SCHEME_BFV ? c.plain_t : 1;   // invariant_noise_budget multiplies by t under bfv only
-    for (size_t b0 = 0; b0 < batch; b0 += C) {
-        const size_t B = std::min(C, batch - b0);
-        const u64 *cb = ct + b0 * ct_stride;
-        if (ntt_form) {   // pha_bgv_decrypt_batched up to its inverse transform
-            launch_phase(c, size_Ql, cb, cb + ln, cipher_size, B, ct_stride, sk_powers, work, ln, s);
-            NttExtra x;
-            x.batch = (uint32_t)B;
-            x.poly_stride = ln;
-            ntt_inverse(c, work, work, work, sel, EPI_INV_CANON, x, s);
-        } else {          // pha_bfv_decrypt_batched up to its scale-and-round
-            NttExtra f;
-            f.poly_stride = ln;
-            if (km1 == 1 || B == 1) {
-                f.batch = (uint32_t)(B * km1);
-                f.in_stride = km1 == 1 ? ct_stride : ln;
-                ntt_forward(c, cb + ln, work, work, sel, EPI_FWD_CANON, f, s);
-            } else {
-                f.batch = (uint32_t)km1;
-                f.in_stride = ln;
-                for (size_t g = 0; g < B; g++) ntt_forward(c, cb + g * ct_stride + ln, work + g * wst, work + g * wst, sel, EPI_FWD_CANON, f, s);
-            }
-            launch_phase(c, size_Ql, nullptr, work, cipher_size, B, wst, sk_powers, work, wst, s);
-            NttExtra x;
-            x.batch = (uint32_t)B;
-            x.poly_stride = wst;
-            x.aux = cb;
-            x.aux_stride = ct_stride ? ct_stride : wst;
-            x.aux_pair_stride = 2 * ct_stride;
-            ntt_inverse(c, work, work, work, sel, EPI_INV_CANON_ADD, x, s);
-        }
-        launch_norm(c, size_Ql, work, B, wst, scalar, cand, norm ? norm + b0 * size_Ql : nullptr, nullptr, budget + b0, s);
+    for (size_t b0 = 0; b0 < batch; b0 += pc.C) {
+        const size_t B = std::min(pc.C, batch - b0);
+        phase_to_coeff(c, size_Ql, ntt_form, CtBatch{ct + b0 * ct_stride, cipher_size, B, ct_stride, sk_powers, n_powers}, work, pc.wst, s);
+        launch_norm(c, size_Ql, work, B, pc.wst, scalar, cand, norm ? norm + b0 * size_Ql : nullptr, nullptr, budget + b0, s);
     }
     PHA_API_END
 }

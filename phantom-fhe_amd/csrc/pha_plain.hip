@@ -10,13 +10,6 @@
 
 using namespace pha;
 
-static void rc(int status) {   // an inner ABI call failed: re-raise with its own category
-    if (status == 0) return;
-    const std::string what = pha_last_error();
-    if (status == -1) throw std::invalid_argument(what);
-    if (status == -2) throw std::logic_error(what);
-    throw std::runtime_error(what);
-}
 static Tool &plain_tool(Context &c, size_t size_Ql) {
     if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("RNSBase is invalid");
     if (!c.plain_t) throw std::invalid_argument("the context has no plain modulus (pha_context_set_plain_modulus)");

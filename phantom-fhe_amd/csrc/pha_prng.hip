@@ -19,7 +19,7 @@
 namespace pha {
 
 constexpr int kPrngThreads = 256;
-constexpr size_t kPrngMaxCount = 65535;   // a launch carries the polynomial in blockIdx.z
+static_assert(kPrngGroupWords == 8, "check_degree() of pha_layout.h refuses a degree below one generator block");
 
 // polynomial z: seed at seeds + z * seed_stride bytes, output at out + z * out_stride words.  cms == 0: [N] signed words;
 // else [cms][N] canonical residues modulo mod[mod_start + y]
@@ -102,45 +102,17 @@ static void launch_uniform(Context &c, u64 *out, size_t out_stride, const uint8_
     check_launch();
 }
 
-// ---- what the entries refuse -------------------------------------------------------------------------------------------------------
-static void check_degree(Context &c) {
-    if (c.n < (size_t)kPrngGroupWords) throw std::invalid_argument("poly_modulus_degree below 8: a generator block is eight words");
-}
-static void check_aligned(const void *a, const void *b) {
-    if ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15) throw std::invalid_argument("buffers must be 16-byte aligned");
-}
-// rows [mod_start, mod_start + cms) of the context's QP table; small: every prime must exceed the largest sample magnitude
-static void check_ref_rows(Context &c, size_t cms, size_t mod_start, bool small) {
-    if (cms < 1 || mod_start > c.size_qp || cms > c.size_qp - mod_start) throw std::invalid_argument("RNSBase is invalid");
-    if (cms > kPrngMaxCount) throw std::invalid_argument("coeff_mod_size out of range");
-    for (size_t y = 0; small && y < cms; y++)
-        if (c.primes[mod_start + y] <= 21) throw std::invalid_argument("a sample of magnitude 21 needs every prime of the rows used above 21");
-}
-static void check_batch(size_t count, size_t words, size_t stride) {
-    if (count > kPrngMaxCount) throw std::invalid_argument("count out of range");
-    if (stride & 1) throw std::invalid_argument("strides must be even (16-byte stores)");
-    if (count > 1 && stride < words) throw std::invalid_argument("out stride below the size of an element: the elements overlap");
-}
+// ---- what the entries refuse: check_sample_ref, check_sample_batch, check_kswitch of pha_layout.h --------------------------------------
 static void sample_ref(pha_context_t ctx, bool ternary, uint64_t *out, const uint8_t *seed, size_t cms, size_t mod_start, void *stream) {
     Context &c = ctx->c;
-    need(out); need(seed);
-    check_degree(c);
-    check_ref_rows(c, cms, mod_start, !ternary);
-    check_aligned(out, seed);
+    check_sample_ref(shape(c), out, seed, cms, mod_start, ternary ? 0 : kNoiseMinPrime);
     launch_small(c, ternary, out, 0, seed, 0, 1, (uint32_t)cms, (uint32_t)mod_start, as_stream(stream));
 }
 static void sample_signed(pha_context_t ctx, bool ternary, const uint8_t *seeds, size_t count, uint64_t *out, size_t out_stride, void *stream) {
     Context &c = ctx->c;
-    need(seeds); need(out);
-    check_degree(c);
-    check_batch(count, c.n, out_stride);
-    check_aligned(out, seeds);
+    check_sample_batch(shape(c), false, 0, false, seeds, count, out, out_stride);
     if (count == 0) return;
     launch_small(c, ternary, out, out_stride, seeds, kPrngSeedBytes, count, 0, 0, as_stream(stream));
-}
-static void check_uniform_rows(Context &c, size_t size_Ql, bool special) {
-    if (size_Ql < 1 || size_Ql > c.size_q) throw std::invalid_argument("RNSBase is invalid");
-    if (special && c.size_p == 0) throw std::invalid_argument("context has no special modulus");
 }
 
 }  // namespace pha
@@ -175,10 +147,7 @@ int pha_sample_error_poly(pha_context_t ctx, uint64_t *out, const uint8_t *seed,
 int pha_sample_uniform_poly(pha_context_t ctx, uint64_t *out, const uint8_t *seed, size_t coeff_mod_size, size_t mod_start_idx, void *stream) {
     PHA_CTX_BEGIN(ctx)
     Context &c = ctx->c;
-    need(out); need(seed);
-    check_degree(c);
-    check_ref_rows(c, coeff_mod_size, mod_start_idx, false);
-    check_aligned(out, seed);
+    check_sample_ref(shape(c), out, seed, coeff_mod_size, mod_start_idx, 0);
     launch_uniform(c, out, 0, seed, 0, 1, (uint32_t)coeff_mod_size, 0, (uint32_t)mod_start_idx, as_stream(stream));
     PHA_API_END
 }
@@ -199,12 +168,8 @@ int pha_sample_uniform_batched(pha_context_t ctx, size_t size_Ql, int with_speci
                                size_t out_stride, void *stream) {
     PHA_CTX_BEGIN(ctx)
     Context &c = ctx->c;
-    need(seeds); need(out);
-    check_degree(c);
-    check_uniform_rows(c, size_Ql, with_special != 0);
+    check_sample_batch(shape(c), true, size_Ql, with_special != 0, seeds, count, out, out_stride);
     const uint32_t special = with_special ? c.size_p : 0u;
-    check_batch(count, (size_Ql + special) * c.n, out_stride);
-    check_aligned(out, seeds);
     if (count == 0) return 0;
     launch_uniform(c, out, out_stride, seeds, kPrngSeedBytes, count, (uint32_t)size_Ql, special, 0, as_stream(stream));
     PHA_API_END
@@ -223,34 +188,18 @@ int pha_generate_kswitch_keys_seeded(pha_context_t ctx, const uint64_t *sk_ntt, 
                                      void *stream) {
     PHA_CTX_BEGIN(ctx)
     Context &c = ctx->c;
-    need(sk_ntt); need(new_keys_ntt); need(seeds); need(evk);
-    check_degree(c);
-    if (c.size_p == 0) throw std::invalid_argument("context has no special modulus");
-    if (c.size_q % c.size_p) throw std::invalid_argument("#Q must be a multiple of special_modulus_size");
-    const bool bgv = ntt_domain_scheme(scheme) && scheme == PHA_SCHEME_BGV;   // validates the scheme
-    Tool &t = c.tool(c.size_q);
-    if (bgv && !t.bgv_ready) throw std::invalid_argument("bgv needs a plain modulus (pha_context_set_plain_modulus)");
-    const size_t n = c.n, dnum = c.size_q / c.size_p, qp_n = (size_t)c.size_qp * n, q_n = (size_t)c.size_q * n;
-    if (n_keys > kPrngMaxCount / dnum) throw std::invalid_argument("n_keys out of range");
-    const size_t count = n_keys * dnum;
-    if ((evk_stride | new_key_stride) & 1) throw std::invalid_argument("strides must be even (16-byte stores)");
-    if (count > 1 && evk_stride < 2 * qp_n) throw std::invalid_argument("evk stride below 2 * size_QP * N: the components overlap");
-    if (n_keys > 1 && new_key_stride < q_n) throw std::invalid_argument("new_key stride below size_Q * N: the keys overlap");
-    check_aligned(evk, seeds);
-    check_aligned(sk_ntt, new_keys_ntt);
+    const size_t dnum = check_kswitch(shape(c), sk_ntt, new_keys_ntt, n_keys, new_key_stride, seeds, evk, evk_stride, scheme,
+                                      [&] { return c.tool(c.size_q).bgv_ready; });
+    const size_t n = c.n, qp_n = (size_t)c.size_qp * n, count = n_keys * dnum;
     if (count == 0) return 0;
-    const size_t evk_span = (count - 1) * evk_stride + 2 * qp_n;
-    if (overlaps(evk, evk_span, sk_ntt, qp_n) || overlaps(evk, evk_span, new_keys_ntt, (n_keys - 1) * new_key_stride + q_n))
-        throw std::invalid_argument("evk must not overlap an input");
     hipStream_t s = as_stream(stream);
     // component b = (key, digit): seeds + 128 b = the uniform seed, then the noise seed
     u64 *e = c.scratch_outer(stream, count * n);
     launch_uniform(c, evk + qp_n, evk_stride, seeds, 2 * kPrngSeedBytes, count, c.size_q, c.size_p, 0, s);          // a, where c1 lies
     launch_small(c, false, e, n, seeds + kPrngSeedBytes, 2 * kPrngSeedBytes, count, 0, 0, s);                       // e, [N] signed words
-    const int st = pha_encrypt_zero_symmetric_batched(ctx, c.size_q, 1, sk_ntt, e, n, evk, count > 1 ? evk_stride : 2 * qp_n, count, scheme, 1,
-                                                      stream);                                                       // c0 = -(a s + NTT(k e))
-    if (st != 0) return st;
-    const KeyAddArgs k{evk, new_keys_ntt, t.p_mod_q2.p, c.d_mod.p, evk_stride, new_key_stride, (uint32_t)n, c.size_p, (uint32_t)dnum};
+    rc(pha_encrypt_zero_symmetric_batched(ctx, c.size_q, 1, sk_ntt, e, n, evk, count > 1 ? evk_stride : 2 * qp_n, count, scheme, 1,
+                                          stream));                                                                  // c0 = -(a s + NTT(k e))
+    const KeyAddArgs k{evk, new_keys_ntt, c.tool(c.size_q).p_mod_q2.p, c.d_mod.p, evk_stride, new_key_stride, (uint32_t)n, c.size_p, (uint32_t)dnum};
     hipLaunchKernelGGL(kswitch_add_new_key_kernel, dim3((unsigned)(n / kPrngThreads), c.size_p, (unsigned)count), dim3(kPrngThreads), 0, s, k);
     check_launch();
     PHA_API_END

@@ -851,12 +851,6 @@ __global__ __launch_bounds__(256) void galois_split_kernel(u64 *dst_ct, u64 *dst
 // ------------------------------------------------------------------------------------------------
 // drivers
 // ------------------------------------------------------------------------------------------------
-bool ntt_domain_scheme(int scheme) {
-    if (scheme == PHA_SCHEME_CKKS || scheme == PHA_SCHEME_BGV) return true;
-    if (scheme == PHA_SCHEME_BFV) return false;
-    throw std::invalid_argument("unsupported scheme");
-}
-
 // fused_ip may be passed to modup (pha_internal.h) only for the shapes that have a fused form
 static bool fusable_ip(Context &c, Tool &t) { return t.alpha > 1 && c.log_n >= 14 && c.log_n <= 17 && t.beta <= 4; }
 // r06: batched key switches of the NTT-form schemes leave the digits' own limbs where they are (modup's own_in_place + InnerArgs::own):

@@ -14,6 +14,8 @@ C. end to end against BvScheme.phase + compose of tests/bv_semantics.py: hyb12_a
    product > 0 for BEHZ products on hyb12_a2 and HPS products on c1_bfv4096 -- an HPS product on hyb12_a2 has no room left by the
    CPU pipeline either (margin 0.0012 bits: its auxiliary base sits below the 40-bit limbs, next to a 60-bit one), so there the
    budget is held exactly against the reference, which is 0;
+   the one front end behind three tails: on a strided batch of uniform ciphertexts the budget entry's norm and the decrypt entries'
+   plaintexts equal the single-step entries applied to the phase built from the earlier entries, bfv and bgv, chunk 0, 1, 2;
 D. refusals with poisoned outputs untouched, batch == 0, norm == NULL, strict mode;
 E. workloads.noise_budget_batch gives the C entry's budgets."""
 import gc
@@ -324,6 +326,58 @@ def test_ckks_headroom_of_an_encrypted_encoding(gpu):
         budget, norm = _budgets(P, ctx, gpu, level, ct[None], sk, P.scheme_type.ckks, chunk)
         assert [int(w) for w in norm[0]] == _words(m, level)
         assert int(budget[0]) == _budget_of(m, big) and budget[0] > 0
+    del ctx
+    _release()
+
+
+@pytest.mark.parametrize("scheme", ["bfv", "bgv"])
+def test_the_three_tails_share_one_phase(scheme, gpu):
+    """One front end feeds the decrypt entries and the noise budget: on one strided batch of uniform ciphertexts (hyb12_a2, level 3,
+    cipher_size 3, batch 5 -- a short last phase group, and under bfv the per-ciphertext forward transforms -- stride 3 L N + 16) the
+    norm of the budget entry and the plaintexts of the decrypt entry are, word for word, those of the single-step entries applied to
+    the phase built from the earlier entries; chunk 0, 1 and 2."""
+    import torch
+    P, ctx = _ctx("hyb12_a2", gpu, T)
+    level, k, B, n = 3, 3, 5, ctx.n
+    ln = level * n
+    stride = k * ln + 16
+    qs = [int(q) for q in primes_of("hyb12_a2")[1]][:level]
+    rng = rng_for(9790 + len(scheme))
+    cts = np.stack([np.stack([uniform_poly(rng, qs, n) for _ in range(k)]) for _ in range(B)])
+    dense = P.to_device(cts, gpu)                                   # [B][k][L][N]
+    buf = _p64((B * stride,), gpu)
+    for b in range(B):
+        buf[b * stride:b * stride + k * ln] = dense[b].reshape(-1)
+    before = buf.clone()
+    sk = ctx.secret_key_powers(P.to_device(uniform_poly(rng, [int(q) for q in primes_of("hyb12_a2")[1]], n), gpu), k - 1)
+    phase = torch.empty((B, level, n), dtype=torch.int64, device=gpu)
+    if scheme == "bfv":     # forward NTT of c1, c2; the phase without c0; inverse NTT; + c0
+        ntt = dense.clone()
+        ntt[:, 0] = 0
+        for i in (1, 2):
+            part = ntt[:, i].contiguous()
+            ctx.nwt_2d_radix8_forward_inplace_batched(part, level, 0, B, ln)
+            ntt[:, i] = part
+        ctx.decrypt_phase_batched(level, ntt, sk, phase)
+        ctx.nwt_2d_radix8_backward_inplace_batched(phase, level, 0, B, ln)
+        for b in range(B):
+            ctx.add_rns_poly(phase[b], dense[b, 0].contiguous(), phase[b], level)
+    else:                   # the phase; inverse NTT
+        ctx.decrypt_phase_batched(level, buf, sk, phase, cipher_size=k, batch=B, strides=(stride, ln))
+        ctx.nwt_2d_radix8_backward_inplace_batched(phase, level, 0, B, ln)
+    bits, want_norm, want_plain = _p32((B,), gpu), _p64((B, level), gpu), _p64((B, n), gpu)
+    ctx.poly_infty_norm_batched(level, phase, bits, want_norm, scalar=T if scheme == "bfv" else 1)
+    for b in range(B):
+        (ctx.hps_decrypt_scale_and_round if scheme == "bfv" else ctx.decrypt_mod_t)(level, want_plain[b], phase[b])
+    decrypt = ctx.bfv_decrypt_batched if scheme == "bfv" else ctx.bgv_decrypt_batched
+    for chunk in (0, 1, 2):
+        budget, norm, plain = _p32((B,), gpu), _p64((B, level), gpu), _p64((B, n), gpu)
+        ctx.invariant_noise_budget_batched(level, buf, sk, getattr(P.scheme_type, scheme), budget, norm, cipher_size=k, batch=B,
+                                           stride=stride, chunk=chunk)
+        decrypt(level, buf, sk, plain, cipher_size=k, batch=B, strides=(stride, n), chunk=chunk)
+        assert torch.equal(norm, want_norm), f"{scheme} chunk {chunk}: the budget entry's norm is not the norm of the phase"
+        assert torch.equal(plain, want_plain), f"{scheme} chunk {chunk}: the decrypt entry's plaintexts are not the tail of the phase"
+        assert bool((budget != POISON32).all()) and bool((buf == before).all()), f"{scheme} chunk {chunk}"
     del ctx
     _release()
 

@@ -137,12 +137,12 @@ for scheme, (name, log_n, bits, size_p, level, plain_t) in SETS.items():
             G = min(batch, 4)
             rows.append({"scheme": scheme, "set": name, "level": level, "cipher_size": k, "batch": batch, "same_words": bool(same),
                          "entry_us_per_ct": statistics.median(te) / batch, "compose_us_per_ct": statistics.median(tc) / batch,
-                         "entry_min_us": min(te) / batch, "compose_min_us": min(tc) / batch,
+                         "entry_min_us": min(te) / batch, "compose_min_us": min(tc) / batch, "entry_max_us": max(te) / batch,
                          "phase_words_entry": k + (k - 1) / G + 1, "phase_words_compose": 4 * (k - 1) + 2})
             r = rows[-1]
             print(f"{scheme:5s} {name:10s} L={level} k={k} B={batch}: entry {r['entry_us_per_ct']:9.2f} us/ct  compose {r['compose_us_per_ct']:9.2f} us/ct  "
                   f"ratio {r['compose_us_per_ct'] / r['entry_us_per_ct']:.2f}  words {r['phase_words_entry']:.2f} vs {r['phase_words_compose']}  "
-                  f"same {same}", flush=True)
+                  f"same {same}  entry windows {r['entry_min_us']:.2f} .. {r['entry_max_us']:.2f}", flush=True)
     del ctx
     torch.cuda.empty_cache()
 print("device:", torch.cuda.get_device_name(0))

@@ -164,12 +164,13 @@ for scheme, name, log_n, bits, size_p, level, plain_t, counts in SETS:
                 tl.append(timed_us(loop, args.iters))
             row = {"scheme": scheme, "set": name, "level": level, "form": form, "count": count, "same_words": bool(same),
                    "entry_us_per_ct": statistics.median(te) / count, "loop_us_per_ct": statistics.median(tl) / count,
-                   "entry_min_us": min(te) / count, "loop_min_us": min(tl) / count}
+                   "entry_min_us": min(te) / count, "loop_min_us": min(tl) / count, "entry_max_us": max(te) / count}
             if form == "symmetric" and scheme == "ckks":
                 row["c0_words_entry"], row["c0_words_loop"] = 6, 12
             rows.append(row)
             print(f"{scheme:5s} {name:10s} L={level} {form:10s} count={count:2d}: entry {row['entry_us_per_ct']:9.2f} us/ct  "
-                  f"loop {row['loop_us_per_ct']:9.2f} us/ct  ratio {row['loop_us_per_ct'] / row['entry_us_per_ct']:.2f}  same {same}", flush=True)
+                  f"loop {row['loop_us_per_ct']:9.2f} us/ct  ratio {row['loop_us_per_ct'] / row['entry_us_per_ct']:.2f}  same {same}  "
+                  f"entry windows {row['entry_min_us']:.2f} .. {row['entry_max_us']:.2f}", flush=True)
             del ct_e, ct_l
     del ctx
     torch.cuda.empty_cache()

@@ -51,6 +51,9 @@ def seeds(label, count):
     return torch.from_numpy(W.derive_seeds(MASTER, label, count)).to(dev)
 
 
+legs = []   # the windows of every timed leg, in the order of the calls
+
+
 def timed(fn):
     """Median microseconds per call: windows of --iters calls between device events, after two warm-up calls."""
     for _ in range(2):
@@ -65,6 +68,8 @@ def timed(fn):
         b.record()
         b.synchronize()
         out.append(a.elapsed_time(b) * 1000.0 / args.iters)
+    print(f"windows of timed leg {len(legs)}: median {statistics.median(out):.2f} min {min(out):.2f} max {max(out):.2f} us", flush=True)
+    legs.append(out)
     return statistics.median(out)
 
 
