@@ -486,7 +486,9 @@ int pha_generate_one_kswitch_key(pha_context_t ctx, const uint64_t *sk_ntt, cons
 /* bfv_multiply_behz (src/evaluate.cu:447-548), the 2 x 2 case at the top data level: ct1, ct2 [2][Q][N] in
  * coefficient form -> dst [3][Q][N] in coefficient form (ct1 == ct2 takes the squaring kernels, like the
  * reference).  Needs pha_context_set_plain_modulus; the auxiliary base Bsk u {m_tilde} (src/rns.cu:392-560) and
- * its NTT tables are built on first use.
+ * its NTT tables are built on first use.  The plain modulus need NOT be below the data primes: the scale by t of step 6 is kept
+ * per limb as t mod q_i with its Shoup quotient (the reference keeps t itself, whose quotient floor(t 2^64 / q_i) does not fit 64
+ * bits once t >= q_i, and returns noise there); for t < every q_i the words are the reference's.
  * ALL the BFV multiply entries, single-pair and batched: the inputs are only read; every pha_bfv_multiply_* entry refuses a dst
  * that overlaps an input (status -1); in strict mode they and pha_bfv_mul_relin_hps_overq_leveled check both operands, named
  * "<entry> ct1" / "<entry> ct2" with the entry's own name (without the pha_ prefix).  A single-pair entry is its batched
@@ -495,7 +497,16 @@ int pha_bfv_multiply_behz(pha_context_t ctx, const uint64_t *ct1, const uint64_t
 /* bfv_multiply_hps with mul_tech_type::hps (src/evaluate.cu:674-818; bConv_HPS src/rns_bconv.cu:248-372;
  * scaleAndRound_HPS_QR_R src/rns.cu:1700-1746): same shapes as pha_bfv_multiply_behz.  The base R (|Q| + 1 primes
  * below the smallest q_i, src/rns.cu:687-693) and its tables are built on first use.  The double-precision
- * sums are fused multiply-add chains, as nvcc builds the reference's kernels by default. */
+ * sums are fused multiply-add chains, as nvcc builds the reference's kernels by default.
+ * Domain.  (1) No base R: when fewer than |Q| + 1 primes = 1 (mod 2N) lie between 2^(bits - 1) and the
+ * smallest q_i, the entry (and the hps_overq ones, which need |Q|) fails with logic_error "failed to find enough qualifying
+ * primes 2" (PHA_ERR_LOGIC), writes nothing and leaves the context usable.  (2) Room in R: the scaled tensor t d / Q must stay
+ * inside (-R / 2, R / 2); with uniform ciphertext words that holds when t sqrt(2N) 4/3 < R / Q (eight standard deviations), i.e.
+ * about t < q_min / (110 sqrt(N / 4096)) for equal-sized data primes and never for chains that mix sizes (R is taken below the
+ * SMALLEST q_i).  Outside it the entry still returns 0 and the reference's words, which decrypt to noise: use behz or hps_overq
+ * there.  (3) The carry of scaleAndRound_HPS_QR_R is reduced modulo r_0 once and then modulo each r_j from that value; the
+ * reference chains the reductions (rns.cu:1733), which makes about N (r_0 - r_|Q|) / r_0 coefficients per polynomial noise
+ * (one per product at 30-bit primes).  Wherever the reference's words are consistent across the R limbs these are the same. */
 int pha_bfv_multiply_hps(pha_context_t ctx, const uint64_t *ct1, const uint64_t *ct2, uint64_t *dst, void *stream);
 /* bfv_multiply_hps with mul_tech_type::hps_overq, no levels dropped (src/evaluate.cu:674-818, overq branches :745-751,
  * :790-792; bConv_BEHZ_var1 src/rns_bconv.cu:231-246; scaleAndRound_HPS_QlRl_Ql src/rns.cu:1748-1796).  Same shapes as

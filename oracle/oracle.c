@@ -1122,8 +1122,11 @@ void orc_bfv_multiply_behz(const orc_behz *b, const u64 *ct1, const u64 *ct2, u6
         u64 *xq = q1 + p * sq * n, *xb = b1 + p * sk * n;
         orc_nwt_backward(c, xq, sq, 0);
         for (size_t i = 0; i < sq; i++) {
-            const u64 ts = orc_compute_shoup(b->plain_t, c->q[i]);
-            for (size_t k = 0; k < n; k++) xq[i * n + k] = shoup(xq[i * n + k], b->plain_t, ts, c->q[i]);
+            /* The reference multiplies by t itself with compute_shoup(t, q_i) (src/context.cu:71-72, src/rns.cu:471): that
+             * quotient floor(t 2^64 / q_i) overflows 64 bits when t >= q_i, so the reference is undefined there (it returns
+             * noise).  t mod q_i is the same words for t < q_i and the intended product for every accepted t. */
+            const u64 tq = b->plain_t % c->q[i], ts = orc_compute_shoup(tq, c->q[i]);
+            for (size_t k = 0; k < n; k++) xq[i * n + k] = shoup(xq[i * n + k], tq, ts, c->q[i]);
         }
         for (size_t j = 0; j < sk; j++) {
             orc_ntt_inverse(xb + j * n, b->log_n, b->bsk[j], b->itw + j * n, b->itws + j * n, b->n_inv[j], b->n_inv_s[j]);
@@ -1274,7 +1277,11 @@ void orc_hps_destroy(orc_hps *h) {
     hpsconv_free(&h->q_to_r); hpsconv_free(&h->r_to_q); free(h->frac); free(h->div_mod_r); free(h);
 }
 /* DRNSTool::scaleAndRound_HPS_QR_R rns.cu:1700-1746: src [Q + R][N] coefficient form -> dst [R][N], scaled by t / Q and rounded;
- * nu accumulates by fused multiply-adds (nvcc's default -fmad), alpha is reduced IN PLACE across the R limbs (:1733) */
+ * nu accumulates by fused multiply-adds (nvcc's default -fmad).  The reference reduces alpha IN PLACE across the R limbs (:1733):
+ * limb j gets ((alpha mod r_0) mod r_1 ...) mod r_j.  Where only the first reduction subtracts anything, every limb holds
+ * alpha - k r_0 (a small error); where a later one does -- (alpha mod r_0) >= r_j, once in r_0 / (r_0 - r_|Q|) coefficients --
+ * the limbs after j disagree with the ones before and the coefficient is noise.  Restated with every limb reducing
+ * (alpha mod r_0) itself: the reference's words wherever they are consistent, the value it means elsewhere. */
 void orc_hps_scale_round_qr_r(const orc_hps *h, const u64 *x, u64 *dst) {
     const size_t n = h->n, sq = h->size_q, sr = h->size_r;
     for (size_t k = 0; k < n; k++) {
@@ -1288,8 +1295,9 @@ void orc_hps_scale_round_qr_r(const orc_hps *h, const u64 *x, u64 *dst) {
             for (size_t i = 0; i < sq; i++) cur += (u128)x[i * n + k] * tab[i];
             cur += (u128)x[(sq + j) * n + k] * tab[sq];
             const u64 v = barrett128(cur, rj, h->qr_mu[sq + j]);
-            alpha = barrett64(alpha, rj, h->qr_mu[sq + j][1]);
-            dst[j * n + k] = addmod(v, alpha, rj);
+            const u64 a = barrett64(alpha, rj, h->qr_mu[sq + j][1]);
+            if (j == 0) alpha = a;
+            dst[j * n + k] = addmod(v, a, rj);
         }
     }
 }

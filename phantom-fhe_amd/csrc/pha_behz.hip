@@ -192,6 +192,17 @@ struct ScaleRoundArgs {
     uint32_t size_q, size_r, aux0, n;
     size_t dst_stride = 0, src_stride = 0;   // polynomial blockIdx.y
 };
+// The carry alpha = floor(nu) < |Q| max q of one coefficient, modulo r_j.  The reference reduces it in place across the R limbs
+// (rns.cu:1733): limb j receives ((alpha mod r_0) mod r_1 ...) mod r_j.  The first reduction is harmless (every limb then holds
+// alpha - k r_0, a change of the result by less than |Q| r_0), but a later one that subtracts anything -- (alpha mod r_0) >= r_j, R
+// descends from the smallest q -- reaches the limbs after j only: their residues then belong to no common integer and the
+// coefficient is noise (once in r_0 / (r_0 - r_|Q|) coefficients: never at 60 bits, every few products at 36, every product at 30).
+// Here every limb reduces alpha mod r_0 itself: the reference's words wherever those are consistent, the right ones elsewhere.
+__device__ __forceinline__ u64 hps_carry(u64 &alpha, uint32_t j, const DModulus &m) {
+    const u64 a = barrett64(alpha, m.value, m.ratio1);
+    if (j == 0) alpha = a;
+    return a;
+}
 // QPAD >= size_q: the Q residues of the coefficient stay in registers across the R limbs.  SPLIT: Q primes <= 60 bits and R
 // primes <= 62: the carry-free dot product (residues cut at 30 bits, table entries at 31)
 template <int QPAD, bool SPLIT>
@@ -230,8 +241,7 @@ __global__ __launch_bounds__(256) void hps_scale_round_kernel(ScaleRoundArgs k) 
         }
         mac128(k.src[(size_t)(k.size_q + j) * k.n + coeff], tab[k.size_q], lo, hi);
         const u64 v = barrett128(lo, hi, m);
-        alpha = barrett64(alpha, m.value, m.ratio1);   // reduced IN PLACE across the R limbs, as rns.cu:1733 does
-        k.dst[(size_t)j * k.n + coeff] = add_mod(v, alpha, m.value);
+        k.dst[(size_t)j * k.n + coeff] = add_mod(v, hps_carry(alpha, j, m), m.value);
     }
 }
 __global__ __launch_bounds__(256) void hps_scale_round_wide_kernel(ScaleRoundArgs k) {  // size_q > 32
@@ -248,8 +258,7 @@ __global__ __launch_bounds__(256) void hps_scale_round_wide_kernel(ScaleRoundArg
         for (uint32_t i = 0; i < k.size_q; i++) mac128(k.src[(size_t)i * k.n + coeff], tab[i], lo, hi);
         mac128(k.src[(size_t)(k.size_q + j) * k.n + coeff], tab[k.size_q], lo, hi);
         const u64 v = barrett128(lo, hi, m);
-        alpha = barrett64(alpha, m.value, m.ratio1);
-        k.dst[(size_t)j * k.n + coeff] = add_mod(v, alpha, m.value);
+        k.dst[(size_t)j * k.n + coeff] = add_mod(v, hps_carry(alpha, j, m), m.value);
     }
 }
 

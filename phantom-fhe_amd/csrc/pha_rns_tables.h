@@ -288,10 +288,13 @@ inline BehzTables behz_tables(const std::vector<u64> &primes, uint32_t size_q, u
         t.inv_mt_mod_bsk.push_back(h_pair(h_invmod(m_tilde % p, p), p));   // :537-546
     }
     for (uint32_t i = 0; i < size_q; i++) t.prod_b_mod_q.push_back(prod_mod(primes, b, primes[i]));
-    // t (:467-479) by limb of a [Q || Bsk] buffer: one inverse transform over both bases multiplies by it
+    // t (:467-479) by limb of a [Q || Bsk] buffer: one inverse transform over both bases multiplies by it.  Stored reduced: the
+    // reference keeps t itself, whose Shoup quotient floor(t 2^64 / q_i) does not fit 64 bits once t >= q_i (t < 2^60 may exceed a
+    // data prime; the Bsk primes have 61 bits).  For t < q_i the words are the reference's.
     for (uint32_t i = 0; i < size_q + size_bsk; i++) {
-        t.t_qb.push_back(plain_t);
-        t.t_qb_shoup.push_back(h_shoup(plain_t, primes[i < size_q ? i : aux0 + i - size_q]));
+        const u64 prime = primes[i < size_q ? i : aux0 + i - size_q];
+        t.t_qb.push_back(plain_t % prime);
+        t.t_qb_shoup.push_back(h_shoup(plain_t % prime, prime));
     }
     const u64 inv_q_mt = h_invmod(prod_mod(primes, q, m_tilde), m_tilde);
     t.neg_inv_prod_q_mod_mt = h_pair((m_tilde - inv_q_mt) % m_tilde, m_tilde);

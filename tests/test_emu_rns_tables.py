@@ -371,3 +371,35 @@ def test_behz_tables(emu):
     neg = (-pow(big_q, -1, mt)) % mt
     inv = pow(big_b, -1, m_sk)
     assert pairs(sc) == [(neg, shoup(neg, mt)), (inv, shoup(inv, m_sk))]
+
+
+def test_behz_scale_by_a_plain_modulus_above_the_data_primes(emu):
+    """t = T59 (59 bits) on a chain with 40-bit limbs: the per-limb factor of the scaled inverse transform is t mod q_i with ITS Shoup
+    quotient, floor((t mod q_i) 2^64 / q_i) < 2^64.  The reference keeps t itself, whose quotient floor(t 2^64 / q_i) needs 83 bits
+    there.  For a limb above t (the 60-bit one, and the 61-bit Bsk primes) the words are t and its quotient, as before."""
+    log_n, chain, size_p = primes_of("hyb12_a2")
+    P0, size_q, two_n = [int(p) for p in chain], len(chain) - size_p, 2 << log_n
+    t59 = primes_down(2 ** 59 - two_n + 1, two_n, 3)[2]
+    assert t59.bit_length() == 59 and sum(1 for q in P0[:size_q] if q < t59) == 5 and P0[0] > t59
+    big_q = prod(P0[:size_q])
+    size_b = size_q + (1 if 32 + t59.bit_length() + big_q.bit_length() >= 61 * size_q + 61 else 0)
+    pq = a64(P0[:size_q])
+    assert emu.emu_behz_size_b(ptr(pq), C.c_uint32(size_q), C.c_uint64(t59)) == size_b
+    found = primes_down(2 ** 61 - two_n + 1, two_n, size_b + 1)
+    aux0 = len(P0)
+    P = P0 + found[1:] + [found[0], 2 ** 32]
+    nbsk = size_b + 1
+    pb, wb, wq, tqb, sc = np.zeros(4 * nbsk, U64), np.zeros(nbsk, U64), np.zeros(size_q, U64), np.zeros(2 * (size_q + nbsk), U64), np.zeros(4, U64)
+    pa = a64(P)
+    emu.emu_behz(ptr(pa), sz(len(P)), C.c_uint32(size_q), C.c_uint32(aux0), C.c_uint32(size_b), C.c_uint64(t59), ptr(pb), ptr(wb), ptr(wq), ptr(tqb), ptr(sc))
+    limbs = P0[:size_q] + [P[aux0 + j] for j in range(nbsk)]
+    want = [t59 % p for p in limbs]
+    assert [int(x) for x in tqb] == want + [shoup(v, p) for v, p in zip(want, limbs)]
+    assert all(shoup(t59, p) >= 2 ** 64 for p in P0[1:size_q]) and all(shoup(v, p) < 2 ** 64 for v, p in zip(want, limbs))
+    # what the pair is for: x * (t mod q) by Shoup's method equals x t mod q for the extreme and some random x
+    r = np.random.default_rng(59)
+    for v, p in zip(want, limbs):
+        for x in [0, 1, p - 1] + [int(y) for y in r.integers(0, p, 5)]:
+            hi = (x * shoup(v, p)) >> 64
+            got = (x * v - hi * p) % 2 ** 64
+            assert (got - p if got >= p else got) == x * t59 % p

@@ -255,7 +255,7 @@ def test_behz_steps(name, plain_t, gpu):
 
 @pytest.mark.parametrize("name,plain_t", [("c1_bfv4096", 65537), ("bfv13_50", 1032193), ("c4_bfv15", 1032193)])
 def test_hps_scale_round_qr_r(name, plain_t, gpu):
-    """scaleAndRound_HPS_QR_R (src/rns.cu:1700-1746) vs the oracle (same fma chain, alpha reduced in place across the R limbs)."""
+    """scaleAndRound_HPS_QR_R (src/rns.cu:1700-1746) vs the oracle (same fma chain, alpha reduced modulo r_0 and then modulo each R limb: DESIGN.md 4.8a1)."""
     import phantom_fhe_amd as P
     log_n, primes, size_p = primes_of(name)
     n = 1 << log_n

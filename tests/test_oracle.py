@@ -372,9 +372,10 @@ def test_bfv_hps_multiply_decrypts_to_the_product(name, plain_t):
     """BFV HPS multiply (mul_tech hps, src/evaluate.cu:674-818) pinned by its meaning, like the BEHZ test; the two
     variants give different ciphertexts (different rounding) that decrypt to the same product.  The base R the
     reference picks (|Q| + 1 primes below the smallest q_i, rns.cu:690-693) only covers t*N*Q when the data primes
-    have about the same size, hence the uniform chains here.  The reference's scale-and-round kernel reduces its
-    carry `alpha` in place across the R limbs (rns.cu:1733), which makes limbs j >= 1 wrong by a multiple of
-    (r_0 mod r_j): noise of about one prime's size, far below Q/t; restated as is."""
+    have about the same size, hence the uniform chains here.  The scale-and-round reduces its carry `alpha` modulo
+    r_0 first, which makes every limb wrong by the same multiple of r_0: noise of about one prime's size, far below
+    Q/t.  (The reference chains the reductions across the R limbs, rns.cu:1733; where a later one subtracts as well
+    the coefficient is noise -- DESIGN.md 4.8a1 -- so every limb reduces alpha mod r_0 itself here.)"""
     log_n, primes, size_p = primes_of(name)
     n = 1 << log_n
     size_q = len(primes) - size_p
